@@ -8,15 +8,19 @@ reference's train.py:231-232 sess.run.  N=1 workload: BASELINE configs[1]
 (fp32, batch 64, one GPU).  Synthetic fundus-shaped inputs (jr.synth),
 resident in HBM before timing; Keras-default random init (App. C Q2).
 
-  python bench.py [--gpus N --steps K --warmup W --dtype f32]
+  python bench.py [--gpus N --steps K --warmup W --dtype f32] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
-Rank 0 prints ONE JSON line.  `roofline` is for the conv implicit-GEMM
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the
+steps, writes its outputs (--dump-outputs) and prints the line; `roofline`,
+`hbm_families` and `cpu_baseline` are null / absent there.  --full adds them
+after the timed region: `roofline` is for the conv implicit-GEMM
 family (the dominant kernels): algorithmic conv FLOPs per step / summed conv
 op time per step, both from an instrumented pass (HIP events around every
-conv call on the engine stream) run right after the timed region.
-`cpu_baseline` times oracle/inception_ref.py (torch-CPU fp32 restatement,
-kind "port") on the host cores for a bounded sample.
+conv call on the engine stream); `hbm_families` the achieved HBM rates of the
+bandwidth-bound kernel families; `cpu_baseline` times oracle/inception_ref.py
+(torch-CPU fp32 restatement, kind "port") on the host cores for a bounded
+sample.  --no-roofline / --no-cpu-baseline take pieces out of a --full run.
 """
 from __future__ import annotations
 
@@ -78,6 +82,14 @@ def parse():
     ap.add_argument("--tiles", default="pinned", choices=["pinned", "heuristic", "autotune"],
                     help="conv tiles: the committed MI355X table of this workload (train.py's default; "
                          "deterministic, bit-stable across boxes), the planner heuristic, or timed autotuning")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what the headline figure does not need: the conv "
+                         "roofline, the per-family HBM rates and the CPU baseline (ensemble mode: the grouped-conv "
+                         "roofline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "loss, logits, predictions, and fixed seeded samples of the updated parameters and of the "
+                         "gradients (train); the inputs are seeded, so two builds compare output for output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=64)
     ap.add_argument("--cpu-steps", type=int, default=2)
@@ -399,6 +411,9 @@ def ensemble_bench(args) -> dict:
         t_all = max_over_ranks(dist, t_mine)
         n_mine = labels.shape[0]
         assert preds[0].shape[0] == n_mine and len(ids) == -(-n_mine // B)
+        if args.dump_outputs and rank == 0:      # this rank's share of the timed pass: [members, images, units]
+            dump_outputs(args.dump_outputs, {"predictions": np.stack([np.asarray(p) for p in preds]),
+                                             "labels": labels})
         ds = lib.dataset.initialize_dataset(d, B, num_workers=evaluate.NUM_WORKERS, prefetch_buffer_size=2 * B,
                                             image_dim=[res, res], decode_dtype="uint8", shard=(rank, world))
         t0 = time.perf_counter()
@@ -420,7 +435,7 @@ def ensemble_bench(args) -> dict:
             e.synchronize()
         t_gpu = time.perf_counter() - t0
         roof = None
-        if rank == 0 and not args.per_member and not args.no_roofline:
+        if rank == 0 and args.full and not args.per_member and not args.no_roofline:
             flops, tconv, nconv = grouped_conv_roofline(engines)
             peak = PEAK_TFLOPS[math if math in ("x8", "x8p", "x6h") else args.dtype]
             ach = flops / tconv / 1e12
@@ -477,6 +492,25 @@ def _stdout_for_json_only() -> int:
 
 def emit(fd: int, out: dict) -> None:
     os.write(fd, (json.dumps(out) + "\n").encode())
+
+
+DUMP_SAMPLE = 1 << 22      # elements kept of a parameter-sized array (16 MiB as float32)
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  An
+    array of more than DUMP_SAMPLE elements is written as a fixed sample of
+    them (sorted indices drawn without replacement from a generator seeded
+    with the array's size, so two runs and two builds keep the same
+    elements); the whole dump stays far below 64 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"outputs ({', '.join(arrays)}) in {out_dir}")
 
 
 def heartbeat(period: float = 50.0) -> None:
@@ -555,6 +589,12 @@ def main():
     loss = eng.loss_value() if train else float(np.mean(eng.predictions()))
     if not np.isfinite(loss):
         raise SystemExit(f"non-finite {'loss' if train else 'prediction'} {loss}")
+    dumped = None
+    if args.dump_outputs and rank == 0:      # what the last timed step left for its caller
+        dumped = {"logits": eng.logits[:B * eng.units].float().cpu().numpy().reshape(B, eng.units),
+                  "predictions": eng.predictions(B)}
+        if train:
+            dumped.update(loss=np.array([loss]), params=eng.params_numpy(), grads=eng.grads_numpy())
     overlap = None
     if ar is not None:          # after the timed region: one traced step (timing events per issue point)
         ar.trace = True
@@ -562,6 +602,8 @@ def main():
         eng.synchronize()
         overlap = ar.overlap_ms()
         ar.trace = False
+    if args.dump_outputs and rank == 0:      # (the traced step above, if any, came after this state was read)
+        dump_outputs(args.dump_outputs, dumped)
 
     devices = len({int(v) for v in gather_devices(dist, local)})
     rehearsal = world > 1 and (devices < world or dist.get_backend() != "nccl")
@@ -571,7 +613,7 @@ def main():
         ms = elapsed / args.steps * 1e3
         log(f"timed {args.steps} steps: {ms:.3f} ms/step")
         roof = None
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             flops, tconv, nconv = conv_roofline(eng)
             ach = flops / tconv / 1e12
             peak = PEAK_TFLOPS[math if math in ("x8", "x8p", "x6h") else args.dtype]
@@ -582,7 +624,7 @@ def main():
                     "algorithmic_gflop_per_step": round(flops / 1e9, 1)}
             if train:
                 roof.update(pmc_traffic(args.dtype, B, res, math))
-        hbm = None if args.no_roofline else family_rates(eng)
+        hbm = family_rates(eng) if args.full and not args.no_roofline else None
         out = {
             "metric": (f"train images/sec, Inception-v3 {res}^2 bs{B}/GPU" if train else
                        f"eval images/sec, Inception-v3 {res}^2 bs{B}/GPU (one ensemble member, batch-stat BN)"),
@@ -609,7 +651,7 @@ def main():
             "roofline": roof,
             "hbm_families": hbm,
         }
-        if not args.no_cpu_baseline and world == 1 and train:
+        if args.full and not args.no_cpu_baseline and world == 1 and train:
             log("cpu baseline")
             out["cpu_baseline"] = cpu_baseline(args, res)
         emit(json_fd, out)

@@ -6,7 +6,7 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"; mkdir -p gpurun_out/r6
 for dt in ${ENS_DTYPES:-bf16 f32}; do
-  timeout -k 10 560 python bench.py --mode ensemble --members 10 --images 57000 --dtype $dt \
+  timeout -k 10 560 python bench.py --full --mode ensemble --members 10 --images 57000 --dtype $dt \
     > gpurun_out/r6/ens57k_$dt.json 2> gpurun_out/r6/ens57k_$dt.log || exit 1
   cat gpurun_out/r6/ens57k_$dt.json
 done

@@ -9,7 +9,7 @@ ok() { [ "$1" -eq 0 ] || [ "$1" -eq 1 ]; }
 timeout -k 10 500 python -u -m pytest tests/test_gpu_ensemble.py tests/test_gpu_eval299.py -v -s --timeout 300 \
   --timeout-method thread > $out/tests.log 2>&1
 rc=$?; echo "ensemble tests rc=$rc"; grep -E "FAILED|passed|failed|config 4" $out/tests.log | tail -12; ok $rc || exit $rc
-timeout -k 10 560 python bench.py --mode ensemble --members 10 --images 57000 > $out/ens57k_f32x6h.json 2> $out/ens57k.log || exit 1
+timeout -k 10 560 python bench.py --full --mode ensemble --members 10 --images 57000 > $out/ens57k_f32x6h.json 2> $out/ens57k.log || exit 1
 cat $out/ens57k_f32x6h.json
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 200 rocprofv3 --kernel-trace -d $R/$out/prof -o run --output-format csv -- \

@@ -5,12 +5,12 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"; out=gpurun_out/meas; mkdir -p $out
-timeout -k 10 400 python bench.py > $out/f32_line.json 2> $out/f32_line.log || exit 1
+timeout -k 10 400 python bench.py --full > $out/f32_line.json 2> $out/f32_line.log || exit 1
 cat $out/f32_line.json
-timeout -k 10 300 python bench.py --dtype bf16 --no-cpu-baseline > $out/bf16_line.json 2> $out/bf16_line.log || exit 1
+timeout -k 10 300 python bench.py --full --dtype bf16 --no-cpu-baseline > $out/bf16_line.json 2> $out/bf16_line.log || exit 1
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/$out/prof -o run --output-format csv -- \
-  python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $R/$out/prof.log 2>&1 || exit 1
+  python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $R/$out/prof.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/$out/prof1 -o run --output-format csv -- \
   python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --lanes 1 > $R/$out/prof1.log 2>&1 || exit 1
 cd $R
