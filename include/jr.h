@@ -471,6 +471,40 @@ int jr_u8_to_f32_scaled(const uint8_t* src, void* dst, int dtype, int64_t n, voi
  * wide, see jr_conv2d_fwd on c_in % 4 != 0). */
 int jr_image_u8_to_nhwc(const uint8_t* src, void* dst, int dtype, int64_t pixels, int32_t c,
                         int32_t dst_stride, void* stream);
+/* Training augmentation fused into the input conversion (not in the
+ * reference, which trains unaugmented): uint8 [n][h][w][3] images -> dst
+ * [n][h][w][dst_stride] of the path dtype (JR_F32 or JR_BF16), image i
+ * transformed with params[i], in fp32, every operation rounded on its own:
+ *  0. x = f32(u8) * f32(1/255)                      (jr_image_u8_to_nhwc)
+ *  1. flags bit 0 mirrors left-right, bit 1 up-down (pure indexing)
+ *  2. hue and saturation, skipped when hue_delta == 0 && sat_factor == 1:
+ *     v = max(r,g,b), m = min(r,g,b), c = v - m, s = v > 0 ? c / v : 0,
+ *     h6 = 0 if c == 0, else (g-b)/c if v == r, else (b-r)/c + 2 if v == g,
+ *     else (r-g)/c + 4;  h6' = (h6 + 6 hue_delta) mod 6 in [0, 6),
+ *     s' = clamp(s sat_factor, 0, 1);  k(n) = (h6' + n) mod 6,
+ *     f(n) = v - v s' clamp(min(k, 4 - k), 0, 1), (r,g,b) = (f(5), f(3), f(1));
+ *     IEEE divisions
+ *  3. contrast, skipped when contrast_factor == 1:
+ *     x = (x - mean_c) contrast_factor + mean_c, mean_c this image's mean of
+ *     channel c over h*w after stage 2 (fp32 partials of 2048 pixels each,
+ *     combined in fp64 in a fixed order, no atomics: bitwise reproducible
+ *     and independent of n and of the image's slot in the batch)
+ *  4. brightness, skipped when brightness_delta == 0: x += brightness_delta
+ *  5. clamp to [0, 1]; channels [3, dst_stride) are written as 0.
+ * The identity table (0, 1, 1, 0, flags 0) gives jr_image_u8_to_nhwc's
+ * output bit for bit.  params: n entries in DEVICE memory.  Two launches on
+ * the stream (the channel sums, then the transform); ws: at least
+ * jr_augment_workspace_size(n, h, w) bytes, 4-byte aligned.  c must be 3,
+ * dst_stride >= 3, n <= 65535. */
+typedef struct jr_augment_param {   /* 32 bytes, one per image */
+  float hue_delta, sat_factor, contrast_factor, brightness_delta;
+  uint32_t flags;                   /* bit0 flip left-right, bit1 flip up-down */
+  uint32_t reserved[3];             /* must be 0 */
+} jr_augment_param;
+size_t jr_augment_workspace_size(int32_t n, int32_t h, int32_t w);
+int jr_image_u8_augment_nhwc(const uint8_t* src, void* dst, int dtype, int32_t n, int32_t h, int32_t w,
+                             int32_t c, int32_t dst_stride, const jr_augment_param* params,
+                             void* ws, size_t ws_bytes, void* stream);
 /* acc[0] += sum (p - y)^2, acc[1] += n   (tf.metrics.mean_squared_error,
  * train.py:175-177) */
 int jr_brier_accumulate(const float* probs, const float* labels, int32_t n, double* acc, void* stream);

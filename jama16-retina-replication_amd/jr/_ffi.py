@@ -85,6 +85,12 @@ class BnPartials(Structure):
                 ("single_stage", c_int32)]
 
 
+class AugmentParam(Structure):
+    """include/jr.h jr_augment_param: one image's augmentation (jr.augment builds the tables)."""
+    _fields_ = [("hue_delta", c_float), ("sat_factor", c_float), ("contrast_factor", c_float),
+                ("brightness_delta", c_float), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
 class PoolDesc(Structure):
     _fields_ = [(n, c_int32) for n in (
         "n", "h", "w", "c", "ho", "wo", "x_c_off", "x_c_stride", "y_c_off", "y_c_stride")]
@@ -196,6 +202,9 @@ _SIGS = {
     "jr_cast_bf16_to_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "jr_u8_to_f32_scaled": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "jr_image_u8_to_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int32, c_int32, c_void_p]),
+    "jr_augment_workspace_size": (c_size_t, [c_int32, c_int32, c_int32]),
+    "jr_image_u8_augment_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     "jr_brier_accumulate": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "jr_crc32c": (ctypes.c_uint32, [c_void_p, c_size_t, ctypes.c_uint32]),
     "jr_masked_crc32c": (ctypes.c_uint32, [c_void_p, c_size_t]),
@@ -296,7 +305,7 @@ def call(name: str, *args) -> int:
     lib = load()
     rc = getattr(lib, name)(*args)
     if isinstance(rc, int) and name not in ("jr_conv2d_workspace_size", "jr_bn_workspace_size",
-                                            "jr_bn_relu_bwd_maxpool_workspace_size",
+                                            "jr_bn_relu_bwd_maxpool_workspace_size", "jr_augment_workspace_size",
                                             "jr_conv2d_get_config", "jr_conv2d_num_configs", "jr_conv2d_config_generation",
                                             "jr_conv_weights_bf16_tiles"):
         check(name, rc)

@@ -1106,9 +1106,11 @@ class Engine:
             stream.wait_event(ev)
 
     # ------------------------------------------------------------------- data
-    def set_batch(self, images, labels=None, n: Optional[int] = None) -> int:
+    def set_batch(self, images, labels=None, n: Optional[int] = None, augment=None) -> int:
         """Copy a batch (NHWC float32, or uint8 to be scaled by 1/255) into the
-        input buffer.  Returns the batch size."""
+        input buffer.  Returns the batch size.  augment: a jr.augment table
+        (one jr_augment_param per image) -- the uint8 batch then goes through
+        jr_image_u8_augment_nhwc (training only; None: no augmentation)."""
         B = int(images.shape[0]) if n is None else n
         if B > self.batch:
             raise ValueError(f"batch {B} > planned {self.batch}")
@@ -1118,7 +1120,22 @@ class Engine:
         with torch.cuda.stream(self.stream):
             x = torch.as_tensor(images)
             pixels = B * ib.h * ib.w
-            if x.dtype == torch.uint8:
+            if augment is not None:
+                if x.dtype != torch.uint8:
+                    raise ValueError("augment needs a uint8 batch (float batches are not augmented)")
+                from . import augment as _augment
+                tab = _augment.as_table(augment, B)
+                if getattr(self, "_aug_ws", None) is None:   # once: sized for the planned batch
+                    nbytes = int(self.lib.jr_augment_workspace_size(self.batch, ib.h, ib.w))
+                    self._aug_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                    self._aug_tab = torch.empty(self.batch * tab.dtype.itemsize, dtype=torch.uint8, device=self.device)
+                self._aug_tab[:tab.nbytes].copy_(torch.from_numpy(tab.view(np.uint8)), non_blocking=True)
+                xd = x.to(self.device, non_blocking=True).reshape(-1)
+                _ffi.check("jr_image_u8_augment_nhwc", self.lib.jr_image_u8_augment_nhwc(
+                    xd.data_ptr(), self.acts[self.g.input_buf].data_ptr(), self.dt, B, ib.h, ib.w, ib.c,
+                    self.in_stride, self._aug_tab.data_ptr(), self._aug_ws.data_ptr(), self._aug_ws.numel(), self._s))
+                self._keep_u8 = xd
+            elif x.dtype == torch.uint8:
                 xd = x.to(self.device, non_blocking=True).reshape(-1)
                 _ffi.check("jr_image_u8_to_nhwc", self.lib.jr_image_u8_to_nhwc(
                     xd.data_ptr(), self.acts[self.g.input_buf].data_ptr(), self.dt, pixels, ib.c,

@@ -92,9 +92,10 @@ class Session:
         self.engine.forward(B)
         return self.engine.predictions(B)
 
-    def train_batch(self, images, labels) -> tuple:
-        """train.py:231-232: one step; returns (global_step, xent, probs)."""
-        B = self.engine.set_batch(images, labels)
+    def train_batch(self, images, labels, augment=None) -> tuple:
+        """train.py:231-232: one step; returns (global_step, xent, probs).
+        augment: a jr.augment table for this (uint8) batch, or None."""
+        B = self.engine.set_batch(images, labels, augment=augment)
         step = self.global_step
         self.engine.train_step(B, allreduce=getattr(self, "allreduce", None))
         self.global_step += 1

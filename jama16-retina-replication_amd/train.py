@@ -89,7 +89,43 @@ def build_parser():
                         "summation order exactly")
     p.add_argument("--shuffle_seed", type=int, default=None)
     p.add_argument("--max_steps_per_epoch", type=int, default=None)
+    # on-device training augmentation (jr.augment; not in the reference: off by default)
+    p.add_argument("--augment", action="store_true",
+                   help="augment every training batch on the GPU: random flips, hue, saturation, contrast and "
+                        "brightness jitter, clamped to [0, 1] (validation and the final sweep are never augmented)")
+    p.add_argument("--augment_seed", type=int, default=0,
+                   help="seed of the augmentation draws (rank r draws from PCG64([seed, r]))")
+    p.add_argument("--augment_hue", type=float, default=None, help="hue shift range +-H in turns (default 0.2)")
+    p.add_argument("--augment_saturation", type=_range_arg, default=None, metavar="LO,HI",
+                   help="saturation factor range (default 0.5,1.5)")
+    p.add_argument("--augment_contrast", type=_range_arg, default=None, metavar="LO,HI",
+                   help="contrast factor range (default 0.5,1.5)")
+    p.add_argument("--augment_brightness", type=float, default=None,
+                   help="brightness shift range +-B of the [0, 1] pixel range (default 0.125)")
+    p.add_argument("--no_augment_flip", action="store_true", help="no random left-right / up-down flips")
     return p
+
+
+def _range_arg(text):
+    """'LO,HI' -> (lo, hi)."""
+    try:
+        lo, hi = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected LO,HI, got {text!r}")
+    return lo, hi
+
+
+def augment_spec(args):
+    """The jr.augment.AugmentSpec of the --augment* flags (None: --augment is off)."""
+    if not args.augment:
+        return None
+    from jr.augment import AugmentSpec
+    over = {"flip": not args.no_augment_flip}
+    for key in ("hue", "saturation", "contrast", "brightness"):
+        v = getattr(args, "augment_" + key)
+        if v is not None:
+            over[key] = v
+    return AugmentSpec(**over)
 
 
 def status_line(epoch, num_epochs, batch_num, xent, i_step=None):
@@ -201,6 +237,10 @@ Use SGD: {bool(args.vanilla_sgd)}
         engine.set_tile_table(table)
     sess = Session(engine, thresholds, NUM_THRESHOLDS, KEPSILON)
     sess.rank = rank
+    # one parameter table per training batch, each rank from its own stream
+    aug_spec = augment_spec(args)
+    aug_rng = np.random.Generator(np.random.PCG64([args.augment_seed, rank])) if aug_spec else None
+    aug_meta = {"augment": {"spec": aug_spec.to_meta(), "seed": args.augment_seed}} if aug_spec else {}
     if dist:
         from jr.dist import BucketAllReduce
         sess.allreduce = BucketAllReduce(engine, world)
@@ -247,7 +287,12 @@ Use SGD: {bool(args.vanilla_sgd)}
                     break
                 if args.max_steps_per_epoch is not None and batch_num >= args.max_steps_per_epoch:
                     break
-                i_global, xent, probs = sess.train_batch(images, labels)
+                if aug_spec is not None:
+                    from jr import augment
+                    i_global, xent, probs = sess.train_batch(images, labels,
+                                                             augment.draw(aug_spec, aug_rng, len(images)))
+                else:
+                    i_global, xent, probs = sess.train_batch(images, labels)
                 sess.update(labels, probs, "brier")
                 if rank == 0:
                     print(status_line(epoch, args.num_epochs, batch_num, xent, i_global), end="\r")
@@ -275,7 +320,7 @@ Use SGD: {bool(args.vanilla_sgd)}
             if rank == 0:
                 print(f"New peak auc reached: {val_auc:10.8}")
                 checkpoint.save(args.save_model_path, engine.g, engine.params_numpy(),
-                                {"epoch": epoch, "val_auc": float(val_auc), "tile_table": engine.tile_table()})
+                                {"epoch": epoch, "val_auc": float(val_auc), "tile_table": engine.tile_table(), **aug_meta})
             saved = True
             waited_epochs = 0
 
