@@ -27,7 +27,6 @@ import ctypes
 import dataclasses
 import json
 import os
-import weakref
 from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -36,7 +35,7 @@ import torch
 from . import _ffi
 from .inception import BN_EPS, Graph, PoolNode, build_inception_v3
 from .init import init_params
-from .lanes import Call, node_lanes, schedule
+from .lanes import Build, Call, Lanes, node_lanes, schedule
 from .plan import ConvUnit, build_plan
 
 DTYPES = {"f32": _ffi.JR_F32, "bf16": _ffi.JR_BF16}
@@ -81,33 +80,29 @@ def pinned_tile_table(conv_math: str, batch: int, height: int, width: int, train
     return None
 
 
-class Engine:
-    """One model replica on one GPU (one process per GPU)."""
+class Replica:
+    """What jr.Engine and jr.EnsembleEngine (jr.ensemble) share: the device
+    and library, arithmetic codes, the launch plan, the lanes, and the
+    tables and uploads both build the same way (members: tensors are
+    member-major; jr.Engine is one member)."""
+    members = 1
 
-    def __init__(self, batch: int, height: int = 299, width: int = 299, units: int = 1,
-                 device: int | torch.device = 0, dtype: str = "f32", train: bool = True,
-                 optimizer: str = "nesterov", lr: float = 3e-3, momentum: float = 0.9,
-                 head: str = "sigmoid", seed: int = 0, graph: Optional[Graph] = None,
-                 autotune: bool = False, tiles: str = "pinned", fuse_siblings: bool = True, lanes: int = 2,
-                 conv_math: Optional[str] = None, defer_wgrad: Optional[bool] = None, fuse_pool: Optional[bool] = None,
-                 fold_stats: Optional[bool] = None):
+    def __init__(self, graph: Graph, device, dtype: str, conv_math: Optional[str], maths: Tuple[str, ...], head: str,
+                 fuse_siblings: bool, fuse_pool: Optional[bool], lanes: int, priorities=()):
         if dtype not in DTYPES:
             raise ValueError(f"dtype must be one of {sorted(DTYPES)}")
         if conv_math is None:            # fp32 default: x8 (fp32-accurate, on the bf16 matrix cores)
             conv_math = "x8" if dtype == "f32" else "bf16"
-        if (dtype == "f32" and conv_math not in ("f32", "x8", "x8p", "x6h")) or (dtype == "bf16" and conv_math != "bf16"):
-            raise ValueError("conv_math: 'x8', 'x8p', 'x6h' or 'f32' for dtype f32 (x8 = JR_F32_X8, x8p = JR_F32_X8P "
-                             "on pre-split operand planes, x6h = JR_F32_X6H scaled fp16 split, f32 = fp32 MFMA); "
-                             "'bf16' for dtype bf16")
+        if conv_math not in (maths if dtype == "f32" else ("bf16",)):
+            raise ValueError(f"conv_math: one of {maths} for dtype f32 (x8 = JR_F32_X8, x8p = JR_F32_X8P on pre-split "
+                             "operand planes, x6h = JR_F32_X6H scaled fp16 split, f32 = fp32 MFMA); 'bf16' for bf16")
         if not torch.cuda.is_available():
-            raise RuntimeError("jr.Engine needs a ROCm GPU (libjr has no CPU path)")
+            raise RuntimeError(f"jr.{type(self).__name__} needs a ROCm GPU (libjr has no CPU path)")
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         _ffi.init(self.device.index or 0)
         self.lib = _ffi.load()
-        self.g = graph or build_inception_v3(height, width, units)
-        self.batch = batch
-        self.dt = DTYPES[dtype]
-        self.dtype = dtype
+        self.g, self.units = graph, graph.units
+        self.dtype, self.dt = dtype, DTYPES[dtype]
         # dtype code of the convolution calls: JR_F32_X8 keeps every tensor
         # fp32 and forms the GEMM products on the bf16 matrix cores from an
         # exact three-way split (jr.h); everything else runs self.dt
@@ -120,48 +115,182 @@ class Engine:
         # max |beta| (Samuelson), beta guarded on the device (jr.h)
         self.x6h = conv_math == "x6h"
         self.cdt = {"x8": _ffi.JR_F32_X8, "x8p": _ffi.JR_F32_X8P, "x6h": _ffi.JR_F32_X6H}.get(conv_math, self.dt)
-        self.train_mode = train
+        # activation dtype: fp32, or bf16 (parameters, gradients, momentum,
+        # BN statistics and the head stay fp32 master copies either way)
+        self.act_dtype = torch.bfloat16 if self.dt == _ffi.JR_BF16 else torch.float32
+        self.esz = 2 if self.dt == _ffi.JR_BF16 else 4
+        self._vw = 16 // self.esz       # channels per 16-byte vector (one launch: <= 256 per row)
+        # the image buffer is kept one 16 B DMA piece wide per pixel (4 fp32 /
+        # 8 bf16 channels, zeros past c = 3): conv1's c_in = 3 runs on libjr's
+        # virtual channel padding
+        self.in_stride = (self.g.bufs[self.g.input_buf].c + self._vw - 1) // self._vw * self._vw
+        self.head_mode = _ffi.JR_HEAD_SIGMOID if head == "sigmoid" else _ffi.JR_HEAD_SOFTMAX
+        # lanes (jr.lanes): lane 0 is self.stream, where every step starts and
+        # ends; every lane has its OWN conv workspace (split-K slabs, stream-K
+        # partial slots, statistics partials), the resource ("ws", lane)
+        self.lanes = Lanes(self.lib, self.device, lanes, priorities)
+        self.lane_streams, self.nlanes, self.precise_waits = self.lanes.streams, self.lanes.n, self.lanes.precise_waits
+        self.stream, self._s = self.lanes.streams[0], self.lanes.handles[0]
+        self.plan = build_plan(self.g, fuse_siblings)
+        self.cunits, self.nparam = self.plan.units, self.plan.nparam
+        # conv2d_bn outputs read only by a max-pool (the stem's conv2d_3 and
+        # conv2d_5): BN + ReLU run inside the pool (jr_bn_relu_maxpool3x3s2_fwd)
+        # and the full-resolution activation is never written
+        if fuse_pool is None:           # (JR_FUSE_POOL=0: the separate apply + max-pool, for A/B runs)
+            fuse_pool = os.environ.get("JR_FUSE_POOL", "1") != "0"
+        self.pool_fused = fusable_pools(self.g, self.plan) if fuse_pool else {}
+        self.fused_bufs = set(self.pool_fused.values())
+        # resources (jr.lanes.schedule): the channel slices of every buffer
+        slices: Dict[int, set] = {self.g.input_buf: {0}}
+        for n in self.g.nodes:
+            slices.setdefault(n.y.buf, set()).add(n.y.c_off)
+        self.slices = {b: sorted(o) for b, o in slices.items()}
+
+    def _t(self, n: int, dtype=torch.float32) -> torch.Tensor:
+        return torch.zeros(int(n), dtype=dtype, device=self.device)
+
+    def _table(self, struct, rows) -> torch.Tensor:
+        """A device copy of a ctypes struct array."""
+        return torch.frombuffer(bytearray(bytes((struct * len(rows))(*rows))), dtype=torch.uint8).to(self.device)
+
+    def _a_all(self, b: int) -> list:
+        return [("a", b, o) for o in self.slices[b]]
+
+    def _p(self, name: str, m: int = 0) -> int:
+        return self.params.data_ptr() + 4 * (m * self.nparam + self.plan.poff[name])
+
+    def _beta(self, n, m: int = 0) -> int:
+        return self._p(f"batch_normalization_{n.idx + 1}/beta", m)
+
+    def _pool_producer(self, n: PoolNode):
+        """The conv2d_bn layer whose BN + ReLU a fused max-pool applies."""
+        return next(m for m in self.g.nodes if m.y.buf == n.x)
+
+    def _alloc_bf16_filters(self, planes: int = 1, hwio: bool = True) -> None:
+        """bf16 operand copies of every conv launch's kernel (block) of every
+        member, written from the fp32 master parameters by ONE
+        jr_conv_weights_bf16_multi launch: HWIO (bwd_data; hwio) and W^T
+        [co][kh][kw][c8] (fwd).  planes = 3 (JR_F32_X8P): each copy is the
+        three bf16 planes of the exact split, jr_conv_weights_x8p_multi."""
+        M = self.members
+        self.wplanes = planes
+        per, tiles, ho, to = [], 0, 0, 0
+        self.wb_hwio_off, self.wb_t_off = {}, {}
+        for u in self.cunits:
+            c8 = (u.cin + 7) // 8 * 8
+            per.append((u, ho if hwio else 0, to, tiles))
+            self.wb_hwio_off[u.first.idx], self.wb_t_off[u.first.idx] = ho, to
+            tiles += self.lib.jr_conv_weights_bf16_tiles(u.kh, u.kw, u.cin, u.cout)
+            # 16 B-aligned starts (8 bf16); x8p: three planes per layer, plane
+            # stride = the layer's element count (jr.h)
+            ho += (planes * u.kh * u.kw * u.cin * u.cout + 7) // 8 * 8
+            to += planes * u.cout * u.kh * u.kw * c8
+        self.wt_ms = (to + 7) // 8 * 8          # member stride of the W^T copies
+        layers = [_ffi.WPrep(m * self.nparam + u.koff, o_h, m * self.wt_ms + o_t, u.kh, u.kw, u.cin, u.cout,
+                             m * tiles + t0, 0) for m in range(M) for u, o_h, o_t, t0 in per]
+        self.wprep_table = self._table(_ffi.WPrep, layers)
+        self.wprep_layers, self.wprep_tiles = len(layers), M * tiles
+        self.w_hwio = self._t(ho, torch.bfloat16) if hwio else None
+        self.w_t = self._t(M * self.wt_ms, torch.bfloat16)
+
+    def _alloc_absmax(self, B: int, rows: int, beta_row: int) -> None:
+        """JR_F32_X6H magnitude words, 64 floats per row: one row per (conv
+        launch, member) for its filter block, the members of a launch
+        contiguous (the grouped conv's convention), then whatever rows the
+        caller keeps; and the jr_absmax_prep table (filters, then every BN
+        beta with the activation guard, their maxima landing in beta_row)."""
+        M = self.members
+        self.absmax = self._t(64 * rows)
+        self._arow = {u.first.idx: k for k, u in enumerate(self.cunits)}
+        nmax = max(B * u.ho * u.wo for u in self.cunits)
+        # activations are BN + ReLU outputs (or pools of them): |y| <= sqrt(N-1)
+        # + max |beta|; bound = a power of two >= sqrt(N_max) + 1024, beta
+        # guarded at that bound, so |y| <= 2 bound < the 4 bound the scale
+        # keeps representable
+        self.act_bound = float(2 ** int(np.ceil(np.log2(np.sqrt(nmax) + 1024))))
+        segs = [_ffi.AbsmaxSeg(m * self.nparam + u.koff, u.kh * u.kw * u.cin * u.cout, k * M + m, 0.0)
+                for k, u in enumerate(self.cunits) for m in range(M)]
+        segs += [_ffi.AbsmaxSeg(m * self.nparam + self.plan.poff[f"batch_normalization_{n.idx + 1}/beta"], n.cout,
+                                beta_row, self.act_bound) for m in range(M) for u in self.cunits for n in u.members]
+        self.absmax_table = self._table(_ffi.AbsmaxSeg, segs)
+        self.absmax_nseg = len(segs)
+
+    def _wmax(self, u: ConvUnit) -> int:
+        return self.absmax.data_ptr() + 4 * 64 * self._arow[u.first.idx] * self.members
+
+    def _conv_desc(self, u: ConvUnit, B: int) -> _ffi.ConvDesc:
+        if self.x8p:          # x describes the operand planes: channel radix padded to 8
+            xs = (u.cin + 7) // 8 * 8
+        else:
+            xs = self.in_stride if u.x == self.g.input_buf else u.cin
+        d = _ffi.ConvDesc(B, u.h, u.w, u.cin, u.cout, u.kh, u.kw, u.stride, u.stride,
+                          u.pad_h, u.pad_w, u.ho, u.wo, 0, xs, 0, u.cout)
+        if self.x6h:
+            d.x_bound = 1.0 if u.x == self.g.input_buf else self.act_bound    # images: f32(k) * f32(1/255) <= 1
+            d.w_absmax = self._wmax(u)
+        return d
+
+    def _upload(self, images, labels, B: int) -> None:
+        """A batch (NHWC float32, or uint8 to be scaled by 1/255) into the
+        first member's input buffer and the labels, on self.stream."""
+        ib = self.g.bufs[self.g.input_buf]
+        x, pixels, dst = torch.as_tensor(images), B * ib.h * ib.w, self.acts[self.g.input_buf]
+        if x.dtype == torch.uint8:
+            xd = x.to(self.device, non_blocking=True).reshape(-1)
+            _ffi.check("jr_image_u8_to_nhwc", self.lib.jr_image_u8_to_nhwc(
+                xd.data_ptr(), dst.data_ptr(), self.dt, pixels, ib.c, self.in_stride, self._s))
+            self._keep_u8 = xd
+        else:
+            v = dst[:pixels * self.in_stride].view(pixels, self.in_stride)
+            v[:, ib.c:].zero_()
+            v[:, :ib.c].copy_(x.to(torch.float32).reshape(pixels, ib.c).to(self.device, non_blocking=True))
+        self._set_labels(labels, B)
+
+    def _set_labels(self, labels, B: int) -> None:
+        if labels is not None:
+            y = torch.as_tensor(labels, dtype=torch.float32).reshape(-1)
+            if y.numel() != B * self.units:
+                raise ValueError("labels must have batch*units elements")
+            self.labels[:y.numel()].copy_(y, non_blocking=True)
+
+    def _check_images(self, images, B: int) -> None:
+        ib = self.g.bufs[self.g.input_buf]
+        if B > self.batch or B <= 0:
+            raise ValueError(f"batch {B} outside 1..{self.batch}")
+        if tuple(images.shape[1:]) != (ib.h, ib.w, ib.c):
+            raise ValueError(f"images must be [B,{ib.h},{ib.w},{ib.c}] NHWC, got {tuple(images.shape)}")
+
+
+class Engine(Replica):
+    """One model replica on one GPU (one process per GPU)."""
+
+    def __init__(self, batch: int, height: int = 299, width: int = 299, units: int = 1,
+                 device: int | torch.device = 0, dtype: str = "f32", train: bool = True,
+                 optimizer: str = "nesterov", lr: float = 3e-3, momentum: float = 0.9,
+                 head: str = "sigmoid", seed: int = 0, graph: Optional[Graph] = None,
+                 autotune: bool = False, tiles: str = "pinned", fuse_siblings: bool = True, lanes: int = 2,
+                 conv_math: Optional[str] = None, defer_wgrad: Optional[bool] = None, fuse_pool: Optional[bool] = None,
+                 fold_stats: Optional[bool] = None):
+        # JR_LANE_PRIORITY="p0,p1,...": HIP stream priority per lane (lower =
+        # higher priority). Default: lane 0 (the trunk) high for fp32 steps,
+        # measured 0.1 ms/step faster over 6 interleaved rounds on two boxes
+        # (profiles/r05_ab_prio_f32*.txt); all normal for bf16, where it
+        # measured neutral. Priority moves no result: scheduling only.
+        prio = os.environ.get("JR_LANE_PRIORITY", "-1,0" if dtype == "f32" else "")
+        super().__init__(graph or build_inception_v3(height, width, units), device, dtype, conv_math,
+                         ("x8", "x8p", "x6h", "f32"), head, fuse_siblings, fuse_pool, lanes,
+                         [int(v) for v in prio.split(",") if v.strip()])
+        self.batch, self.train_mode = batch, train
         if optimizer not in ("nesterov", "momentum", "sgd", "adam"):
             raise ValueError(f"unknown optimizer {optimizer}")
         self.optimizer = optimizer
-        self.lr = float(lr)
-        self.momentum = float(momentum)
+        self.lr, self.momentum = float(lr), float(momentum)
         # Adam (north-star extra; TF AdamOptimizer defaults): accum holds m;
         # beta1_power / beta2_power are fp32 variables initialised to beta1 /
         # beta2 and multiplied by them (fp32) after every step, as TF's
         # AdamOptimizer._finish does
         self.adam_b1, self.adam_b2, self.adam_eps, self.adam_t = 0.9, 0.999, 1e-8, 0
         self.adam_b1p, self.adam_b2p = np.float32(self.adam_b1), np.float32(self.adam_b2)
-        self.head_mode = _ffi.JR_HEAD_SIGMOID if head == "sigmoid" else _ffi.JR_HEAD_SOFTMAX
-        self.units = self.g.units
-        # JR_LANE_PRIORITY="p0,p1,...": HIP stream priority per lane (lower =
-        # higher priority). Default: lane 0 (the trunk) high for fp32 steps,
-        # measured 0.1 ms/step faster over 6 interleaved rounds on two boxes
-        # (profiles/r05_ab_prio_f32*.txt); all normal for bf16, where it
-        # measured neutral. Priority moves no result: scheduling only.
-        prio_def = "-1,0" if self.dt == _ffi.JR_F32 else ""
-        prio = [int(v) for v in os.environ.get("JR_LANE_PRIORITY", prio_def).split(",") if v.strip()]
-        prio += [0] * max(0, int(lanes) - len(prio))
-        self.stream = torch.cuda.Stream(device=self.device, priority=prio[0])
-        self._s = ctypes.c_void_p(self.stream.cuda_stream)
-        # lanes (jr.lanes): lane 0 is self.stream, where every step starts and ends
-        self.nlanes = max(1, int(lanes))
-        self.lane_streams = [self.stream] + [torch.cuda.Stream(device=self.device, priority=prio[i])
-                                             for i in range(1, self.nlanes)]
-        self._lane_s = [ctypes.c_void_p(st.cuda_stream) for st in self.lane_streams]
-        self._fork_ev = torch.cuda.Event()
-        self._join_ev = [torch.cuda.Event() for _ in range(self.nlanes - 1)]
-        self._tail_ev = [torch.cuda.Event() for _ in range(self.nlanes)]
-        # eager runs: a cross-lane consumer waits for its producing call (an
-        # event recorded right after it) instead of the other lane's tail
-        # (JR_PRECISE_WAITS=0: tail waits, as captured graphs always use)
-        self.precise_waits = os.environ.get("JR_PRECISE_WAITS", "1") != "0"
-        self._join_each = os.environ.get("JR_DP_JOIN_EACH", "0") == "1"
-        self._prod_ev: Dict[int, object] = {}
-        # producer events: libjr's (no timing, no system-scope fence: cheaper
-        # to record) or torch's (JR_LANE_EVENTS=torch, for A/B runs)
-        self._native_ev = os.environ.get("JR_LANE_EVENTS", "native") != "torch"
-        self._capturing = False
         # backward order per conv launch: the data gradient (the critical
         # path to the next layer's BN backward) before the filter gradient
         # (JR_DGRAD_FIRST=0: filter gradient first)
@@ -169,14 +298,6 @@ class Engine:
         # a fused sibling launch's members' BN + ReLU in one launch
         # (JR_APPLY_MULTI=0: one launch per member, for A/B runs)
         self.apply_multi = os.environ.get("JR_APPLY_MULTI", "1") != "0"
-        self._vw = 8 if dtype == "bf16" else 4          # channels per 16-byte vector (one launch: <= 256 per row)
-        self.plan = build_plan(self.g, fuse_siblings)
-        # conv2d_bn outputs read only by a max-pool (the stem's conv2d_3 and
-        # conv2d_5): BN + ReLU run inside the pool (jr_bn_relu_maxpool3x3s2_fwd)
-        # and the full-resolution activation is never written
-        if fuse_pool is None:           # (JR_FUSE_POOL=0: the separate apply + max-pool, for A/B runs)
-            fuse_pool = os.environ.get("JR_FUSE_POOL", "1") != "0"
-        self.pool_fused = fusable_pools(self.g, self.plan) if fuse_pool else {}
         # the BN-statistics finalize folded into the BN apply for launches whose
         # partials are single-stage and at most JR_FOLD_MAX_P per channel
         # (jr_conv2d_fwd_bn_partials + jr_bn_relu_apply_stats: a kernel
@@ -187,11 +308,29 @@ class Engine:
             fold_stats = os.environ.get("JR_FOLD_STATS", "0") == "1"
         self.fold_stats = bool(fold_stats)
         self.fold_max_p = int(os.environ.get("JR_FOLD_MAX_P", "512"))
-        self.cunits: List[ConvUnit] = self.plan.units
-        self.layout, self.nparam = self.plan.layout, self.plan.nparam
-        self._alloc()
-        self.load_params(init_params(self.g, seed))
-        self._calls: Dict[int, Tuple[list, list, list]] = {}
+        # fp32: the fused stem pools' backward carries the BN reduce (bf16
+        # keeps the separate kernels, whose batch-of-rows fp32 sums it would
+        # not reproduce bit for bit; JR_FUSE_POOL_BWD=0: separate for fp32 too)
+        self.pool_bwd = (self.pool_fused if self.dt == _ffi.JR_F32 and os.environ.get("JR_FUSE_POOL_BWD", "1") != "0"
+                         else {})
+        # the stem's filter gradients on lane 1 (JR_STEM_WGRAD_LANE=0: on lane 0 with the rest of the stem)
+        self.stem_wgrad_lane = os.environ.get("JR_STEM_WGRAD_LANE", "1") != "0"
+        # the block-output BN backwards batched per block (jr_bn_relu_bwd_batch,
+        # opt-in JR_BN_BATCH=1: bitwise the per-layer launch sets, measured
+        # neutral -- bf16 9.343 -> 9.359, f32 24.85 -> 24.90 ms, the per-layer
+        # sets already overlap on the two lanes)
+        self.bn_batch_on = not self.x8p and not self.x6h and os.environ.get("JR_BN_BATCH", "0") == "1"
+        # a captured graph's edges are the producer waits; JR_GRAPH_PRECISE=0:
+        # tail waits (bf16 replay 10.04 vs 9.28 ms per step, eager 9.31:
+        # profiles/r05_graph_probe.txt)
+        self.graph_precise = os.environ.get("JR_GRAPH_PRECISE", "1") != "0"
+        readers: Dict[int, int] = {}
+        for q in self.g.nodes:
+            readers[q.x] = readers.get(q.x, 0) + 1
+        # the stem: the layers before the first buffer with several readers
+        self._stem_end = next((j for j, q in enumerate(self.g.nodes) if readers[q.x] > 1), 0)
+        self.layout = self.plan.layout
+        self._calls: Dict[Tuple[int, int], tuple] = {}
         self._retired: list = []        # call sets a captured graph may still reference
         # filter gradients of split-K wgrad GEMMs: slabs kept per layer and
         # summed by ONE jr_wgrad_reduce launch per flush point (the end of the
@@ -208,17 +347,21 @@ class Engine:
         self._flush_points: List[int] = []
         self._graphs: Dict[int, int] = {}
         self.bucket_hooks: List[Tuple[int, Callable]] = []
-        # conv tiles: "pinned" = the committed MI355X table for this workload
-        # (jr/tiles_mi355x.json, tools/make_tile_tables.py) when there is one,
-        # else the planner heuristic -- both deterministic, so every run on
-        # every box sums in the same order; "autotune" (or autotune=True)
-        # times the candidates on this box (fastest, box-dependent order)
+        self._aug_ws = None
+        self._alloc()
+        self.load_params(init_params(self.g, seed))
+        self._choose_tiles("autotune" if autotune else tiles)
+
+    def _choose_tiles(self, tiles: str) -> None:
+        """Conv tiles: "pinned" = the committed MI355X table for this workload
+        (jr/tiles_mi355x.json, tools/make_tile_tables.py) when there is one,
+        else the planner heuristic -- both deterministic, so every run on
+        every box sums in the same order; "autotune" (or autotune=True)
+        times the candidates on this box (fastest, box-dependent order)."""
         if tiles not in ("pinned", "heuristic", "autotune"):
             raise ValueError("tiles: 'pinned', 'heuristic' or 'autotune'")
-        if autotune:
-            tiles = "autotune"
         self.tiles = "heuristic"
-        self.clear_tile_table()         # libjr's per-geometry overrides are process-wide
+        self._clear_configs()           # libjr's per-geometry overrides are process-wide
         if tiles == "autotune":
             self.autotune()
             self.tiles = "autotune"
@@ -230,22 +373,16 @@ class Engine:
         self._own_tiles()
 
     # ------------------------------------------------------------------ memory
-    def _t(self, n: int, dtype=torch.float32) -> torch.Tensor:
-        return torch.zeros(int(n), dtype=dtype, device=self.device)
-
     def _alloc(self) -> None:
-        g, B = self.g, self.batch
-        fl = torch.float32
-        # activation dtype: fp32, or bf16 (parameters, gradients, momentum,
-        # BN statistics and the head stay fp32 master copies either way)
-        at = torch.bfloat16 if self.dt == _ffi.JR_BF16 else fl
-        self.act_dtype = at
-        self.esz = 2 if self.dt == _ffi.JR_BF16 else 4
-        # the image buffer is kept one 16 B DMA piece wide per pixel (4 fp32 /
-        # 8 bf16 channels, zeros past c = 3): conv1's c_in = 3 runs on libjr's
-        # virtual channel padding
-        q = 8 if self.dt == _ffi.JR_BF16 else 4
-        self.in_stride = (g.bufs[g.input_buf].c + q - 1) // q * q
+        g, B, at = self.g, self.batch, self.act_dtype
+        if self.x6h:
+            # (first: every conv descriptor points into it) filter rows 0..U-1,
+            # raw-output gradient rows U..2U-1.  The betas' maxima land in the
+            # last gradient row, zeroed again by the same prep and raised by the
+            # first BN backward only after it: harmless, a larger bound; conv2d_1's
+            # data gradient is never used (jr.EnsembleEngine: a row of their own)
+            U = len(self.cunits)
+            self._alloc_absmax(B, 2 * U, 2 * U - 1)
         self.acts = [self._t(B * b.h * b.w * (self.in_stride if b.id == g.input_buf else b.c), at)
                      for b in g.bufs]
         # raw (pre-BN) output and BN statistics per conv launch; a fused
@@ -275,6 +412,7 @@ class Engine:
         self.labels = self._t(B * self.units)
         self.loss = self._t(4)
         self.params = self._t(self.nparam)
+        self.draw_stem2, self.bn_batch, self.drawb = None, [], []
         if self.train_mode:
             self.grads = self._t(self.nparam)
             self.accum = self._t(self.nparam)
@@ -292,13 +430,9 @@ class Engine:
                                if self.nlanes > 1 and not self.x8p else None)
             self.draw = self.draw_lane[0]
             self.dfeat = self._t(B * feat_c)
-            # the block-output BN backwards batched per block (jr_bn_relu_bwd_batch,
-            # opt-in JR_BN_BATCH=1: bitwise the per-layer launch sets, measured
-            # neutral -- bf16 9.343 -> 9.359, f32 24.85 -> 24.90 ms, the per-layer
-            # sets already overlap on the two lanes): their raw gradients live in
-            # two alternating sets of per-layer buffers
-            self.bn_batch = (self._bn_batch_groups(B)
-                             if not self.x8p and not self.x6h and os.environ.get("JR_BN_BATCH", "0") == "1" else [])
+            # the batched block-output BN backwards' raw gradients live in two
+            # alternating sets of per-layer buffers
+            self.bn_batch = self._bn_batch_groups(B) if self.bn_batch_on else []
             slots = max((len(grp) for grp in self.bn_batch), default=0)
             self.drawb = [[self._t(max(B * grp[k].ho * grp[k].wo * grp[k].cout
                                        for grp in self.bn_batch if k < len(grp)), at) for k in range(slots)]
@@ -314,7 +448,7 @@ class Engine:
             for op in (ops if self.train_mode else ops[:1]):
                 ws = max(ws, self.lib.jr_conv2d_workspace_size(ctypes.byref(d), op, self.cdt))
             ws = max(ws, self.lib.jr_bn_workspace_size(B * u.ho * u.wo, u.cout))   # one backward per launch (or less)
-        for grp in getattr(self, "bn_batch", []):        # one batched BN backward per block
+        for grp in self.bn_batch:                        # one batched BN backward per block
             ws = max(ws, sum((self.lib.jr_bn_workspace_size(B * u.ho * u.wo, u.cout) + 255) // 256 * 256
                              for u in grp))
         for i in self.pool_fused:                      # the fused max-pool + BN backward's partials
@@ -322,40 +456,10 @@ class Engine:
         self.ws_bytes = int(ws)
         self.ws_lane = [self._t((self.ws_bytes + 15) // 4 + 4) for _ in range(self.nlanes)]
         # the stem filter gradients' own workspace on lane 1
-        self.ws_stem = (self._t((self.ws_bytes + 15) // 4 + 4)
-                        if self.train_mode and getattr(self, "draw_stem2", None) is not None else None)
+        self.ws_stem = self._t((self.ws_bytes + 15) // 4 + 4) if self.draw_stem2 is not None else None
         self.ws = self.ws_lane[0]
-        if self.x6h:
-            self._alloc_absmax(B)
-
-    def _alloc_absmax(self, B: int) -> None:
-        """JR_F32_X6H magnitude words: 64 floats per conv launch for its
-        filter block (rows 0..U-1) and for its raw-output gradient (rows
-        U..2U-1), and the jr_absmax_prep table (filters, then every BN beta
-        with the activation guard)."""
-        U = len(self.cunits)
-        self.absmax = self._t(64 * 2 * U)
-        self._arow = {u.first.idx: k for k, u in enumerate(self.cunits)}
-        nmax = max(B * u.ho * u.wo for u in self.cunits)
-        # activations are BN + ReLU outputs (or pools of them): |y| <= sqrt(N-1)
-        # + max |beta|; bound = a power of two >= sqrt(N_max) + 1024, beta
-        # guarded at that bound, so |y| <= 2 bound < the 4 bound the scale
-        # keeps representable
-        self.act_bound = float(2 ** int(np.ceil(np.log2(np.sqrt(nmax) + 1024))))
-        segs = [_ffi.AbsmaxSeg(u.koff, u.kh * u.kw * u.cin * u.cout, k, 0.0) for k, u in enumerate(self.cunits)]
-        for u in self.cunits:
-            for m in u.members:
-                off = self.plan.poff[f"batch_normalization_{m.idx + 1}/beta"]
-                segs.append(_ffi.AbsmaxSeg(off, m.cout, 2 * U - 1, self.act_bound))
-        # (the betas' maxima land in the last gradient row, zeroed again by
-        # the same prep and raised by the first BN backward only after it:
-        # harmless, a larger bound; conv2d_1's data gradient is never used)
-        arr = (_ffi.AbsmaxSeg * len(segs))(*segs)
-        self.absmax_table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-        self.absmax_nseg = len(segs)
-
-    def _wmax(self, u: ConvUnit) -> int:
-        return self.absmax.data_ptr() + 4 * 64 * self._arow[u.first.idx]
+        # launch -> its group of batched BN backwards
+        self._in_batch = {u.first.idx: grp for grp in self.bn_batch for u in grp}
 
     def _dmax(self, u: ConvUnit) -> int:
         return self.absmax.data_ptr() + 4 * 64 * (len(self.cunits) + self._arow[u.first.idx])
@@ -366,7 +470,7 @@ class Engine:
         branch-final layers of an Inception block), one launch set per launch
         (c / vector width <= 256), at most 512 reduce chunks (jr_bn.hip
         chunk_geom), not the stem's pooled layers; blocks with two or more."""
-        g, vw = self.g, (8 if self.dt == _ffi.JR_BF16 else 4)
+        g, vw = self.g, self._vw
         producers: Dict[int, set] = {}
         for u in self.cunits:
             for m in u.members:
@@ -412,33 +516,6 @@ class Engine:
         if self.train_mode:
             n = max(B * u.ho * u.wo * u.cout for u in self.cunits)
             self.drawp_lane = [self._t(3 * n, bf) for _ in range(self.nlanes)]
-
-    def _alloc_bf16_filters(self, planes: int = 1) -> None:
-        """bf16 operand copies of every conv launch's kernel (block), refreshed
-        from the fp32 master parameters by ONE jr_conv_weights_bf16_multi
-        launch at the start of each forward: HWIO (bwd_data) and
-        W^T [co][kh][kw][c8] (fwd).  planes = 3 (JR_F32_X8P): each copy is
-        the three bf16 planes of the exact split, jr_conv_weights_x8p_multi."""
-        L = self.lib
-        self.wplanes = planes
-        layers, tiles = [], 0
-        self.wb_hwio_off, self.wb_t_off = {}, {}
-        ho = to = 0
-        for u in self.cunits:
-            c8 = (u.cin + 7) // 8 * 8
-            layers.append(_ffi.WPrep(u.koff, ho, to, u.kh, u.kw, u.cin, u.cout, tiles, 0))
-            self.wb_hwio_off[u.first.idx], self.wb_t_off[u.first.idx] = ho, to
-            tiles += L.jr_conv_weights_bf16_tiles(u.kh, u.kw, u.cin, u.cout)
-            # 16 B-aligned starts (8 bf16); x8p: three planes per layer, plane
-            # stride = the layer's element count (jr.h)
-            hw_n = u.kh * u.kw * u.cin * u.cout
-            ho += (planes * hw_n + 7) // 8 * 8
-            to += planes * u.cout * u.kh * u.kw * c8
-        arr = (_ffi.WPrep * len(layers))(*layers)
-        self.wprep_table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-        self.wprep_layers, self.wprep_tiles = len(layers), tiles
-        self.w_hwio = self._t(ho, torch.bfloat16)
-        self.w_t = self._t(to, torch.bfloat16)
 
     def _wprep_call(self, stream=None):
         fn = self.lib.jr_conv_weights_x8p_multi if self.wplanes == 3 else self.lib.jr_conv_weights_bf16_multi
@@ -541,8 +618,6 @@ class Engine:
         """Record the configs this engine's call lists are bound to (libjr's
         overrides are process-wide: another engine or caller of the same
         geometry may change them; _ensure_tiles puts these back)."""
-        if not hasattr(self, "tiles"):
-            return                  # still in __init__ (clear_tile_table before the table is chosen)
         self._tile_cfgs = self.tile_table()["configs"]
         self._tile_gen = self.lib.jr_conv2d_config_generation()
 
@@ -550,11 +625,9 @@ class Engine:
         """Re-apply this engine's configs if libjr's overrides changed since it
         applied them (the deferred filter-gradient segments bind
         the split count of the plan at call-list build time)."""
-        gen = self.lib.jr_conv2d_config_generation()
-        if getattr(self, "_tile_cfgs", None) is None or gen == self._tile_gen:
-            return
-        self._apply_configs(self._tile_cfgs)     # the same plans the call lists were built with
-        self._tile_gen = self.lib.jr_conv2d_config_generation()
+        if self.lib.jr_conv2d_config_generation() != self._tile_gen:
+            self._apply_configs(self._tile_cfgs)     # the same plans the call lists were built with
+            self._tile_gen = self.lib.jr_conv2d_config_generation()
 
     def _apply_configs(self, cfgs: dict) -> None:
         for u in self.cunits:
@@ -577,8 +650,7 @@ class Engine:
         self._own_tiles()
 
     def _clear_configs(self) -> None:
-        if hasattr(self, "_calls"):
-            self._drop_calls()
+        self._drop_calls()
         for u in self.cunits:
             d = self._conv_desc(u, self.batch)
             ops = [(_ffi.JR_CONV_FWD, 0)]
@@ -614,23 +686,13 @@ class Engine:
         torch.cuda.synchronize(self.device)
         return self.plan.to_keras(self.g, self.grads.cpu().numpy())
 
-    def _p(self, name: str) -> int:
-        return self.params.data_ptr() + 4 * self.plan.poff[name]
-
     def _gp(self, name: str) -> int:
         return self.grads.data_ptr() + 4 * self.plan.poff[name]
 
     # ------------------------------------------------------------ descriptors
     def _conv_desc(self, u: ConvUnit, B: int) -> _ffi.ConvDesc:
-        if self.x8p:          # x describes the operand planes: channel radix padded to 8
-            xs = (u.cin + 7) // 8 * 8
-        else:
-            xs = self.in_stride if u.x == self.g.input_buf else u.cin
-        d = _ffi.ConvDesc(B, u.h, u.w, u.cin, u.cout, u.kh, u.kw, u.stride, u.stride,
-                          u.pad_h, u.pad_w, u.ho, u.wo, 0, xs, 0, u.cout)
-        if self.x6h and hasattr(self, "absmax"):
-            d.x_bound = 1.0 if u.x == self.g.input_buf else self.act_bound    # images: f32(k) * f32(1/255) <= 1
-            d.w_absmax = self._wmax(u)
+        d = super()._conv_desc(u, B)
+        if self.x6h:
             d.dy_absmax = self._dmax(u)
         return d
 
@@ -644,466 +706,402 @@ class Engine:
         the launch's channels fit one 256-thread row (jr_bn: <= 256 vectors of
         4 fp32 / 8 bf16), else one set per member.  [(member, col_off), ...]"""
         groups = [list(zip(u.members, u.col_off))]
-        if u.cout // (8 if self.dt == _ffi.JR_BF16 else 4) > 256:
+        if u.cout // self._vw > 256:
             groups = [[mc] for mc in groups[0]]
         return groups
 
-    def _build_calls(self, B: int, nl: Optional[int] = None, one_stream: bool = False):
+    def _build_calls(self, B: int, nl: Optional[int] = None):
         """Pre-bound Calls (jr.lanes) for forward, backward, update on nl
         lanes (default self.nlanes), with their cross-lane waits:
-        (fwd, bwd, opt, keep, None).  one_stream: every call is bound to
-        lane 0's stream (per-lane scratch kept) for the explicit-DAG graph
-        capture, where the lanes become graph branches (capture())."""
+        (fwd, bwd, opt, keep, None)."""
         self._ensure_tiles()
         nl = self.nlanes if nl is None else max(1, min(int(nl), self.nlanes))
-        key = (B, nl, one_stream)
+        key = (B, nl)
         if key in self._calls:
             return self._calls[key]
         if B > self.batch or B <= 0:
             raise ValueError(f"batch {B} outside 1..{self.batch}")
-        L, g, dt, cdt = self.lib, self.g, self.dt, self.cdt
-        S = [ctypes.c_void_p(st.cuda_stream) for st in self.lane_streams[:nl]]
-        if one_stream:
-            S = [S[0]] * nl
-        WS = [ctypes.c_void_p(w.data_ptr()) for w in self.ws_lane[:nl]]
-        wsb = ctypes.c_size_t(self.ws_bytes)
-        lane_of = node_lanes(g, self.plan, nl)
-        keep = []  # keep ctypes structs alive
-        fwd, bwd, opt, seq = [], [], [], []
+        g, unit_of = self.g, self.plan.unit_of
+        b = Build(B, self.lanes, nl, self.ws_lane, self.ws_bytes, node_lanes(g, self.plan, nl), self._flush_points)
+        self._fwd_prep(b)
+        for i, n in enumerate(g.nodes):
+            if n.kind != "conv":
+                self._fwd_pool(b, i, n)
+            elif unit_of[n.idx].first is n:     # a group is emitted with its first member
+                self._fwd_conv(b, b.lane_of[i], unit_of[n.idx])
+        self._fwd_head(b)
+        if self.train_mode:
+            if self.defer_wgrad:
+                self._bwd_slab_arena(b)
+            self._bwd_head(b)
+            for i in range(len(g.nodes) - 1, -1, -1):
+                n = g.nodes[i]
+                if n.kind != "conv":
+                    self._bwd_pool(b, i, n)
+                elif unit_of[n.idx].first is n:     # a group runs at its first member: every member's dy is final then
+                    self._bwd_conv(b, i, unit_of[n.idx])
+            self._bwd_flush(b)
+            self._opt_update(b)
+        schedule(b.seq)
+        self._calls[key] = (b.fwd, b.bwd, b.opt, b.keep, None)
+        return self._calls[key]
 
-        def add(lst, fn, args, name, lane, reads=(), writes=(), nbytes=0):
-            c = Call(fn, args, name, lane, tuple(reads), tuple(writes), nbytes=int(nbytes))
-            lst.append(c)
-            seq.append(c)
+    # resources and operands of the calls: activations, their gradients, and
+    # what a conv reads -- x8p: the split planes of its input buffer, written
+    # once (by the lane of its first consumer) when the buffer is complete;
+    # its filters (w16: their bf16 copies); x6h: their magnitude words too
+    def _A(self, bid: int) -> int:
+        return self.acts[bid].data_ptr()
 
-        # resources (jr.lanes.schedule): activation / gradient channel slices
-        slices: Dict[int, set] = {g.input_buf: {0}}
-        for n in g.nodes:
-            slices.setdefault(n.y.buf, set()).add(n.y.c_off)
-        a_all = lambda b: [("a", b, o) for o in sorted(slices[b])]  # noqa: E731
-        d_all = lambda b: [("d", b, o) for o in sorted(slices[b])]  # noqa: E731
-        A = lambda bid: self.acts[bid].data_ptr()  # noqa: E731
-        unit_of = self.plan.unit_of
-        x8p = self.x8p
-        wkey = ("w16",) if (dt == _ffi.JR_BF16 or x8p) else ("p",)
-        if dt == _ffi.JR_BF16 or x8p:
-            add(fwd, *self._wprep_call(S[0]), 0, [("p",)], [("w16",)])
-        # x6h: the convs read their filters' magnitude words besides the filters
-        xw = [("wmax",)] if self.x6h else []
+    def _D(self, bid: int) -> int:
+        return self.dacts[bid].data_ptr()
+
+    def _d_all(self, bid: int) -> list:
+        return [("d", bid, o) for o in self.slices[bid]]
+
+    def _AX(self, bid: int) -> int:
+        return (self.aplanes[bid] if self.x8p else self.acts[bid]).data_ptr()
+
+    def _ax_reads(self, bid: int) -> list:
+        return [("ap", bid)] if self.x8p else self._a_all(bid)
+
+    def _w_reads(self) -> list:
+        return [("w16",) if (self.dt == _ffi.JR_BF16 or self.x8p) else ("p",)] + ([("wmax",)] if self.x6h else [])
+
+    def _dbeta(self, m) -> int:
+        return self._gp(f"batch_normalization_{m.idx + 1}/beta")
+
+    def _bn_segs(self, members) -> list:
+        """Per member: its upstream gradient slice, beta and dbeta."""
+        return [_ffi.BnSeg(self._D(m.y.buf), m.y.c_off, self.g.bufs[m.y.buf].c, m.cout, self._beta(m), self._dbeta(m))
+                for m in members]
+
+    # ---- forward
+    def _fwd_prep(self, b: Build) -> None:
+        if self.dt == _ffi.JR_BF16 or self.x8p:
+            b.add(b.fwd, *self._wprep_call(b.S[0]), 0, [("p",)], [("w16",)])
         if self.x6h:
             # the filters' magnitudes (and the beta guard), and every
             # gradient row zeroed, before the first conv of the step
-            add(fwd, L.jr_absmax_prep, (self.params.data_ptr(), self.absmax_table.data_ptr(), self.absmax_nseg,
-                                        self.absmax.data_ptr(), self.absmax.numel(), S[0]), "absmax_prep", 0,
-                [("p",)], [("wmax",)] + [("dmax", u.first.idx) for u in self.cunits], nbytes=4 * self.nparam)
-        # x8p: conv operands are the split planes of the input buffer, written
-        # once (by the lane of its first consumer) when the buffer is complete
-        AX = (lambda bid: self.aplanes[bid].data_ptr()) if x8p else A  # noqa: E731
-        ax_reads = (lambda bid: [("ap", bid)]) if x8p else a_all  # noqa: E731
-        split_done = set()
-        fused_bufs = set(self.pool_fused.values())
-        for i, n in enumerate(g.nodes):
-            ln = lane_of[i]
-            s, ws = S[ln], WS[ln]
-            if n.kind == "conv":
-                u = unit_of[n.idx]
-                if u.first is not n:
-                    continue            # emitted with the group's first member
-                d = self._conv_desc(u, B)
-                keep.append(d)
-                M = B * u.ho * u.wo
-                uid = u.first.idx
-                raw = self.raw_unit[uid].data_ptr()
-                if x8p and u.x not in split_done:
-                    split_done.add(u.x)
-                    b = g.bufs[u.x]
-                    cp = self.plane_c[u.x]
-                    rows = B * b.h * b.w
-                    src_stride = self.in_stride if u.x == g.input_buf else b.c
-                    add(fwd, L.jr_split_x8p, (A(u.x), rows, b.c, 0, src_stride, AX(u.x), cp, 0, cp,
-                                              self.batch * b.h * b.w * cp, s),
-                        "split_x8p", ln, a_all(u.x), [("ap", u.x)], nbytes=rows * (4 * b.c + 6 * cp))
+            b.add(b.fwd, self.lib.jr_absmax_prep,
+                  (self.params.data_ptr(), self.absmax_table.data_ptr(), self.absmax_nseg, self.absmax.data_ptr(),
+                   self.absmax.numel(), b.S[0]), "absmax_prep", 0,
+                  [("p",)], [("wmax",)] + [("dmax", u.first.idx) for u in self.cunits], nbytes=4 * self.nparam)
+
+    def _fwd_conv(self, b: Build, ln: int, u: ConvUnit) -> None:
+        """A conv launch with the BN batch statistics of its raw output, and
+        its members' BN + ReLU."""
+        L, g, dt, B, s, ws = self.lib, self.g, self.dt, b.B, b.S[ln], b.WS[ln]
+        d = self._conv_desc(u, B)
+        b.keep.append(d)
+        M, uid = B * u.ho * u.wo, u.first.idx
+        raw, mean, invstd = (t[uid].data_ptr() for t in (self.raw_unit, self.mean_unit, self.invstd_unit))
+        if self.x8p and u.x not in b.split_done:
+            b.split_done.add(u.x)
+            xb, cp = g.bufs[u.x], self.plane_c[u.x]
+            rows = B * xb.h * xb.w
+            b.add(b.fwd, L.jr_split_x8p, (self._A(u.x), rows, xb.c, 0, self.in_stride if u.x == g.input_buf else xb.c,
+                                          self._AX(u.x), cp, 0, cp, self.batch * xb.h * xb.w * cp, s),
+                  "split_x8p", ln, self._a_all(u.x), [("ap", u.x)], nbytes=rows * (4 * xb.c + 6 * cp))
+        reads = self._ax_reads(u.x) + self._w_reads()
+        unfused = not any(m.y.buf in self.fused_bufs for m in u.members)
+        lay = None
+        if self.fold_stats and unfused:
+            lay = _ffi.BnPartials()
+            _ffi.check("jr_conv2d_bn_partials_layout",
+                       L.jr_conv2d_bn_partials_layout(ctypes.byref(d), self.cdt, ctypes.byref(lay)))
+            if not lay.single_stage or lay.P > self.fold_max_p:
                 lay = None
-                if self.fold_stats and not any(m.y.buf in fused_bufs for m in u.members):
-                    lay = _ffi.BnPartials()
-                    _ffi.check("jr_conv2d_bn_partials_layout",
-                               L.jr_conv2d_bn_partials_layout(ctypes.byref(d), cdt, ctypes.byref(lay)))
-                    if not lay.single_stage or lay.P > self.fold_max_p:
-                        lay = None
-                if lay is not None:
-                    # conv + the statistics partials; each member's BN apply
-                    # combines its channels' partials (and stores mean / invstd)
-                    add(fwd, L.jr_conv2d_fwd_bn_partials, (ctypes.byref(d), cdt, AX(u.x), self._wf(u), raw, ws, wsb,
-                                                           s),
-                        "conv_fwd", ln, ax_reads(u.x) + [wkey] + xw, [("r", uid), ("ws", ln)])
-                    part = ws.value + lay.ws_offset
-                    for m, co in zip(u.members, u.col_off):
-                        yb = g.bufs[m.y.buf]
-                        add(fwd, L.jr_bn_relu_apply_stats,
-                            (dt, raw, co, u.cout, M, m.cout, part, lay.P, lay.R, u.cout, co, BN_EPS,
-                             self.mean[m.idx].data_ptr(), self.invstd[m.idx].data_ptr(),
-                             self._p(f"batch_normalization_{m.idx + 1}/beta"), A(m.y.buf), m.y.c_off, yb.c, s),
-                            "bn_relu", ln, [("r", uid), ("ws", ln), ("p",)], [("a", m.y.buf, m.y.c_off), ("r", uid)],
-                            nbytes=2 * M * m.cout * self.esz)
-                    continue
-                # conv + the BN batch statistics of its raw output, fused
-                add(fwd, L.jr_conv2d_fwd_bn_stats, (ctypes.byref(d), cdt, AX(u.x), self._wf(u), raw, BN_EPS,
-                                                    self.mean_unit[uid].data_ptr(),
-                                                    self.invstd_unit[uid].data_ptr(), ws, wsb, s),
-                    "conv_fwd", ln, ax_reads(u.x) + [wkey] + xw, [("r", uid), ("ws", ln)])
-                if (self.apply_multi and len(u.members) > 1 and u.cout // self._vw <= 256
-                        and not any(m.y.buf in fused_bufs for m in u.members)):
-                    # every member's BN + ReLU in one launch (jr_bn_relu_apply_multi)
-                    segs = (_ffi.BnApplySeg * len(u.members))(*[
-                        _ffi.BnApplySeg(A(m.y.buf), m.y.c_off, g.bufs[m.y.buf].c, m.cout,
-                                        self._p(f"batch_normalization_{m.idx + 1}/beta")) for m in u.members])
-                    keep.append(segs)
-                    add(fwd, L.jr_bn_relu_apply_multi, (dt, len(u.members), ctypes.byref(segs), raw, 0, u.cout, M,
-                                                        u.cout, self.mean_unit[uid].data_ptr(),
-                                                        self.invstd_unit[uid].data_ptr(), s),
-                        "bn_relu", ln, [("r", uid), ("p",)], [("a", m.y.buf, m.y.c_off) for m in u.members],
-                        nbytes=2 * M * u.cout * self.esz)
-                    continue
-                for m, co in zip(u.members, u.col_off):
-                    if m.y.buf in fused_bufs:
-                        continue        # applied inside its max-pool
-                    yb = g.bufs[m.y.buf]
-                    add(fwd, L.jr_bn_relu_apply, (dt, raw, co, u.cout, M, m.cout, self.mean[m.idx].data_ptr(),
-                                                  self.invstd[m.idx].data_ptr(),
-                                                  self._p(f"batch_normalization_{m.idx + 1}/beta"),
-                                                  A(m.y.buf), m.y.c_off, yb.c, s),
-                        "bn_relu", ln, [("r", uid), ("p",)], [("a", m.y.buf, m.y.c_off)],
-                        nbytes=2 * M * m.cout * self.esz)
-            elif n.kind == "maxpool" and i in self.pool_fused:
-                d = self._pool_desc(n, B)
-                pn = next(m for m in g.nodes if m.y.buf == n.x)          # the conv2d_bn layer it applies
-                d.x_c_off, d.x_c_stride = 0, pn.cout                       # its raw output
-                keep.append(d)
-                puid = unit_of[pn.idx].first.idx
-                add(fwd, L.jr_bn_relu_maxpool3x3s2_fwd, (ctypes.byref(d), dt, self.raw_unit[puid].data_ptr(),
-                                                         self.mean[pn.idx].data_ptr(), self.invstd[pn.idx].data_ptr(),
-                                                         self._p(f"batch_normalization_{pn.idx + 1}/beta"),
-                                                         A(n.y.buf), self.argmax[i].data_ptr(), s),
-                    "bn_relu_maxpool_fwd", ln, [("r", puid), ("p",)], [("a", n.y.buf, n.y.c_off), ("am", i)],
-                    nbytes=B * n.c * (n.h * n.w * self.esz + n.ho * n.wo * (self.esz + 1)))
-            elif n.kind == "maxpool":
-                d = self._pool_desc(n, B)
-                keep.append(d)
-                add(fwd, L.jr_maxpool3x3s2_fwd, (ctypes.byref(d), dt, A(n.x), A(n.y.buf), self.argmax[i].data_ptr(), s),
-                    "maxpool_fwd", ln, a_all(n.x), [("a", n.y.buf, n.y.c_off), ("am", i)],
-                    nbytes=B * n.c * (n.h * n.w * self.esz + n.ho * n.wo * (self.esz + 1)))
-            else:
-                d = self._pool_desc(n, B)
-                keep.append(d)
-                add(fwd, L.jr_avgpool3x3s1_fwd, (ctypes.byref(d), dt, A(n.x), A(n.y.buf), s),
-                    "avgpool_fwd", ln, a_all(n.x), [("a", n.y.buf, n.y.c_off)],
-                    nbytes=B * n.c * (n.h * n.w + n.ho * n.wo) * self.esz)
+        if lay is not None:
+            # conv + the statistics partials; each member's BN apply
+            # combines its channels' partials (and stores mean / invstd)
+            b.add(b.fwd, L.jr_conv2d_fwd_bn_partials,
+                  (ctypes.byref(d), self.cdt, self._AX(u.x), self._wf(u), raw, ws, b.wsb, s),
+                  "conv_fwd", ln, reads, [("r", uid), ("ws", ln)])
+            part = ws.value + lay.ws_offset
+            for m, co in zip(u.members, u.col_off):
+                b.add(b.fwd, L.jr_bn_relu_apply_stats,
+                      (dt, raw, co, u.cout, M, m.cout, part, lay.P, lay.R, u.cout, co, BN_EPS,
+                       self.mean[m.idx].data_ptr(), self.invstd[m.idx].data_ptr(), self._beta(m), self._A(m.y.buf),
+                       m.y.c_off, g.bufs[m.y.buf].c, s),
+                      "bn_relu", ln, [("r", uid), ("ws", ln), ("p",)], [("a", m.y.buf, m.y.c_off), ("r", uid)],
+                      nbytes=2 * M * m.cout * self.esz)
+            return
+        b.add(b.fwd, L.jr_conv2d_fwd_bn_stats,
+              (ctypes.byref(d), self.cdt, self._AX(u.x), self._wf(u), raw, BN_EPS, mean, invstd, ws, b.wsb, s),
+              "conv_fwd", ln, reads, [("r", uid), ("ws", ln)])
+        if self.apply_multi and len(u.members) > 1 and u.cout // self._vw <= 256 and unfused:
+            # every member's BN + ReLU in one launch (jr_bn_relu_apply_multi)
+            segs = (_ffi.BnApplySeg * len(u.members))(*[
+                _ffi.BnApplySeg(self._A(m.y.buf), m.y.c_off, g.bufs[m.y.buf].c, m.cout, self._beta(m))
+                for m in u.members])
+            b.keep.append(segs)
+            b.add(b.fwd, L.jr_bn_relu_apply_multi,
+                  (dt, len(u.members), ctypes.byref(segs), raw, 0, u.cout, M, u.cout, mean, invstd, s),
+                  "bn_relu", ln, [("r", uid), ("p",)], [("a", m.y.buf, m.y.c_off) for m in u.members],
+                  nbytes=2 * M * u.cout * self.esz)
+            return
+        for m, co in zip(u.members, u.col_off):
+            if m.y.buf in self.fused_bufs:
+                continue        # applied inside its max-pool
+            b.add(b.fwd, L.jr_bn_relu_apply,
+                  (dt, raw, co, u.cout, M, m.cout, self.mean[m.idx].data_ptr(), self.invstd[m.idx].data_ptr(),
+                   self._beta(m), self._A(m.y.buf), m.y.c_off, g.bufs[m.y.buf].c, s),
+                  "bn_relu", ln, [("r", uid), ("p",)], [("a", m.y.buf, m.y.c_off)], nbytes=2 * M * m.cout * self.esz)
+
+    def _fwd_pool(self, b: Build, i: int, n: PoolNode) -> None:
+        L, dt, B, ln = self.lib, self.dt, b.B, b.lane_of[i]
+        s, d = b.S[ln], self._pool_desc(n, B)
+        b.keep.append(d)
+        out = [("a", n.y.buf, n.y.c_off)]
+        if i in self.pool_fused:
+            pn = self._pool_producer(n)
+            d.x_c_off, d.x_c_stride = 0, pn.cout                       # its raw output
+            puid = self.plan.unit_of[pn.idx].first.idx
+            b.add(b.fwd, L.jr_bn_relu_maxpool3x3s2_fwd,
+                  (ctypes.byref(d), dt, self.raw_unit[puid].data_ptr(), self.mean[pn.idx].data_ptr(),
+                   self.invstd[pn.idx].data_ptr(), self._beta(pn), self._A(n.y.buf), self.argmax[i].data_ptr(), s),
+                  "bn_relu_maxpool_fwd", ln, [("r", puid), ("p",)], out + [("am", i)],
+                  nbytes=B * n.c * (n.h * n.w * self.esz + n.ho * n.wo * (self.esz + 1)))
+        elif n.kind == "maxpool":
+            b.add(b.fwd, L.jr_maxpool3x3s2_fwd,
+                  (ctypes.byref(d), dt, self._A(n.x), self._A(n.y.buf), self.argmax[i].data_ptr(), s),
+                  "maxpool_fwd", ln, self._a_all(n.x), out + [("am", i)],
+                  nbytes=B * n.c * (n.h * n.w * self.esz + n.ho * n.wo * (self.esz + 1)))
+        else:
+            b.add(b.fwd, L.jr_avgpool3x3s1_fwd, (ctypes.byref(d), dt, self._A(n.x), self._A(n.y.buf), s),
+                  "avgpool_fwd", ln, self._a_all(n.x), out, nbytes=B * n.c * (n.h * n.w + n.ho * n.wo) * self.esz)
+
+    def _fwd_head(self, b: Build) -> None:
+        g, s0 = self.g, b.S[0]
         ob = g.bufs[g.output_buf]
-        s0 = S[0]
-        add(fwd, L.jr_gap_fwd, (dt, A(g.output_buf), B, ob.h * ob.w, ob.c, self.feat.data_ptr(), s0),
-            "gap_fwd", 0, a_all(g.output_buf), [("feat",)])
-        add(fwd, L.jr_head_fwd, (self.head_mode, self.feat.data_ptr(), self._p("dense/kernel"),
-                                 self._p("dense/bias"), self.labels.data_ptr(), B, ob.c, self.units,
-                                 self.logits.data_ptr(), self.probs.data_ptr(), self.loss.data_ptr(), s0),
-            "head_fwd", 0, [("feat",), ("p",), ("lab",)], [("head",)])
-        if self.train_mode:
-            D = lambda bid: self.dacts[bid].data_ptr()  # noqa: E731
-            # deferred filter gradients: per-layer slab regions of one arena
-            defer: Dict[int, Tuple[_ffi.WgradSeg, int, int]] = {}
-            if self.defer_wgrad:
-                off = 0
-                for u in self.cunits:
-                    d = self._conv_desc(u, B)
-                    keep.append(d)
-                    sg = _ffi.WgradSeg()
-                    _ffi.check("jr_conv2d_wgrad_seg", L.jr_conv2d_wgrad_seg(ctypes.byref(d), cdt, ctypes.byref(sg)))
-                    if sg.splits > 1:
-                        nb = 4 * sg.splits * sg.m * sg.n
-                        sg.dw = self.grads.data_ptr() + 4 * u.koff
-                        defer[u.first.idx] = (sg, off, nb)
-                        off += (nb + 255) // 256 * 256
-                arena = self._t(off // 4 + 64)
-                keep.append(arena)
-                for sg, o, _ in defer.values():
-                    sg.slabs = arena.data_ptr() + o
-                self.slab_bytes = off
-            pending: List[Tuple[_ffi.WgradSeg, int]] = []
-            flush_at = list(self._flush_points)
+        b.add(b.fwd, self.lib.jr_gap_fwd,
+              (self.dt, self._A(g.output_buf), b.B, ob.h * ob.w, ob.c, self.feat.data_ptr(), s0),
+              "gap_fwd", 0, self._a_all(g.output_buf), [("feat",)])
+        b.add(b.fwd, self.lib.jr_head_fwd,
+              (self.head_mode, self.feat.data_ptr(), self._p("dense/kernel"), self._p("dense/bias"),
+               self.labels.data_ptr(), b.B, ob.c, self.units, self.logits.data_ptr(), self.probs.data_ptr(),
+               self.loss.data_ptr(), s0),
+              "head_fwd", 0, [("feat",), ("p",), ("lab",)], [("head",)])
 
-            def flush():
-                """One jr_wgrad_reduce over every pending layer (lane 0)."""
-                if not pending:
-                    return
-                arr = (_ffi.WgradSeg * len(pending))()
-                blocks = 0
-                for k, (sg, _) in enumerate(pending):
-                    arr[k] = sg
-                    arr[k].block0 = blocks
-                    blocks += sg.blocks
-                table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-                keep.append(table)
-                nbytes = sum(4 * sg.m * sg.n * (sg.splits + 1) for sg, _ in pending)
-                add(bwd, L.jr_wgrad_reduce, (table.data_ptr(), len(pending), blocks, S[0]), "wgrad_reduce", 0,
-                    [("slab", uid) for _, uid in pending], [("g", uid) for _, uid in pending], nbytes=nbytes)
-                pending.clear()
-            add(bwd, L.jr_head_bwd, (self.head_mode, self.feat.data_ptr(), self._p("dense/kernel"),
-                                     self.probs.data_ptr(), self.labels.data_ptr(), B, ob.c, self.units,
-                                     self.dfeat.data_ptr(), self._gp("dense/kernel"), self._gp("dense/bias"), s0),
-                "head_bwd", 0, [("feat",), ("p",), ("head",), ("lab",)], [("dfeat",), ("g", "dense")])
-            add(bwd, L.jr_gap_bwd, (dt, self.dfeat.data_ptr(), B, ob.h * ob.w, ob.c, D(g.output_buf), s0),
-                "gap_bwd", 0, [("dfeat",)], d_all(g.output_buf))
-            written = set()
-            # fp32: the fused stem pools' backward carries the BN reduce
-            # (bf16 keeps the separate kernels, whose batch-of-rows fp32 sums
-            # it would not reproduce bit for bit)
-            pool_bwd = (self.pool_fused if dt == _ffi.JR_F32 and os.environ.get("JR_FUSE_POOL_BWD", "1") != "0"
-                        else {})
-            readers: Dict[int, int] = {}
-            for q in g.nodes:
-                readers[q.x] = readers.get(q.x, 0) + 1
-            # the stem: the layers before the first buffer with several readers
-            stem_end = next((j for j, q in enumerate(g.nodes) if readers[q.x] > 1), 0)
-            stem_split = (nl > 1 and self.draw_stem2 is not None
-                          and os.environ.get("JR_STEM_WGRAD_LANE", "1") != "0")
-            sbuf = 0
-            # batched block-output BN backwards: unit -> (group, slot); a group
-            # is issued where its first unit comes up (its upstream gradients
-            # are final there), on that unit's lane, into set `bset`
-            in_batch = {u.first.idx: (gi, k) for gi, grp in enumerate(self.bn_batch) for k, u in enumerate(grp)}
-            batch_draw: Dict[int, Tuple[int, Tuple]] = {}   # uid -> (raw-gradient pointer, resource)
-            bset = 0
-            for i in range(len(g.nodes) - 1, -1, -1):
-                n = g.nodes[i]
-                ln = lane_of[i]
-                s, ws = S[ln], WS[ln]
-                acc = 1 if n.x in written else 0
-                if n.kind == "conv":
-                    u = unit_of[n.idx]
-                    if u.first is not n:
-                        continue        # a group runs at its first member: every member's dy is final then
-                    d = self._conv_desc(u, B)
-                    keep.append(d)
-                    M = B * u.ho * u.wo
-                    uid = u.first.idx
-                    raw = self.raw_unit[uid].data_ptr()
-                    draw = self.draw_lane[ln].data_ptr()
-                    dkey = ("draw", ln)
-                    wl = ln
-                    if stem_split and i < stem_end and ln == 0:   # filter gradient on lane 1
-                        if sbuf:
-                            draw, dkey = self.draw_stem2.data_ptr(), ("draw2", 0)
-                        sbuf ^= 1
-                        wl = 1
-                    if uid in in_batch and uid not in batch_draw:   # the block's batched BN backward
-                        grp = self.bn_batch[in_batch[uid][0]]
-                        layers = (_ffi.BnBwdLayer * len(grp))()
-                        reads, writes = [("r", v.first.idx) for v in grp] + [("p",)], [("ws", ln)]
-                        for k, v in enumerate(grp):
-                            vid = v.first.idx
-                            ptr = self.drawb[bset][k].data_ptr()
-                            batch_draw[vid] = (ptr, ("drawb", bset, k))
-                            segs = [_ffi.BnSeg(D(m.y.buf), m.y.c_off, g.bufs[m.y.buf].c, m.cout,
-                                               self._p(f"batch_normalization_{m.idx + 1}/beta"),
-                                               self._gp(f"batch_normalization_{m.idx + 1}/beta")) for m in v.members]
-                            layers[k].nseg = len(segs)
-                            for j, sgm in enumerate(segs):
-                                layers[k].segs[j] = sgm
-                            layers[k].x = self.raw_unit[vid].data_ptr()
-                            layers[k].x_c_off, layers[k].x_c_stride = 0, v.cout
-                            layers[k].m, layers[k].c = B * v.ho * v.wo, v.cout
-                            layers[k].mean = self.mean_unit[vid].data_ptr()
-                            layers[k].invstd = self.invstd_unit[vid].data_ptr()
-                            layers[k].dx = ptr
-                            reads += [("d", m.y.buf, m.y.c_off) for m in v.members]
-                            writes += [("drawb", bset, k), ("g", vid)]
-                        keep.append(layers)
-                        add(bwd, L.jr_bn_relu_bwd_batch, (dt, len(grp), ctypes.byref(layers), ws, wsb, s),
-                            "bn_relu_bwd", ln, reads, writes,
-                            nbytes=sum(3 * B * v.ho * v.wo * v.cout * self.esz for v in grp))
-                        bset ^= 1
-                    if uid in batch_draw:
-                        draw, dkey = batch_draw[uid]
-                    # one backward launch set for all members of the launch (segments:
-                    # each member's upstream gradient slice, beta and dbeta)
-                    pool_i = next((j for j, b in pool_bwd.items() if b == u.first.y.buf), None)
-                    if pool_i is not None:    # the max-pool backward adds the BN reduce's sums
-                        pn, m0 = g.nodes[pool_i], u.first
-                        pd = self._pool_desc(pn, B)
-                        keep.append(pd)
-                        pargs = (dt, ctypes.byref(pd), self.argmax[pool_i].data_ptr(), D(pn.y.buf), D(pn.x), raw,
-                                 u.cout, self.mean_unit[uid].data_ptr(), self.invstd_unit[uid].data_ptr(),
-                                 self._p(f"batch_normalization_{m0.idx + 1}/beta"), draw,
-                                 self._gp(f"batch_normalization_{m0.idx + 1}/beta"), ws, wsb)
-                        pfn = L.jr_bn_relu_bwd_maxpool
-                        if self.x6h:    # also the raw-output gradient's magnitude (dy_absmax of its GEMMs)
-                            pfn, pargs = L.jr_bn_relu_bwd_maxpool_absmax, pargs + (self._dmax(u),)
-                        add(bwd, pfn, pargs + (s,),
-                            "bn_relu_bwd", ln, [("d", pn.y.buf, pn.y.c_off), ("am", pool_i), ("r", uid), ("p",)],
-                            d_all(pn.x) + [dkey, ("g", uid), ("ws", ln)] + ([("dmax", uid)] if self.x6h else []),
-                            nbytes=4 * M * u.cout * self.esz)
-                    for grp in ([] if pool_i is not None or uid in batch_draw else self._bn_groups(u)):
-                        co0 = grp[0][1]
-                        cg = sum(m.cout for m, _ in grp)
-                        segs = (_ffi.BnSeg * len(grp))(*[
-                            _ffi.BnSeg(D(m.y.buf), m.y.c_off, g.bufs[m.y.buf].c, m.cout,
-                                       self._p(f"batch_normalization_{m.idx + 1}/beta"),
-                                       self._gp(f"batch_normalization_{m.idx + 1}/beta")) for m, _ in grp])
-                        keep.append(segs)
-                        bargs = (dt, len(grp), ctypes.byref(segs), raw, co0, u.cout, M, cg,
-                                 self.mean_unit[uid].data_ptr() + 4 * co0, self.invstd_unit[uid].data_ptr() + 4 * co0,
-                                 draw, ws, wsb)
-                        bfn = L.jr_bn_relu_bwd_multi
-                        if self.x6h:
-                            bfn, bargs = L.jr_bn_relu_bwd_multi_absmax, bargs + (self._dmax(u),)
-                        add(bwd, bfn, bargs + (s,),
-                            "bn_relu_bwd", ln, [("d", m.y.buf, m.y.c_off) for m, _ in grp] + [("r", uid), ("p",)],
-                            [dkey, ("g", uid), ("ws", ln)] + ([("dmax", uid)] if self.x6h else []),
-                            nbytes=3 * M * cg * self.esz)
-                    if x8p:             # the raw-output gradient as split planes (dgrad and wgrad operand)
-                        drawp = self.drawp_lane[ln].data_ptr()
-                        add(bwd, L.jr_split_x8p, (draw, M, u.cout, 0, u.cout, drawp, u.cout, 0, u.cout, M * u.cout, s),
-                            "split_x8p", ln, [("draw", ln)], [("drawp", ln)], nbytes=10 * M * u.cout)
-                        draw, dkey = drawp, ("drawp", ln)
-                    def dgrad():
-                        if u.x != g.input_buf:
-                            add(bwd, L.jr_conv2d_bwd_data, (ctypes.byref(d), cdt, draw, self._wd(u), D(u.x), acc, ws,
-                                                            wsb, s),
-                                "conv_dgrad", ln, [dkey, wkey] + xw, d_all(u.x) + [("ws", ln)])
-                            written.add(u.x)
-                    if self.dgrad_first:
-                        dgrad()
-                    if uid in defer:
-                        sg, _, nb = defer[uid]
-                        add(bwd, L.jr_conv2d_bwd_filter_slabs, (ctypes.byref(d), cdt, AX(u.x), draw, sg.slabs, nb,
-                                                                S[wl]),
-                            "conv_wgrad", wl, ax_reads(u.x) + [dkey], [("slab", uid)])
-                        pending.append((sg, uid))
-                    elif wl != ln:
-                        add(bwd, L.jr_conv2d_bwd_filter, (ctypes.byref(d), cdt, AX(u.x), draw,
-                                                          self.grads.data_ptr() + 4 * u.koff,
-                                                          ctypes.c_void_p(self.ws_stem.data_ptr()), wsb, S[wl]),
-                            "conv_wgrad", wl, ax_reads(u.x) + [dkey], [("g", uid), ("wss",)])
-                    else:
-                        add(bwd, L.jr_conv2d_bwd_filter, (ctypes.byref(d), cdt, AX(u.x), draw,
-                                                          self.grads.data_ptr() + 4 * u.koff, ws, wsb, s),
-                            "conv_wgrad", ln, ax_reads(u.x) + [dkey], [("g", uid), ("ws", ln)])
-                    if not self.dgrad_first:
-                        dgrad()
-                    trigger = False
-                    while flush_at and flush_at[0] >= u.koff:
-                        flush_at.pop(0)
-                        trigger = True
-                    if trigger:
-                        flush()
-                    bwd.append(Call("param_ready", u.koff, "hook", 0))
-                elif n.kind == "maxpool" and i in pool_bwd:
-                    continue            # with its producer's BN backward (jr_bn_relu_bwd_maxpool)
-                elif n.kind == "maxpool":
-                    d = self._pool_desc(n, B)
-                    keep.append(d)
-                    add(bwd, L.jr_maxpool3x3s2_bwd, (ctypes.byref(d), dt, self.argmax[i].data_ptr(), D(n.y.buf),
-                                                     D(n.x), acc, s),
-                        "maxpool_bwd", ln, [("am", i), ("d", n.y.buf, n.y.c_off)], d_all(n.x),
-                        nbytes=B * n.c * (n.ho * n.wo * (self.esz + 1) + n.h * n.w * self.esz * (1 + acc)))
-                    written.add(n.x)
-                else:
-                    d = self._pool_desc(n, B)
-                    keep.append(d)
-                    add(bwd, L.jr_avgpool3x3s1_bwd, (ctypes.byref(d), dt, D(n.y.buf), D(n.x), acc, s),
-                        "avgpool_bwd", ln, [("d", n.y.buf, n.y.c_off)], d_all(n.x),
-                        nbytes=B * n.c * (n.ho * n.wo + n.h * n.w * (1 + acc)) * self.esz)
-                    written.add(n.x)
-            flush()
-            P, G = self.params.data_ptr(), self.grads.data_ptr()
-            greads = [("g", u.first.idx) for u in self.cunits] + [("g", "dense")]
-            if self.optimizer == "nesterov":
-                add(opt, L.jr_nesterov_update, (P, G, self.accum.data_ptr(), self.nparam, self.lr,
-                                                self.momentum, 1.0, s0), "nesterov", 0, greads, [("p",), ("acc",)],
-                    nbytes=20 * self.nparam)
-            elif self.optimizer == "momentum":
-                add(opt, L.jr_momentum_update, (P, G, self.accum.data_ptr(), self.nparam, self.lr,
-                                                self.momentum, 1.0, s0), "momentum", 0, greads, [("p",), ("acc",)])
-            elif self.optimizer == "sgd":
-                add(opt, L.jr_sgd_update, (P, G, self.nparam, self.lr, 1.0, s0), "sgd", 0, greads, [("p",)])
-            else:   # adam: lr_t of the step is filled in by apply_update
-                add(opt, L.jr_adam_update, (P, G, self.accum.data_ptr(), self.adam_v.data_ptr(), self.nparam,
-                                            self.lr, self.adam_b1, self.adam_b2, self.adam_eps, 1.0, s0),
-                    "adam", 0, greads, [("p",), ("acc",)])
-        schedule(seq)
-        self._calls[key] = (fwd, bwd, opt, keep, None)
-        return self._calls[key]
+    # ---- backward
+    def _bwd_slab_arena(self, b: Build) -> None:
+        """Deferred filter gradients: per-layer slab regions of one arena."""
+        off = 0
+        for u in self.cunits:
+            d = self._conv_desc(u, b.B)
+            b.keep.append(d)
+            sg = _ffi.WgradSeg()
+            _ffi.check("jr_conv2d_wgrad_seg", self.lib.jr_conv2d_wgrad_seg(ctypes.byref(d), self.cdt, ctypes.byref(sg)))
+            if sg.splits > 1:
+                nb = 4 * sg.splits * sg.m * sg.n
+                sg.dw = self.grads.data_ptr() + 4 * u.koff
+                b.defer[u.first.idx] = (sg, off, nb)
+                off += (nb + 255) // 256 * 256
+        arena = self._t(off // 4 + 64)
+        b.keep.append(arena)
+        for sg, o, _ in b.defer.values():
+            sg.slabs = arena.data_ptr() + o
+        self.slab_bytes = off
 
-    def _run(self, calls, events=None, hook: Optional[Callable[[int], None]] = None) -> None:
-        for c in calls:
-            if c.fn == "param_ready":
-                # no join here: the hook fences the lanes onto ITS stream, and
-                # only when a bucket is actually issued (fence_lanes); lane 0
-                # never waits for lane 1 at a conv unit (VERDICT r05 weak 5)
-                if hook is not None:
-                    if self._join_each:     # round-5 behaviour, A/B runs only (JR_DP_JOIN_EACH=1)
-                        self._join()
-                    hook(c.args)
-                continue
-            st = self.lane_streams[c.lane]
-            if self.precise_waits and not self._capturing:
-                for lj, j in c.pwaits:      # the producing call on the other lane (jr.lanes.schedule)
-                    ev = self._prod_ev.get(j)
-                    if ev is None:          # producer never run in this process (e.g. backward() first): its tail
-                        ev = self._tail_ev[lj]
-                        ev.record(self.lane_streams[lj])
-                        st.wait_event(ev)
-                    elif self._native_ev:
-                        _ffi.check("jr_stream_wait_event", self.lib.jr_stream_wait_event(self._lane_s[c.lane], ev))
-                    else:
-                        st.wait_event(ev)
-            else:
-                for lj in c.waits:          # the other lane's tail (jr.lanes.schedule)
-                    ev = self._tail_ev[lj]
-                    ev.record(self.lane_streams[lj])
-                    st.wait_event(ev)
-            rc = c.fn(*c.args)
-            if rc:
-                raise _ffi.JRError(c.name, rc, _ffi.last_error())
-            if c.record and self.precise_waits and not self._capturing:
-                ev = self._prod_ev.get(c.idx)
-                if ev is None:
-                    ev = self._prod_ev[c.idx] = self._new_event()
-                if self._native_ev:
-                    _ffi.check("jr_event_record", self.lib.jr_event_record(ev, self._lane_s[c.lane]))
-                else:
-                    ev.record(st)
+    def _bwd_flush(self, b: Build) -> None:
+        """One jr_wgrad_reduce over every pending layer (lane 0)."""
+        if not b.pending:
+            return
+        arr = (_ffi.WgradSeg * len(b.pending))()
+        blocks = 0
+        for k, (sg, _) in enumerate(b.pending):
+            arr[k] = sg
+            arr[k].block0 = blocks
+            blocks += sg.blocks
+        table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+        b.keep.append(table)
+        nbytes = sum(4 * sg.m * sg.n * (sg.splits + 1) for sg, _ in b.pending)
+        b.add(b.bwd, self.lib.jr_wgrad_reduce, (table.data_ptr(), len(b.pending), blocks, b.S[0]), "wgrad_reduce", 0,
+              [("slab", uid) for _, uid in b.pending], [("g", uid) for _, uid in b.pending], nbytes=nbytes)
+        b.pending.clear()
 
-    def _new_event(self):
-        if not self._native_ev:
-            return torch.cuda.Event()
-        ev = ctypes.c_void_p()
-        _ffi.check("jr_event_create", self.lib.jr_event_create(ctypes.byref(ev)))
-        weakref.finalize(self, self.lib.jr_event_destroy, ev)
-        return ev
+    def _bwd_head(self, b: Build) -> None:
+        g, s0 = self.g, b.S[0]
+        ob = g.bufs[g.output_buf]
+        b.add(b.bwd, self.lib.jr_head_bwd,
+              (self.head_mode, self.feat.data_ptr(), self._p("dense/kernel"), self.probs.data_ptr(),
+               self.labels.data_ptr(), b.B, ob.c, self.units, self.dfeat.data_ptr(), self._gp("dense/kernel"),
+               self._gp("dense/bias"), s0),
+              "head_bwd", 0, [("feat",), ("p",), ("head",), ("lab",)], [("dfeat",), ("g", "dense")])
+        b.add(b.bwd, self.lib.jr_gap_bwd,
+              (self.dt, self.dfeat.data_ptr(), b.B, ob.h * ob.w, ob.c, self._D(g.output_buf), s0),
+              "gap_bwd", 0, [("dfeat",)], self._d_all(g.output_buf))
 
-    def _fork(self) -> None:
-        """Every lane waits for the work enqueued on lane 0 so far."""
-        if self.nlanes > 1:
-            self._fork_ev.record(self.stream)
-            for st in self.lane_streams[1:]:
-                st.wait_event(self._fork_ev)
+    def _bwd_conv(self, b: Build, i: int, u: ConvUnit) -> None:
+        """A conv launch's backward: the BN backward of its members into the
+        raw-output gradient, the data and the filter gradient, and the
+        param_ready hook (with a flush of the deferred filter gradients where
+        a flush point falls)."""
+        ln, uid = b.lane_of[i], u.first.idx
+        acc = 1 if u.x in b.written else 0
+        d = self._conv_desc(u, b.B)
+        b.keep.append(d)
+        draw, dkey, wl = self.draw_lane[ln].data_ptr(), ("draw", ln), ln
+        if (len(b.S) > 1 and self.draw_stem2 is not None and self.stem_wgrad_lane
+                and i < self._stem_end and ln == 0):    # the stem: filter gradient on lane 1
+            if b.sbuf:
+                draw, dkey = self.draw_stem2.data_ptr(), ("draw2", 0)
+            b.sbuf ^= 1
+            wl = 1
+        if uid in self._in_batch and uid not in b.batch_draw:
+            self._bwd_bn_batch(b, ln, self._in_batch[uid])
+        pool_i = next((j for j, buf in self.pool_bwd.items() if buf == u.first.y.buf), None)
+        if uid in b.batch_draw:
+            draw, dkey = b.batch_draw[uid]
+        if pool_i is not None:
+            self._bwd_bn_pool(b, ln, u, pool_i, draw, dkey)
+        elif uid not in b.batch_draw:
+            self._bwd_bn_groups(b, ln, u, draw, dkey)
+        if self.x8p:             # the raw-output gradient as split planes (dgrad and wgrad operand)
+            M, drawp = b.B * u.ho * u.wo, self.drawp_lane[ln].data_ptr()
+            b.add(b.bwd, self.lib.jr_split_x8p,
+                  (draw, M, u.cout, 0, u.cout, drawp, u.cout, 0, u.cout, M * u.cout, b.S[ln]),
+                  "split_x8p", ln, [("draw", ln)], [("drawp", ln)], nbytes=10 * M * u.cout)
+            draw, dkey = drawp, ("drawp", ln)
+        if self.dgrad_first:
+            self._bwd_dgrad(b, ln, u, d, draw, dkey, acc)
+        self._bwd_wgrad(b, ln, wl, u, d, draw, dkey)
+        if not self.dgrad_first:
+            self._bwd_dgrad(b, ln, u, d, draw, dkey, acc)
+        if b.flush_at and b.flush_at[0] >= u.koff:      # a flush point falls here
+            while b.flush_at and b.flush_at[0] >= u.koff:
+                b.flush_at.pop(0)
+            self._bwd_flush(b)
+        b.bwd.append(Call("param_ready", u.koff, "hook", 0))
 
-    def _join(self) -> None:
-        """Lane 0 waits for every other lane's work enqueued so far."""
-        for ev, st in zip(self._join_ev, self.lane_streams[1:]):
-            ev.record(st)
-            self.stream.wait_event(ev)
+    def _bwd_bn_batch(self, b: Build, ln: int, grp) -> None:
+        """The batched BN backward of a block's launches: issued where the
+        group's first launch comes up (its upstream gradients are final
+        there), on that launch's lane, into the raw-gradient set b.bset."""
+        B = b.B
+        layers = (_ffi.BnBwdLayer * len(grp))()
+        reads, writes = [("r", v.first.idx) for v in grp] + [("p",)], [("ws", ln)]
+        for k, v in enumerate(grp):
+            vid = v.first.idx
+            ptr = self.drawb[b.bset][k].data_ptr()
+            b.batch_draw[vid] = (ptr, ("drawb", b.bset, k))
+            segs = self._bn_segs(v.members)
+            layers[k].nseg = len(segs)
+            for j, sgm in enumerate(segs):
+                layers[k].segs[j] = sgm
+            layers[k].x = self.raw_unit[vid].data_ptr()
+            layers[k].x_c_off, layers[k].x_c_stride = 0, v.cout
+            layers[k].m, layers[k].c = B * v.ho * v.wo, v.cout
+            layers[k].mean = self.mean_unit[vid].data_ptr()
+            layers[k].invstd = self.invstd_unit[vid].data_ptr()
+            layers[k].dx = ptr
+            reads += [("d", m.y.buf, m.y.c_off) for m in v.members]
+            writes += [("drawb", b.bset, k), ("g", vid)]
+        b.keep.append(layers)
+        b.add(b.bwd, self.lib.jr_bn_relu_bwd_batch, (self.dt, len(grp), ctypes.byref(layers), b.WS[ln], b.wsb, b.S[ln]),
+              "bn_relu_bwd", ln, reads, writes, nbytes=sum(3 * B * v.ho * v.wo * v.cout * self.esz for v in grp))
+        b.bset ^= 1
+
+    def _bwd_bn_pool(self, b: Build, ln: int, u: ConvUnit, pool_i: int, draw: int, dkey) -> None:
+        """The max-pool backward adds the BN reduce's sums (a fused stem pool)."""
+        uid, pn, m0 = u.first.idx, self.g.nodes[pool_i], u.first
+        pd = self._pool_desc(pn, b.B)
+        b.keep.append(pd)
+        args = (self.dt, ctypes.byref(pd), self.argmax[pool_i].data_ptr(), self._D(pn.y.buf), self._D(pn.x),
+                self.raw_unit[uid].data_ptr(), u.cout, self.mean_unit[uid].data_ptr(),
+                self.invstd_unit[uid].data_ptr(), self._beta(m0), draw, self._dbeta(m0), b.WS[ln], b.wsb)
+        fn = self.lib.jr_bn_relu_bwd_maxpool
+        if self.x6h:    # also the raw-output gradient's magnitude (dy_absmax of its GEMMs)
+            fn, args = self.lib.jr_bn_relu_bwd_maxpool_absmax, args + (self._dmax(u),)
+        b.add(b.bwd, fn, args + (b.S[ln],),
+              "bn_relu_bwd", ln, [("d", pn.y.buf, pn.y.c_off), ("am", pool_i), ("r", uid), ("p",)],
+              self._d_all(pn.x) + [dkey, ("g", uid), ("ws", ln)] + ([("dmax", uid)] if self.x6h else []),
+              nbytes=4 * b.B * u.ho * u.wo * u.cout * self.esz)
+
+    def _bwd_bn_groups(self, b: Build, ln: int, u: ConvUnit, draw: int, dkey) -> None:
+        """One backward launch set per group of members (_bn_groups)."""
+        uid, M = u.first.idx, b.B * u.ho * u.wo
+        for grp in self._bn_groups(u):
+            co0 = grp[0][1]
+            cg = sum(m.cout for m, _ in grp)
+            segs = (_ffi.BnSeg * len(grp))(*self._bn_segs(m for m, _ in grp))
+            b.keep.append(segs)
+            args = (self.dt, len(grp), ctypes.byref(segs), self.raw_unit[uid].data_ptr(), co0, u.cout, M, cg,
+                    self.mean_unit[uid].data_ptr() + 4 * co0, self.invstd_unit[uid].data_ptr() + 4 * co0,
+                    draw, b.WS[ln], b.wsb)
+            fn = self.lib.jr_bn_relu_bwd_multi
+            if self.x6h:
+                fn, args = self.lib.jr_bn_relu_bwd_multi_absmax, args + (self._dmax(u),)
+            b.add(b.bwd, fn, args + (b.S[ln],),
+                  "bn_relu_bwd", ln, [("d", m.y.buf, m.y.c_off) for m, _ in grp] + [("r", uid), ("p",)],
+                  [dkey, ("g", uid), ("ws", ln)] + ([("dmax", uid)] if self.x6h else []), nbytes=3 * M * cg * self.esz)
+
+    def _bwd_dgrad(self, b: Build, ln: int, u: ConvUnit, d, draw: int, dkey, acc: int) -> None:
+        if u.x == self.g.input_buf:
+            return
+        b.add(b.bwd, self.lib.jr_conv2d_bwd_data,
+              (ctypes.byref(d), self.cdt, draw, self._wd(u), self._D(u.x), acc, b.WS[ln], b.wsb, b.S[ln]),
+              "conv_dgrad", ln, [dkey] + self._w_reads(), self._d_all(u.x) + [("ws", ln)])
+        b.written.add(u.x)
+
+    def _bwd_wgrad(self, b: Build, ln: int, wl: int, u: ConvUnit, d, draw: int, dkey) -> None:
+        """The filter gradient on lane wl: deferred (split-K slabs kept for
+        the next jr_wgrad_reduce) or final; the stem's on lane 1 (wl != ln)
+        use their own workspace."""
+        uid, reads = u.first.idx, self._ax_reads(u.x) + [dkey]
+        if uid in b.defer:
+            sg, _, nb = b.defer[uid]
+            b.add(b.bwd, self.lib.jr_conv2d_bwd_filter_slabs,
+                  (ctypes.byref(d), self.cdt, self._AX(u.x), draw, sg.slabs, nb, b.S[wl]),
+                  "conv_wgrad", wl, reads, [("slab", uid)])
+            b.pending.append((sg, uid))
+            return
+        ws, wskey = (ctypes.c_void_p(self.ws_stem.data_ptr()), ("wss",)) if wl != ln else (b.WS[ln], ("ws", ln))
+        b.add(b.bwd, self.lib.jr_conv2d_bwd_filter,
+              (ctypes.byref(d), self.cdt, self._AX(u.x), draw, self.grads.data_ptr() + 4 * u.koff, ws, b.wsb, b.S[wl]),
+              "conv_wgrad", wl, reads, [("g", uid), wskey])
+
+    def _bwd_pool(self, b: Build, i: int, n: PoolNode) -> None:
+        if i in self.pool_bwd:
+            return              # with its producer's BN backward (jr_bn_relu_bwd_maxpool)
+        L, dt, B, ln = self.lib, self.dt, b.B, b.lane_of[i]
+        acc = 1 if n.x in b.written else 0
+        d = self._pool_desc(n, B)
+        b.keep.append(d)
+        if n.kind == "maxpool":
+            b.add(b.bwd, L.jr_maxpool3x3s2_bwd,
+                  (ctypes.byref(d), dt, self.argmax[i].data_ptr(), self._D(n.y.buf), self._D(n.x), acc, b.S[ln]),
+                  "maxpool_bwd", ln, [("am", i), ("d", n.y.buf, n.y.c_off)], self._d_all(n.x),
+                  nbytes=B * n.c * (n.ho * n.wo * (self.esz + 1) + n.h * n.w * self.esz * (1 + acc)))
+        else:
+            b.add(b.bwd, L.jr_avgpool3x3s1_bwd, (ctypes.byref(d), dt, self._D(n.y.buf), self._D(n.x), acc, b.S[ln]),
+                  "avgpool_bwd", ln, [("d", n.y.buf, n.y.c_off)], self._d_all(n.x),
+                  nbytes=B * n.c * (n.ho * n.wo + n.h * n.w * (1 + acc)) * self.esz)
+        b.written.add(n.x)
+
+    # ---- optimizer
+    def _opt_update(self, b: Build) -> None:
+        L, s0, n = self.lib, b.S[0], self.nparam
+        P, G, acc = self.params.data_ptr(), self.grads.data_ptr(), self.accum.data_ptr()
+        greads = [("g", u.first.idx) for u in self.cunits] + [("g", "dense")]
+        if self.optimizer in ("nesterov", "momentum"):
+            nesterov = self.optimizer == "nesterov"
+            b.add(b.opt, L.jr_nesterov_update if nesterov else L.jr_momentum_update,
+                  (P, G, acc, n, self.lr, self.momentum, 1.0, s0), self.optimizer, 0, greads, [("p",), ("acc",)],
+                  nbytes=20 * n if nesterov else 0)
+        elif self.optimizer == "sgd":
+            b.add(b.opt, L.jr_sgd_update, (P, G, n, self.lr, 1.0, s0), "sgd", 0, greads, [("p",)])
+        else:   # adam: lr_t of the step is filled in by apply_update
+            b.add(b.opt, L.jr_adam_update, (P, G, acc, self.adam_v.data_ptr(), n, self.lr, self.adam_b1, self.adam_b2,
+                                            self.adam_eps, 1.0, s0), "adam", 0, greads, [("p",), ("acc",)])
 
     def fence_lanes(self, stream) -> None:
-        """`stream` (a consumer outside the lanes: the gradient all-reduce's
-        stream) waits for the work enqueued on EVERY lane so far; the lanes
-        themselves wait for nothing.  Used by jr.dist.BucketAllReduce at each
-        bucket's issue point instead of joining the lanes onto lane 0."""
-        if not hasattr(self, "_fence_ev"):
-            self._fence_ev = [torch.cuda.Event() for _ in range(self.nlanes)]
-        for ev, st in zip(self._fence_ev, self.lane_streams):
-            ev.record(st)
-            stream.wait_event(ev)
+        """`stream` (the gradient all-reduce's) waits for the work enqueued on
+        EVERY lane so far; the lanes themselves wait for nothing.  Used by
+        jr.dist.BucketAllReduce at each bucket's issue point instead of
+        joining the lanes onto lane 0."""
+        self.lanes.fence(stream)
 
     # ------------------------------------------------------------------- data
     def set_batch(self, images, labels=None, n: Optional[int] = None, augment=None) -> int:
@@ -1112,20 +1110,18 @@ class Engine:
         (one jr_augment_param per image) -- the uint8 batch then goes through
         jr_image_u8_augment_nhwc (training only; None: no augmentation)."""
         B = int(images.shape[0]) if n is None else n
-        if B > self.batch:
-            raise ValueError(f"batch {B} > planned {self.batch}")
+        self._check_images(images, B)
         ib = self.g.bufs[self.g.input_buf]
-        if tuple(images.shape[1:]) != (ib.h, ib.w, ib.c):
-            raise ValueError(f"images must be [B,{ib.h},{ib.w},{ib.c}] NHWC, got {tuple(images.shape)}")
         with torch.cuda.stream(self.stream):
-            x = torch.as_tensor(images)
-            pixels = B * ib.h * ib.w
-            if augment is not None:
+            if augment is None:
+                self._upload(images, labels, B)
+            else:
+                x = torch.as_tensor(images)
                 if x.dtype != torch.uint8:
                     raise ValueError("augment needs a uint8 batch (float batches are not augmented)")
                 from . import augment as _augment
                 tab = _augment.as_table(augment, B)
-                if getattr(self, "_aug_ws", None) is None:   # once: sized for the planned batch
+                if self._aug_ws is None:   # once: sized for the planned batch
                     nbytes = int(self.lib.jr_augment_workspace_size(self.batch, ib.h, ib.w))
                     self._aug_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
                     self._aug_tab = torch.empty(self.batch * tab.dtype.itemsize, dtype=torch.uint8, device=self.device)
@@ -1135,37 +1131,22 @@ class Engine:
                     xd.data_ptr(), self.acts[self.g.input_buf].data_ptr(), self.dt, B, ib.h, ib.w, ib.c,
                     self.in_stride, self._aug_tab.data_ptr(), self._aug_ws.data_ptr(), self._aug_ws.numel(), self._s))
                 self._keep_u8 = xd
-            elif x.dtype == torch.uint8:
-                xd = x.to(self.device, non_blocking=True).reshape(-1)
-                _ffi.check("jr_image_u8_to_nhwc", self.lib.jr_image_u8_to_nhwc(
-                    xd.data_ptr(), self.acts[self.g.input_buf].data_ptr(), self.dt, pixels, ib.c,
-                    self.in_stride, self._s))
-                self._keep_u8 = xd
-            else:
-                dst = self.acts[self.g.input_buf][:pixels * self.in_stride].view(pixels, self.in_stride)
-                dst[:, ib.c:].zero_()
-                dst[:, :ib.c].copy_(x.to(torch.float32).reshape(pixels, ib.c).to(self.device, non_blocking=True))
-            if labels is not None:
-                y = torch.as_tensor(labels, dtype=torch.float32).reshape(-1)
-                if y.numel() != B * self.units:
-                    raise ValueError("labels must have batch*units elements")
-                self.labels[:y.numel()].copy_(y, non_blocking=True)
+                self._set_labels(labels, B)
         return B
 
     # ------------------------------------------------------------------- runs
     def forward(self, B: Optional[int] = None) -> None:
-        fwd, _, _, _, ev = self._build_calls(B or self.batch)
-        self._fork()
-        self._run(fwd, ev)
-        self._join()
+        fwd = self._build_calls(B or self.batch)[0]
+        self.lanes.fork()
+        self.lanes.run(fwd)
+        self.lanes.join()
 
     def backward(self, B: Optional[int] = None, hook=None) -> None:
-        _, bwd, _, _, ev = self._build_calls(B or self.batch)
-        self._run(bwd, ev, hook)
-        self._join()
+        self.lanes.run(self._build_calls(B or self.batch)[1], hook)
+        self.lanes.join()
 
     def apply_update(self, B: Optional[int] = None, grad_scale: float = 1.0) -> None:
-        _, _, opt, _, ev = self._build_calls(B or self.batch)
+        opt = self._build_calls(B or self.batch)[2]
         if grad_scale != 1.0 or self.optimizer == "adam":
             c = opt[0]
             args = list(c.args)
@@ -1183,7 +1164,7 @@ class Engine:
                 self.adam_b1p = f(self.adam_b1p * f(self.adam_b1))
                 self.adam_b2p = f(self.adam_b2p * f(self.adam_b2))
             opt = [dataclasses.replace(c, args=tuple(args))]
-        self._run(opt, ev)
+        self.lanes.run(opt)
 
     def train_step(self, B: Optional[int] = None, allreduce=None) -> None:
         """fwd + bwd (+ bucketed all-reduce) + optimizer, enqueued on the lanes;
@@ -1204,11 +1185,10 @@ class Engine:
         """Capture fwd+bwd+update for batch B into a HIP graph (single GPU;
         not for Adam, whose step scalar changes every step); the two lane
         streams are captured (fork/join by events) and become parallel
-        branches of the graph.  At most two lanes: on ROCm 7.2, cross-waits
-        among three or more captured streams crashed hipGraphInstantiate, and
-        the same DAG built explicitly on one capturing stream (stream capture
-        dependencies set per call) crashed hipGraphLaunch depending on the
-        process's history; more lanes run eagerly."""
+        branches of the graph, the producer waits its edges.  At most two
+        lanes: on ROCm 7.2, cross-waits among three or more captured streams
+        (waits on events recorded mid-stream) crashed hipGraphInstantiate
+        (DESIGN.md §3); more lanes run eagerly."""
         B = B or self.batch
         if self.optimizer == "adam":
             raise ValueError("Adam steps run eagerly (the step's alpha is a host scalar)")
@@ -1217,20 +1197,17 @@ class Engine:
         fwd, bwd, opt, _, _ = self._build_calls(B)
         torch.cuda.synchronize(self.device)
         _ffi.check("jr_graph_begin", self.lib.jr_graph_begin(self._s))
-        # the producer waits become the graph's edges (two lanes at most: with
-        # three, waits on events recorded mid-stream crashed hipGraphInstantiate
-        # on ROCm 7.2); JR_GRAPH_PRECISE=0: tail waits (bf16 replay 10.04 vs
-        # 9.28 ms per step, eager 9.31: profiles/r05_graph_probe.txt)
-        self._capturing = os.environ.get("JR_GRAPH_PRECISE", "1") == "0"
+        ln = self.lanes
+        ln.capturing = not self.graph_precise
         try:
-            self._fork()
-            self._run(fwd)
-            self._join()
-            self._run(bwd)
-            self._join()
-            self._run(opt)
+            ln.fork()
+            ln.run(fwd)
+            ln.join()
+            ln.run(bwd)
+            ln.join()
+            ln.run(opt)
         finally:
-            self._capturing = False
+            ln.capturing = False
             ex = ctypes.c_void_p()
             _ffi.check("jr_graph_end", self.lib.jr_graph_end(self._s, ctypes.byref(ex)))
         self._graphs[B] = ex.value

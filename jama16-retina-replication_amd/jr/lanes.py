@@ -28,8 +28,13 @@ edges).
 """
 from __future__ import annotations
 
+import ctypes
+import os
+import weakref
 from dataclasses import dataclass, field
 from typing import Dict, List, Sequence, Tuple
+
+from . import _ffi
 
 
 @dataclass
@@ -130,6 +135,157 @@ def schedule(calls: Sequence[Call]) -> None:
             synced[(c.lane, lj)] = tail[lj]
             c.waits.append(lj)
         tail[c.lane] = i
+
+
+class Build:
+    """The state of one call-list build: stream and workspace handles per
+    lane, the node -> lane map, the ctypes objects the calls point into
+    (keep), the phase lists and the step's issue order (seq), and what the
+    backward carries from launch to launch."""
+
+    def __init__(self, B: int, lanes: "Lanes", nl: int, ws_lane, ws_bytes: int, lane_of: Dict[int, int],
+                 flush_points: Sequence[int] = ()):
+        self.B = B
+        self.S = lanes.handles[:nl]
+        self.WS = [ctypes.c_void_p(w.data_ptr()) for w in ws_lane[:nl]]
+        self.wsb = ctypes.c_size_t(ws_bytes)
+        self.lane_of = lane_of
+        self.keep: list = []
+        self.fwd, self.bwd, self.opt, self.seq = [], [], [], []
+        self.split_done = set()         # x8p: input buffers whose operand planes are written
+        self.written = set()            # gradient buffers written so far (later writers accumulate)
+        self.defer: Dict[int, tuple] = {}   # deferred filter gradients: launch -> (WgradSeg, arena offset, bytes)
+        self.pending: list = []         # (WgradSeg, launch) awaiting the next jr_wgrad_reduce
+        self.flush_at = list(flush_points)
+        self.sbuf = self.bset = 0       # alternating raw-gradient buffers: the stem's, the batched BN backwards'
+        self.batch_draw: Dict[int, tuple] = {}      # batched BN backwards: launch -> (raw gradient, its resource)
+
+    def add(self, lst, fn, args, name, lane, reads=(), writes=(), nbytes=0) -> None:
+        c = Call(fn, args, name, lane, tuple(reads), tuple(writes), nbytes=int(nbytes))
+        lst.append(c)
+        self.seq.append(c)
+
+
+class Lanes:
+    """The lanes of one engine: their HIP streams (lane 0 is where every step
+    starts and ends), the events between them, and the flat loop that issues
+    a call list on them."""
+
+    def __init__(self, lib, device, n: int, priorities: Sequence[int] = ()):
+        import torch
+        self.lib, self.n = lib, max(1, int(n))
+        prio = list(priorities) + [0] * self.n
+        self.streams = [torch.cuda.Stream(device=device, priority=prio[i]) for i in range(self.n)]
+        self.handles = [ctypes.c_void_p(st.cuda_stream) for st in self.streams]
+        self._fork_ev = torch.cuda.Event()
+        self._join_ev = [torch.cuda.Event() for _ in range(self.n - 1)]
+        self._tail_ev = [torch.cuda.Event() for _ in range(self.n)]
+        self._fence_ev = [torch.cuda.Event() for _ in range(self.n)]
+        # eager runs: a cross-lane consumer waits for its producing call (an
+        # event recorded right after it) instead of the other lane's tail
+        # (JR_PRECISE_WAITS=0: tail waits; capturing: set while a graph
+        # capture is to use tail waits too)
+        self.precise_waits = os.environ.get("JR_PRECISE_WAITS", "1") != "0"
+        self.capturing = False
+        self.join_each = os.environ.get("JR_DP_JOIN_EACH", "0") == "1"
+        # producer events by call index: libjr's (no timing, no system-scope
+        # fence: cheaper to record), created on first use, or torch's
+        # (JR_LANE_EVENTS=torch, for A/B runs)
+        self.native_ev = os.environ.get("JR_LANE_EVENTS", "native") != "torch"
+        self._prod_ev: Dict[int, object] = {}
+
+    def _new_event(self):
+        if not self.native_ev:
+            import torch
+            return torch.cuda.Event()
+        ev = ctypes.c_void_p()
+        _ffi.check("jr_event_create", self.lib.jr_event_create(ctypes.byref(ev)))
+        weakref.finalize(self, self.lib.jr_event_destroy, ev)
+        return ev
+
+    def fork(self) -> None:
+        """Every lane waits for the work enqueued on lane 0 so far."""
+        if self.n > 1:
+            self._fork_ev.record(self.streams[0])
+            for st in self.streams[1:]:
+                st.wait_event(self._fork_ev)
+
+    def join(self) -> None:
+        """Lane 0 waits for every other lane's work enqueued so far."""
+        for ev, st in zip(self._join_ev, self.streams[1:]):
+            ev.record(st)
+            self.streams[0].wait_event(ev)
+
+    def fence(self, stream) -> None:
+        """`stream` (a consumer outside the lanes) waits for the work enqueued
+        on EVERY lane so far; the lanes themselves wait for nothing."""
+        for ev, st in zip(self._fence_ev, self.streams):
+            ev.record(st)
+            stream.wait_event(ev)
+
+    def run(self, calls: Sequence[Call], hook=None) -> None:
+        streams, handles, tail_ev, prod_ev = self.streams, self.handles, self._tail_ev, self._prod_ev
+        native, precise = self.native_ev, self.precise_waits and not self.capturing
+        for c in calls:
+            if c.fn == "param_ready":
+                # no join here: the hook fences the lanes onto ITS stream, and
+                # only when a bucket is actually issued (fence); lane 0 never
+                # waits for lane 1 at a conv unit (VERDICT r05 weak 5)
+                if hook is not None:
+                    if self.join_each:      # round-5 behaviour, A/B runs only (JR_DP_JOIN_EACH=1)
+                        self.join()
+                    hook(c.args)
+                continue
+            st = streams[c.lane]
+            if precise:
+                for lj, j in c.pwaits:      # the producing call on the other lane (schedule)
+                    ev = prod_ev.get(j)
+                    if ev is None:          # producer never run in this process (e.g. backward() first): its tail
+                        ev = tail_ev[lj]
+                        ev.record(streams[lj])
+                        st.wait_event(ev)
+                    elif native:
+                        _ffi.check("jr_stream_wait_event", self.lib.jr_stream_wait_event(handles[c.lane], ev))
+                    else:
+                        st.wait_event(ev)
+            else:
+                for lj in c.waits:          # the other lane's tail (schedule)
+                    ev = tail_ev[lj]
+                    ev.record(streams[lj])
+                    st.wait_event(ev)
+            rc = c.fn(*c.args)
+            if rc:
+                raise _ffi.JRError(c.name, rc, _ffi.last_error())
+            if c.record and precise:
+                ev = prod_ev.get(c.idx)
+                if ev is None:
+                    ev = prod_ev[c.idx] = self._new_event()
+                if native:
+                    _ffi.check("jr_event_record", self.lib.jr_event_record(ev, handles[c.lane]))
+                else:
+                    ev.record(st)
+
+
+def _sig_arg(v) -> str:
+    if isinstance(v, float) or (isinstance(v, int) and abs(v) < 2 ** 31):
+        return repr(v)
+    if isinstance(v, ctypes.c_size_t):
+        return repr(v.value)
+    return "N" if v is None else "P"    # P: pointers, byref, ctypes structs
+
+
+def signature(calls: Sequence[Call]) -> str:
+    """Canonical pointer-free text of a call sequence, one line per Call in
+    list order: what is launched, where, after what, with which scalars
+    (tests/test_gpu_call_signature.py pins the step's schedule with it)."""
+    lines = []
+    for c in calls:
+        args = c.args if isinstance(c.args, tuple) else (c.args,)
+        fn = c.fn if isinstance(c.fn, str) else getattr(c.fn, "__name__", repr(c.fn))
+        lines.append(f"{c.name} {fn} lane={c.lane} idx={c.idx} reads={list(c.reads)} writes={list(c.writes)} "
+                     f"waits={sorted(c.waits)} pwaits={list(c.pwaits)} record={c.record} nbytes={c.nbytes} "
+                     f"args=({','.join(_sig_arg(v) for v in args)})")
+    return "\n".join(lines) + "\n"
 
 
 def check_schedule(calls: Sequence[Call], precise: bool = False) -> None:

@@ -5,7 +5,7 @@ real step (resources as the engine declares them)."""
 import random
 
 from jr.inception import build_inception_v3
-from jr.lanes import Call, check_schedule, node_lanes, schedule
+from jr.lanes import Call, check_schedule, node_lanes, schedule, signature
 from jr.plan import build_plan
 
 
@@ -59,6 +59,8 @@ def test_schedule_skips_waits_already_implied():
     schedule(calls)
     assert calls[1].waits == [1] and calls[2].waits == []   # lane 0 already waited for lane 1's tail
     assert calls[1].pwaits == [(1, 0)] and calls[2].pwaits == [] and calls[0].record
+    assert signature(calls).splitlines()[1] == ("b None lane=0 idx=1 reads=[('x',)] writes=[('y',)] waits=[1] "
+                                                "pwaits=[(1, 0)] record=False nbytes=0 args=()")
     check_schedule(calls)
     check_schedule(calls, precise=True)
 
