@@ -28,8 +28,6 @@ unsigned* stream_scratch(hipStream_t s, int kind, size_t words);
 // clears it.  Allocated by jr_init (or on first use outside a capture).
 unsigned* device_error_word(hipStream_t s);
 
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // Bijective XCD-aware remap of a flat workgroup id (cdna_hip_programming.md
 // §5 "XCD swizzle must be bijective"): blocks b, b+8, b+16 ... are dealt to one
 // XCD by the dispatcher, so consecutive remapped ids land on one XCD's L2.

@@ -35,13 +35,17 @@
 // k runs over (r, c, ci4 < 4); the input buffer must hold 4 readable
 // (finite; the engine keeps them zero) channels per pixel and the weight
 // rows ci4 >= c_in read as zeros.
+//
+// This file: the fp32-family kernel (k_conv and its two operand splits), the
+// launcher (run_gemm dispatches a plan's config id to its kernel family;
+// run_conv, autotune), the C entry points, and the statistics-finalize and
+// deferred filter-gradient reduce kernels.  What to launch -- the config-id
+// space, tile and split-K choice, workspace sizes, descriptor validation, the
+// tune cache -- is decided by the host-only planner (jr_conv_plan.h).
 #include "jr_conv_impl.h"
 
-#include <array>
-#include <cstdlib>
+#include <algorithm>
 #include <type_traits>
-#include <map>
-#include <mutex>
 #include <vector>
 
 namespace jr {
@@ -838,285 +842,15 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
 }
 
 // ---------------------------------------------------------------- host side
+// (planning: jr_conv_plan.h)
 
-struct Phase {
-  int py, px, r0, c0, na, nb, ey, ex, hc, wc;
-};
-
-// A config id is tile | (splits << 8): splits == 0 lets the planner pick
-// the split-K factor, otherwise it is forced (autotuning explores both).
-constexpr int kSplitShift = 8;
-// split-K factors up to 1024: the stem filter gradients (3 tiles of M = 288,
-// K = 1.4 M pixels) still gain from 256 to 512 slabs (more resident blocks)
-constexpr int kMaxSplits = 1024;
-static int cfg_tile(int cfg) { return cfg & ((1 << kSplitShift) - 1); }
-static int cfg_splits(int cfg) { return cfg >> kSplitShift; }
-
-struct Plan {
-  int cfg;   // encoded id
-  int tile;
-  int M, N, K;
-  int mt, nt, ktiles, splits, kt_per_split;
-  // stream-K (k_conv SK): blocks and iterations (tiles x K-tiles) per block
-  bool sk;
-  int sk_blocks;
-  long long sk_ipb;
-  int sk_slot;   // floats of one block's partial (BM x BN)
-};
-
-// Channel padding of the reduction operand: 16 B DMA pieces hold 4 fp32 or
-// 8 bf16 channels.
-static bool bf16_operands(int dtype) { return dtype == JR_BF16 || dtype == JR_F32_X8P; }
-// JR_F32_X6H shares JR_F32_X8's tiles, config ids and plans (its kernels
-// differ only in the split: fp16, six products, scaled operands)
-static bool x8_family(int dtype) { return dtype == JR_F32_X8 || dtype == JR_F32_X6H; }
-static int chan_pad(int c, int dtype) {
-  const int q = bf16_operands(dtype) ? 8 : 4;
-  return (c + q - 1) / q * q;
-}
-// GEMM tiles of a dtype (the planner heuristic ranks these), and every
-// selectable config: for JR_BF16 the halo-tiled FWD configs follow them.
-static int std_count(int dtype) {
-  return dtype == JR_BF16 ? kNumCfgsBf16 : dtype == JR_F32_X8P ? kNumCfgsX8P : kNumCfgs;
-}
-// JR_F32_X8 also selects the fp32-MFMA kernel of every fp32 tile (ids
-// kNumCfgs + t): both are fp32-accurate, and on the stem's N = 32 / 64
-// filter-gradient GEMMs, whose per-wave split VALU outweighs the 8-product
-// MFMA gain, the fp32 MFMA is the faster one -- autotuning and the pinned
-// tables choose per GEMM (the planner heuristic keeps x8).
-// JR_BF16 ids: [0, 17) GEMM tiles, [17, 25) halo configs, then the wide
-// (8-wave) tiles, then the stream-K grids of the GEMM tiles and of the wide
-// tiles (k_conv_bf16 SK); JR_F32_X8P: [0, 17) tiles, then the wide ones (new
-// ids are appended so committed tile tables keep their meaning).
-static int wide_base(int dtype) {
-  return dtype == JR_BF16 ? kNumCfgsBf16 + kNumHaloBf16 : dtype == JR_F32_X8P ? kNumCfgsX8P : 1 << 20;
-}
-static int wide_count(int dtype) {
-  return dtype == JR_BF16 ? kNumCfgsBf16W : dtype == JR_F32_X8P ? kNumCfgsX8PW : 0;
-}
-// first stream-K id: JR_F32_X8 [28, 42) = the stream-K grid of x8 tile
-// (id - 28) (k_conv SK); JR_BF16 see above
-static int sk_base(int dtype) {
-  return x8_family(dtype) ? 2 * kNumCfgs : dtype == JR_BF16 ? wide_base(dtype) + kNumCfgsBf16W : 1 << 20;
-}
-static int cfg_count(int dtype) {
-  return dtype == JR_BF16 ? sk_base(dtype) + kNumCfgsBf16 + kNumCfgsBf16W
-         : dtype == JR_F32_X8P ? wide_base(dtype) + kNumCfgsX8PW
-         : x8_family(dtype) ? 3 * kNumCfgs
-         : std_count(dtype);
-}
-static bool is_halo(int dtype, int tile) {
-  return dtype == JR_BF16 && tile >= kNumCfgsBf16 && tile < kNumCfgsBf16 + kNumHaloBf16;
-}
-static bool is_wide(int dtype, int tile) { return tile >= wide_base(dtype) && tile < wide_base(dtype) + wide_count(dtype); }
-static bool is_x8_f32(int dtype, int tile) { return x8_family(dtype) && tile >= kNumCfgs && tile < 2 * kNumCfgs; }
-static bool is_sk(int dtype, int tile) { return tile >= sk_base(dtype) && tile < cfg_count(dtype); }
-// the (non-stream-K) id whose tile a stream-K id runs
-static int sk_tile(int dtype, int tile) {
-  const int k = tile - sk_base(dtype);
-  return dtype == JR_BF16 && k >= kNumCfgsBf16 ? wide_base(dtype) + k - kNumCfgsBf16 : k;
-}
-static const TileCfg& tile_cfg(int dtype, int tile) {
-  if (is_sk(dtype, tile)) tile = sk_tile(dtype, tile);
-  if (is_halo(dtype, tile)) return kHaloBf16[tile - kNumCfgsBf16].t;
-  if (is_wide(dtype, tile)) return (dtype == JR_BF16 ? kCfgsBf16W : kCfgsX8PW)[tile - wide_base(dtype)];
-  if (is_x8_f32(dtype, tile)) return kCfgs[tile - kNumCfgs];
-  return (dtype == JR_BF16 ? kCfgsBf16 : dtype == JR_F32_X8P ? kCfgsX8P : kCfgs)[tile];
-}
-// Halo rows a BM-row tile needs: output rows it spans (bound) + kh - 1.
-static int halo_rows(const jr_conv_desc* d, int bm) { return (bm + d->wo - 2) / d->wo + 1 + d->kh - 1; }
-static bool halo_ok(const jr_conv_desc* d, int op, int dtype, int tile) {
-  if (!is_halo(dtype, tile) || op != OP_FWD) return false;
-  const HaloCfg& h = kHaloBf16[tile - kNumCfgsBf16];
-  return d->kh == h.kh && d->kw == h.kw && d->stride_h == 1 && d->stride_w == 1 && d->ho == d->h &&
-         d->wo == d->w && d->c_in % 32 == 0 && halo_rows(d, h.t.bm) * (d->w + d->kw - 1) < h.slots;
-}
-
-static void dgrad_phases(const jr_conv_desc* d, Phase* ph, int* nph) {
-  int k = 0;
-  for (int py = 0; py < d->stride_h; ++py) {
-    for (int px = 0; px < d->stride_w; ++px) {
-      Phase p{};
-      p.py = py; p.px = px;
-      p.hc = py < d->h ? (d->h - py + d->stride_h - 1) / d->stride_h : 0;
-      p.wc = px < d->w ? (d->w - px + d->stride_w - 1) / d->stride_w : 0;
-      p.r0 = (py + d->pad_h) % d->stride_h;
-      p.c0 = (px + d->pad_w) % d->stride_w;
-      p.na = p.r0 < d->kh ? (d->kh - p.r0 + d->stride_h - 1) / d->stride_h : 0;
-      p.nb = p.c0 < d->kw ? (d->kw - p.c0 + d->stride_w - 1) / d->stride_w : 0;
-      p.ey = (py + d->pad_h - p.r0) / d->stride_h;
-      p.ex = (px + d->pad_w - p.c0) / d->stride_w;
-      ph[k++] = p;
-    }
-  }
-  *nph = k;
-}
-
-constexpr int kSkBlocks = 512;     // stream-K grid: 2 x 256 CUs
-constexpr int kSkMinIters = 4;     // K-tiles per stream-K block at least
-
-// Blocks the planner's split-K factor aims for (>= 2.5 per CU). x8 filter
-// gradients aim for 384: their slabs are summed per layer on the GEMM's lane
-// (the fp32 engine default), and fewer slabs measured 0.12-0.14 ms per step
-// faster on two boxes (profiles/r05_ab_wsplit*_f32.txt; 320 / 1,024 slower,
-// bf16 at 384 slower). JR_WGRAD_SPLIT_TARGET overrides it (A/B knob, read once).
-// JR_WGRAD_SPLIT_KMAX (A/B knob, read once): x8 filter gradients aim for 384
-// only where K = B.Ho.Wo is at most this, 640 above it (round 5's
-// K-bounded rule: faster at 299^2 and 587^2, moved the B=16 fp32 curve
-// past the round-5 bar; re-judged against the calibrated bars).
-static int split_target(int dtype, int op, long long K) {
-  static const int wg = [] {
-    const char* e = std::getenv("JR_WGRAD_SPLIT_TARGET");
-    const int v = e ? std::atoi(e) : 0;
-    return v > 0 ? v : 0;
-  }();
-  static const long long kmax = [] {
-    const char* e = std::getenv("JR_WGRAD_SPLIT_KMAX");
-    const long long v = e ? std::atoll(e) : 0;
-    return v > 0 ? v : 0LL;
-  }();
-  if (op != OP_WGRAD) return 640;
-  if (wg > 0) return wg;
-  if (x8_family(dtype) || dtype == JR_F32_X8P) return kmax > 0 && K > kmax ? 640 : 384;
-  return 640;
-}
-
-static Plan plan_with(int dtype, int cfg, int M, int N, int K, int op) {
-  Plan p{};
-  p.M = M; p.N = N; p.K = K; p.cfg = cfg; p.tile = cfg_tile(cfg);
-  const TileCfg& t = tile_cfg(dtype, p.tile);
-  p.mt = (int)ceil_div(M, t.bm);
-  p.nt = (int)ceil_div(N, t.bn);
-  p.ktiles = (int)ceil_div(K, t.bk);
-  const int tiles = p.mt * p.nt;
-  int splits = 1;
-  const int target = split_target(dtype, op, K);
-  if (tiles < target) {
-    splits = (int)ceil_div(target, tiles);
-    const int max_by_k = std::max(1, p.ktiles / 8);
-    splits = std::min(std::min(splits, max_by_k), 256);
-  }
-  if (cfg_splits(cfg) > 0) splits = std::min(cfg_splits(cfg), std::max(p.ktiles, 1));
-  if (is_sk(dtype, p.tile)) {
-    // stream-K: a fixed grid (two blocks per CU at most resident; larger
-    // tiles run it in two equal rounds), at least kSkMinIters K-tiles each
-    // (the config's split field picks the grid instead: 128 x s blocks, s <= 8)
-    const long long grid = cfg_splits(cfg) > 0 ? 128LL * std::min(cfg_splits(cfg), 8) : kSkBlocks;
-    splits = 1;
-    const long long W = (long long)tiles * std::max(p.ktiles, 1);
-    const long long P = std::max(1LL, std::min<long long>(grid, W / kSkMinIters));
-    p.sk = true;
-    p.sk_ipb = ceil_div(W, P);
-    p.sk_blocks = (int)ceil_div(W, p.sk_ipb);
-    p.sk_slot = t.bm * t.bn;   // two per block: the first segment's piece and the owner's last
-  }
-  p.kt_per_split = (int)ceil_div(std::max(p.ktiles, 1), splits);
-  p.splits = (int)ceil_div(std::max(p.ktiles, 1), p.kt_per_split);
-  return p;
-}
-
-static int heuristic_cfg(int dtype, int M, int N, int K) {
-  double best = 1e300;
-  int bc = 0;
-  for (int c = 0; c < std_count(dtype); ++c) {
-    const TileCfg& t = tile_cfg(dtype, c);
-    const double tiles = (double)ceil_div(M, t.bm) * ceil_div(N, t.bn);
-    double work = tiles * t.bm * t.bn / t.eff;
-    // grids that cannot fill the 256 CUs and cannot be split along K lose
-    if (tiles < 256 && ceil_div(K, t.bk) < 32) work *= 256.0 / tiles;
-    if (work < best * 0.999) { best = work; bc = c; }
-  }
-  return bc;
-}
-
-// Autotune cache: (op, GEMM dims, conv geometry) -> best config.
-typedef std::array<int, 13> TuneKey;
-static std::mutex g_tune_mu;
-static std::map<TuneKey, int> g_tuned;
-// bumped whenever an entry of g_tuned changes value (set_config, autotune):
-// a caller that bound plans (split-K slab sizes) to the overrides it applied
-// re-applies them when the generation moved (jr_conv2d_config_generation)
-static unsigned long long g_tune_gen = 1;
-static void tune_set(const TuneKey& k, int cfg) {   // g_tune_mu held; cfg < 0 erases
-  auto it = g_tuned.find(k);
-  if (cfg < 0) {
-    if (it != g_tuned.end()) { g_tuned.erase(it); ++g_tune_gen; }
-  } else if (it == g_tuned.end() || it->second != cfg) {
-    g_tuned[k] = cfg;
-    ++g_tune_gen;
-  }
-}
-
-static TuneKey tune_key(int dtype, int op, int M, int N, int K, const jr_conv_desc* d) {
-  return TuneKey{dtype, op, M, N, K, d->h, d->w, d->kh, d->kw, d->stride_h, d->c_in, d->c_out, d->n};
-}
-
-static Plan make_plan(int dtype, int op, int M, int N, int K, const jr_conv_desc* d, int force_cfg = -1) {
-  int cfg = force_cfg;
-  if (cfg < 0) {
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    auto it = g_tuned.find(tune_key(dtype, op, M, N, K, d));
-    if (it != g_tuned.end()) cfg = it->second;
-  }
-  // a halo config (tuned, pinned or forced) only where its geometry holds
-  if (cfg < 0 || (is_halo(dtype, cfg_tile(cfg)) && !halo_ok(d, op, dtype, cfg_tile(cfg))))
-    cfg = heuristic_cfg(dtype, M, N, K);
-  return plan_with(dtype, cfg, M, N, K, op);
-}
-
-// z-lanes per float4 column of the split-K reduce (k_splitk_reduce and the
-// deferred k_wgrad_reduce: the same G gives the same summation order)
-static int reduce_lanes(const Plan& p) {
-  const long long total = (long long)p.M * p.N / 4;
-  int G = 1;
-  while (G < 64 && G * 4 <= p.splits && total * G < 128 * 1024) G *= 2;
-  return G;
-}
-
-// stream-K: one BM x BN fp32 partial slot per block (the hand-off flags are
-// stream_scratch words)
-static size_t plan_ws(const Plan& p) {
-  if (p.sk) return 2 * (size_t)p.sk_blocks * p.sk_slot * sizeof(float);
-  return p.splits > 1 ? (size_t)p.splits * (size_t)p.M * (size_t)p.N * sizeof(float) : 0;
-}
-
-// Fused BN statistics (FWD): partials of R rows each, P per column.  Without
-// split-K the GEMM epilogue writes one per wave row-group (R = WM); with it,
-// k_splitk_reduce_stats one per block of R rows (~512 blocks).
+// A forward GEMM with fused BN statistics: where (mean, invstd) go.
 struct StatsReq {
   float eps;
   float* mean;
   float* invstd;
   bool defer = false;   // leave the single-stage partials in ws for jr_bn_relu_apply_stats
 };
-
-static void stats_geom(int dtype, const Plan& p, int* P, int* R) {
-  const TileCfg& t = tile_cfg(dtype, p.tile);
-  if (p.splits <= 1) {
-    *R = t.bm / t.wgm;
-    *P = p.mt * t.wgm;
-    return;
-  }
-  const int rpp = 256 / (std::min(p.N, 1024) / 4);
-  int r = std::max<int>(rpp, (int)ceil_div(p.M, 512));
-  r = (int)ceil_div(r, rpp) * rpp;
-  *R = r;
-  *P = (int)ceil_div(p.M, r);
-}
-
-static size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
-#ifndef JR_STATS_CHUNK
-#define JR_STATS_CHUNK 4096
-#endif
-constexpr int kStatsChunk = JR_STATS_CHUNK;   // partials one finalize block combines
-
-static size_t stats_ws(int dtype, const Plan& p) {
-  int P, R;
-  stats_geom(dtype, p, &P, &R);
-  const size_t S = P > kStatsChunk ? (size_t)ceil_div(P, kStatsChunk) : 0;
-  return (2 * (size_t)p.N * P + 3 * (size_t)p.N * S) * sizeof(float);
-}
 
 // Fast-path kernels (UT): FWD/DGRAD when the reduction channel radix is a
 // multiple of BK (every layer but conv1 FWD at BK = 16); WGRAD when BK / wo < ho
@@ -1136,6 +870,7 @@ static void launch_cfg(const ConvArgs& a, dim3 grid, hipStream_t s) {
 // SK: the stream-K grid (k_conv SK) of the tile
 template <int OP, int DBG = 0, bool X8 = false, bool SK = false, bool H6 = false>
 static void launch_op(int cfg, const ConvArgs& a, dim3 grid, hipStream_t s) {
+  static_assert(kNumCfgs == 14, "launch_op: one case per kCfgs entry");
   switch (cfg) {
     case 0: launch_cfg<OP, 0, DBG, X8, SK, H6>(a, grid, s); break;
     case 1: launch_cfg<OP, 1, DBG, X8, SK, H6>(a, grid, s); break;
@@ -1150,51 +885,8 @@ static void launch_op(int cfg, const ConvArgs& a, dim3 grid, hipStream_t s) {
     case 10: launch_cfg<OP, 10, DBG, X8, SK, H6>(a, grid, s); break;
     case 11: launch_cfg<OP, 11, DBG, X8, SK, H6>(a, grid, s); break;
     case 12: launch_cfg<OP, 12, DBG, X8, SK, H6>(a, grid, s); break;
-    default: launch_cfg<OP, 13, DBG, X8, SK, H6>(a, grid, s); break;
+    default: launch_cfg<OP, kNumCfgs - 1, DBG, X8, SK, H6>(a, grid, s); break;   // 13, the last tile
   }
-}
-
-
-static int validate(const jr_conv_desc* d, int op, int dtype) {
-  if (dtype != JR_F32 && dtype != JR_BF16 && dtype != JR_F32_X8 && dtype != JR_F32_X8P && dtype != JR_F32_X6H)
-    return fail(JR_ERR_INVALID, "conv: bad dtype");
-  const int q = bf16_operands(dtype) ? 8 : 4;   // channels per 16 B piece
-  if (!d) return fail(JR_ERR_INVALID, "conv: null descriptor");
-  if (op < OP_FWD || op > OP_WGRAD) return fail(JR_ERR_INVALID, "conv: bad op");
-  if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->c_in <= 0 || d->c_out <= 0 || d->kh <= 0 ||
-      d->kw <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0)
-    return fail(JR_ERR_INVALID, "conv: non-positive dimension");
-  const int ho = (d->h + 2 * d->pad_h - d->kh) / d->stride_h + 1;
-  const int wo = (d->w + 2 * d->pad_w - d->kw) / d->stride_w + 1;
-  if (ho != d->ho || wo != d->wo || ho <= 0 || wo <= 0)
-    return fail(JR_ERR_INVALID, "conv: ho/wo inconsistent with h,w,k,stride,pad");
-  if (d->pad_h >= d->kh || d->pad_w >= d->kw)
-    return fail(JR_ERR_INVALID, "conv: padding must be smaller than the kernel");
-  const int cp = chan_pad(d->c_in, dtype);
-  if (d->x_c_off < 0 || d->x_c_off + cp > d->x_c_stride)
-    return fail(JR_ERR_INVALID, "conv: input channel slice (padded to 4 fp32 / 8 bf16 channels) out of range");
-  if (d->y_c_off < 0 || d->y_c_off + d->c_out > d->y_c_stride)
-    return fail(JR_ERR_INVALID, "conv: output channel slice out of range");
-  if (d->c_out % 16 != 0)
-    return fail(JR_ERR_UNSUPPORTED, "conv: c_out must be a multiple of 16");
-  if (d->x_c_off % q || d->x_c_stride % q || d->y_c_off % q || d->y_c_stride % q)
-    return fail(JR_ERR_INVALID, "conv: channel offsets and strides must be multiples of 4 (fp32) / 8 (bf16)");
-  if (op == OP_DGRAD && d->c_in % q != 0)
-    return fail(JR_ERR_UNSUPPORTED, "conv bwd_data: c_in must be a multiple of 4 (fp32) / 8 (bf16)");
-  if (d->stride_h * d->stride_w > 64) return fail(JR_ERR_UNSUPPORTED, "conv: stride too large");
-  const long long xin = (long long)d->n * d->h * d->w * d->x_c_stride;
-  const long long yout = (long long)d->n * d->ho * d->wo * d->y_c_stride;
-  const long long wsz = (long long)d->kh * d->kw * d->c_in * d->c_out;
-  if (xin >= (1LL << 31) || yout >= (1LL << 31) || wsz >= (1LL << 31))
-    return fail(JR_ERR_INVALID, "conv: tensor too large for 32-bit element offsets");
-  return JR_OK;
-}
-
-static void fill_common(ConvArgs& a, const jr_conv_desc* d, int dtype) {
-  a.n = d->n; a.h = d->h; a.w = d->w; a.cin = d->c_in; a.cp = chan_pad(d->c_in, dtype); a.cout = d->c_out;
-  a.kh = d->kh; a.kw = d->kw; a.sh = d->stride_h; a.sw = d->stride_w;
-  a.ph = d->pad_h; a.pw = d->pad_w; a.ho = d->ho; a.wo = d->wo;
-  a.xo = d->x_c_off; a.xs = d->x_c_stride; a.yo = d->y_c_off; a.ys = d->y_c_stride;
 }
 
 // JR_F32_X6H: the magnitude bounds of the op's A and B operands (FWD x, w;
@@ -1219,13 +911,31 @@ JR_API int jr_debug_set_stamps(void* p) {
 }
 #endif
 
-// One GEMM (plus its split-K reduce) on the stream.
-// defer (WGRAD): write the split-K slabs into ws and stop (jr_wgrad_reduce
-// sums them later, batched with other layers').
-// Workspace of one member of a grouped GEMM: split-K slabs, then the fused
-// BN statistics partials (their two-stage combine space included).
-static size_t member_ws(int dtype, const Plan& p, bool stats) {
-  return align256(stats ? align256(plan_ws(p)) + stats_ws(dtype, p) : plan_ws(p));
+// The GEMM arguments every launch of (d, op, dtype) shares: the geometry,
+// the op's two operands (bf16 kernels reinterpret), their JR_F32_X6H scales
+// and JR_F32_X8P plane strides, and the output addressing.
+static ConvArgs conv_args(const jr_conv_desc* d, int op, int dtype, const void* A, const void* B) {
+  ConvArgs a{};
+  a.n = d->n; a.h = d->h; a.w = d->w; a.cin = d->c_in; a.cp = chan_pad(d->c_in, dtype); a.cout = d->c_out;
+  a.kh = d->kh; a.kw = d->kw; a.sh = d->stride_h; a.sw = d->stride_w;
+  a.ph = d->pad_h; a.pw = d->pad_w; a.ho = d->ho; a.wo = d->wo;
+  a.xo = d->x_c_off; a.xs = d->x_c_stride; a.yo = d->y_c_off; a.ys = d->y_c_stride;
+  fill_scales(a, d, op, dtype);
+  a.A = static_cast<const float*>(A);
+  a.B = static_cast<const float*>(B);
+  if (dtype == JR_F32_X8P) {   // plane strides = each operand tensor's element count (jr.h)
+    const long long xe = (long long)d->n * d->h * d->w * d->x_c_stride;
+    const long long ye = (long long)d->n * d->ho * d->wo * d->y_c_stride;
+    const long long we = (long long)d->kh * d->kw * d->c_in * d->c_out;                  // HWIO
+    const long long wt = (long long)d->c_out * d->kh * d->kw * chan_pad(d->c_in, dtype);  // W^T
+    if (op == OP_FWD) { a.a_ps = xe; a.b_ps = wt; }
+    else if (op == OP_DGRAD) { a.a_ps = ye; a.b_ps = we; }
+    else { a.a_ps = xe; a.b_ps = ye; }
+  }
+  if (op == OP_FWD) { a.c_off = d->y_c_off; a.c_stride = d->y_c_stride; }
+  else if (op == OP_DGRAD) { a.c_off = d->x_c_off; a.c_stride = d->x_c_stride; }
+  else { a.c_off = 0; a.c_stride = d->c_out; }
+  return a;
 }
 
 // (mean, invstd) from the statistics partials [2][N][P] of R rows each
@@ -1261,12 +971,6 @@ static int finalize_stats(float* stats, int sP, int sR, int M, int N, int member
 
 // conv2d_1 as the direct kernel (jr_conv_direct.hip), its statistics
 // partials at ws (member m at ws + m * wsm) and finalized as any GEMM's.
-static size_t conv1_direct_ws(const jr_conv_desc* d) {
-  int P, R;
-  conv1_direct_partials(d, &P, &R);
-  return align256((size_t)2 * d->c_out * P * sizeof(float));
-}
-
 static int run_conv1_direct(const jr_conv_desc* d, int dtype, const void* x, const void* w, void* y, void* ws,
                             size_t ws_bytes, hipStream_t s, const StatsReq* st, int members = 1, long long x_mb = 0,
                             long long w_mb = 0, long long y_mb = 0, long long st_mb = 0) {
@@ -1282,6 +986,9 @@ static int run_conv1_direct(const jr_conv_desc* d, int dtype, const void* x, con
   return finalize_stats(stats, P, R, (int)M, d->c_out, members, (long long)wsm, st, st_mb, s);
 }
 
+// One GEMM (plus its split-K reduce) on the stream.
+// defer (WGRAD): write the split-K slabs into ws and stop (jr_wgrad_reduce
+// sums them later, batched with other layers').
 template <int OP>
 static int run_gemm(int dtype, ConvArgs a, const Plan& p, void* out, void* ws, size_t ws_bytes, hipStream_t s,
                     const StatsReq* st = nullptr, bool defer = false, int members = 1, long long st_mb = 0) {
@@ -1332,45 +1039,46 @@ static int run_gemm(int dtype, ConvArgs a, const Plan& p, void* out, void* ws, s
     if (!a.sk_err) return fail(JR_ERR_HIP, "conv: no device error word (call jr_init before capturing)");
     grid = dim3(p.sk_blocks, members, 1);
   }
-  if (is_halo(dtype, p.tile)) {
-    const HaloCfg& h = kHaloBf16[p.tile - kNumCfgsBf16];
-    a.halo_wp = a.w + a.kw - 1;
-    a.halo_nr = (h.t.bm + a.wo - 2) / a.wo + 1 + a.kh - 1;
-    launch_conv_halo(p.tile - kNumCfgsBf16, a, grid, s);
-  } else if (bf16_operands(dtype)) {
-    // operand address mode (k_conv_bf16 AM): the tap is wave-uniform when the
-    // reduction channel radix is a multiple of BK (0), else every piece walks
-    // its own address with at most one carry per radix and K-tile (1), else
-    // the mixed-radix loop (2: conv1's 8 channels; WGRAD on images shorter
-    // than BK / wo rows)
-    const TileCfg& t = tile_cfg(dtype, p.tile);
-    int am;
-    if (OP == OP_WGRAD) {
-      am = t.bk / a.wo < a.ho ? 1 : 2;
-    } else {
-      const int cred = OP == OP_FWD ? a.cp : a.cout;
-      am = cred % t.bk == 0 ? 0 : cred >= t.bk ? 1 : 2;
+  const CfgEntry& e = cfg_entry(dtype, p.tile);
+  switch (e.kernel) {
+    case Kernel::HALO:
+      a.halo_wp = a.w + a.kw - 1;
+      a.halo_nr = (e.t->bm + a.wo - 2) / a.wo + 1 + a.kh - 1;
+      launch_conv_halo(e.index, a, grid, s);
+      break;
+    case Kernel::BF16:
+    case Kernel::BF16_WIDE: {
+      // operand address mode (k_conv_bf16 AM): the tap is wave-uniform when the
+      // reduction channel radix is a multiple of BK (0), else every piece walks
+      // its own address with at most one carry per radix and K-tile (1), else
+      // the mixed-radix loop (2: conv1's 8 channels; WGRAD on images shorter
+      // than BK / wo rows)
+      const TileCfg& t = *e.t;
+      int am;
+      if (OP == OP_WGRAD) {
+        am = t.bk / a.wo < a.ho ? 1 : 2;
+      } else {
+        const int cred = OP == OP_FWD ? a.cp : a.cout;
+        am = cred % t.bk == 0 ? 0 : cred >= t.bk ? 1 : 2;
+      }
+      const bool wide = e.kernel == Kernel::BF16_WIDE;
+      const int np = dtype == JR_F32_X8P ? 3 : 1;   // operand planes
+      if (e.sk) launch_conv_bf16_sk(OP, e.index, wide, am, a, grid, s);   // JR_BF16 only
+      else if (wide) launch_conv_bf16_wide(OP, e.index, am, a, grid, s, np);
+      else launch_conv_bf16(OP, e.index, am, a, grid, s, np);
+      break;
     }
-    if (p.sk) {   // the stream-K grid of a standard or wide JR_BF16 tile
-      const int tt = sk_tile(dtype, p.tile);
-      const bool w = is_wide(dtype, tt);
-      launch_conv_bf16_sk(OP, w ? tt - wide_base(dtype) : tt, w, am, a, grid, s);
-    } else if (is_wide(dtype, p.tile))
-      launch_conv_bf16_wide(OP, p.tile - wide_base(dtype), am, a, grid, s, dtype == JR_F32_X8P ? 3 : 1);
-    else
-      launch_conv_bf16(OP, p.tile, am, a, grid, s, dtype == JR_F32_X8P ? 3 : 1);
-  } else if (is_x8_f32(dtype, p.tile)) {
-    launch_op<OP>(p.tile - kNumCfgs, a, grid, s);     // the fp32-MFMA kernel of that tile
-  } else if (p.sk && dtype == JR_F32_X6H) {
-    launch_op<OP, 0, true, true, true>(p.tile - 2 * kNumCfgs, a, grid, s);   // stream-K grid, fp16 six products
-  } else if (p.sk) {
-    launch_op<OP, 0, true, true>(p.tile - 2 * kNumCfgs, a, grid, s);   // the stream-K grid of that x8 tile
-  } else if (dtype == JR_F32_X6H) {
-    launch_op<OP, 0, true, false, true>(p.tile, a, grid, s);
-  } else if (dtype == JR_F32_X8) {
-    launch_op<OP, 0, true>(p.tile, a, grid, s);
-  } else {
-    launch_op<OP>(p.tile, a, grid, s);
+    case Kernel::F32_MFMA:
+      launch_op<OP>(e.index, a, grid, s);
+      break;
+    case Kernel::X8_SPLIT: {   // JR_F32_X6H: the fp16 six-product split of the same tile
+      const bool h6 = dtype == JR_F32_X6H;
+      if (e.sk && h6) launch_op<OP, 0, true, true, true>(e.index, a, grid, s);
+      else if (e.sk) launch_op<OP, 0, true, true>(e.index, a, grid, s);
+      else if (h6) launch_op<OP, 0, true, false, true>(e.index, a, grid, s);
+      else launch_op<OP, 0, true>(e.index, a, grid, s);
+      break;
+    }
   }
   int rc = check_launch("conv gemm");
   if (rc) return rc;
@@ -1403,57 +1111,6 @@ static int run_gemm(int dtype, ConvArgs a, const Plan& p, void* out, void* ws, s
   return check_launch("conv split-k reduce");
 }
 
-static void gemm_dims(const jr_conv_desc* d, int op, int dtype, const Phase* ph, int* M, int* N, int* K) {
-  const int cp = chan_pad(d->c_in, dtype);
-  if (op == OP_FWD) { *M = d->n * d->ho * d->wo; *N = d->c_out; *K = d->kh * d->kw * cp; }
-  else if (op == OP_WGRAD) { *M = d->kh * d->kw * cp; *N = d->c_out; *K = d->n * d->ho * d->wo; }
-  else { *M = d->n * ph->hc * ph->wc; *N = d->c_in; *K = ph->na * ph->nb * d->c_out; }
-}
-
-static Plan plan_for(const jr_conv_desc* d, int op, int dtype, const Phase* ph, int force_cfg = -1) {
-  int M, N, K;
-  gemm_dims(d, op, dtype, ph, &M, &N, &K);
-  return make_plan(dtype, op, M, N, K, d, force_cfg);
-}
-
-// Workspace: twice the max over every candidate tile's planned split-K, so
-// any tuned choice fits.
-static size_t ws_bytes_for(const jr_conv_desc* d, int op, int dtype) {
-  Phase ph[64];
-  int nph = 1;
-  if (op == OP_DGRAD) dgrad_phases(d, ph, &nph);
-  size_t w = 0, sw = 0;
-  for (int i = 0; i < nph; ++i) {
-    if (op == OP_DGRAD && (ph[i].na == 0 || ph[i].nb == 0 || ph[i].hc == 0 || ph[i].wc == 0)) continue;
-    for (int c = 0; c < cfg_count(dtype); ++c) {
-      const Plan p = plan_for(d, op, dtype, op == OP_DGRAD ? &ph[i] : nullptr, c);
-      w = std::max(w, plan_ws(p));
-      if (op == OP_FWD) {   // fused BN statistics partials, split or not
-        Plan p1 = p;
-        p1.splits = 1;
-        sw = std::max(sw, std::max(stats_ws(dtype, p), stats_ws(dtype, p1)));
-      }
-    }
-  }
-  // 2x: room for the autotuner's doubled split-K factors; FWD: the statistics
-  // partials live behind the slabs (or, conv2d_1's direct kernel, at 0)
-  if (op == OP_FWD && conv1_direct_ok(d, dtype)) sw = std::max(sw, conv1_direct_ws(d));
-  return op == OP_FWD ? align256(2 * w) + sw : 2 * w;
-}
-
-// DGRAD plan of one stride phase as run_conv launches it (a phase no tap
-// reaches is a K = 0 GEMM that stores zeros).  ok = false: nothing to launch.
-static Plan dgrad_phase_plan(const jr_conv_desc* d, int dtype, const Phase& p, int force_cfg, bool* ok) {
-  *ok = p.hc > 0 && p.wc > 0;
-  if (p.na == 0 || p.nb == 0) {
-    const int M = d->n * p.hc * p.wc;
-    Plan pl = plan_with(dtype, heuristic_cfg(dtype, M, d->c_in, 16), M, d->c_in, 16, OP_DGRAD);
-    pl.K = 0; pl.ktiles = 0; pl.splits = 1; pl.kt_per_split = 1;
-    return pl;
-  }
-  return plan_for(d, OP_DGRAD, dtype, &p, force_cfg);
-}
-
 // Runs the op; force_cfg >= 0 overrides the plan (autotuning).
 static int run_conv(const jr_conv_desc* d, int op, int dtype, const void* A, const void* B, void* C,
                     int accumulate, void* ws, size_t ws_bytes, void* stream, int force_cfg = -1,
@@ -1463,39 +1120,19 @@ static int run_conv(const jr_conv_desc* d, int op, int dtype, const void* A, con
   if (!A || !B || !C) return fail(JR_ERR_INVALID, "conv: null tensor pointer");
   if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15)
     return fail(JR_ERR_INVALID, "conv: tensors must be 16-byte aligned");
-  ConvArgs a{};
-  fill_common(a, d, dtype);
-  fill_scales(a, d, op, dtype);
-  a.A = static_cast<const float*>(A);   // bf16 kernels reinterpret
-  a.B = static_cast<const float*>(B);
+  ConvArgs a = conv_args(d, op, dtype, A, B);
   a.accumulate = accumulate;
-  if (dtype == JR_F32_X8P) {   // plane strides = each operand tensor's element count (jr.h)
-    const long long xe = (long long)d->n * d->h * d->w * d->x_c_stride;
-    const long long ye = (long long)d->n * d->ho * d->wo * d->y_c_stride;
-    const long long we = (long long)d->kh * d->kw * d->c_in * d->c_out;                  // HWIO
-    const long long wt = (long long)d->c_out * d->kh * d->kw * chan_pad(d->c_in, dtype);  // W^T
-    if (op == OP_FWD) { a.a_ps = xe; a.b_ps = wt; }
-    else if (op == OP_DGRAD) { a.a_ps = ye; a.b_ps = we; }
-    else { a.a_ps = xe; a.b_ps = ye; }
-  }
   hipStream_t s = as_stream(stream);
-  void* out = C;
+  const OpPhases phases(d, op);
   if (op == OP_FWD) {
     if (force_cfg < 0 && conv1_direct_ok(d, dtype)) return run_conv1_direct(d, dtype, A, B, C, ws, ws_bytes, s, st);
-    a.c_off = d->y_c_off; a.c_stride = d->y_c_stride;
-    return run_gemm<OP_FWD>(dtype, a, plan_for(d, op, dtype, nullptr, force_cfg), out, ws, ws_bytes, s, st);
+    return run_gemm<OP_FWD>(dtype, a, plan_for(d, op, dtype, phases.ph[0], force_cfg), C, ws, ws_bytes, s, st);
   }
-  if (op == OP_WGRAD) {
-    a.c_off = 0; a.c_stride = d->c_out;
-    return run_gemm<OP_WGRAD>(dtype, a, plan_for(d, op, dtype, nullptr, force_cfg), out, ws, ws_bytes, s);
-  }
-  Phase ph[64];
-  int nph = 0;
-  dgrad_phases(d, ph, &nph);
-  a.c_off = d->x_c_off; a.c_stride = d->x_c_stride;
-  for (int i = 0; i < nph; ++i) {
+  if (op == OP_WGRAD)
+    return run_gemm<OP_WGRAD>(dtype, a, plan_for(d, op, dtype, phases.ph[0], force_cfg), C, ws, ws_bytes, s);
+  for (int i = 0; i < phases.n; ++i) {
     if (only_phase >= 0 && i != only_phase) continue;
-    const Phase& p = ph[i];
+    const Phase& p = phases.ph[i];
     bool ok;
     Plan pl = dgrad_phase_plan(d, dtype, p, force_cfg, &ok);
     if (!ok) continue;
@@ -1503,7 +1140,7 @@ static int run_conv(const jr_conv_desc* d, int op, int dtype, const void* A, con
     a.ey = p.ey; a.ex = p.ex; a.hc = p.hc; a.wc = p.wc;
     // no tap reaches this phase: a K = 0 GEMM stores zeros (or leaves dx)
     if ((p.na == 0 || p.nb == 0) && accumulate) continue;
-    rc = run_gemm<OP_DGRAD>(dtype, a, pl, out, ws, ws_bytes, s);
+    rc = run_gemm<OP_DGRAD>(dtype, a, pl, C, ws, ws_bytes, s);
     if (rc) return rc;
   }
   return JR_OK;
@@ -1515,22 +1152,21 @@ static int autotune(const jr_conv_desc* d, int op, int dtype, const void* A, con
                     size_t ws_bytes, void* stream, int reps) {
   int rc = validate(d, op, dtype);
   if (rc) return rc;
-  Phase ph[64];
-  int nph = 1;
-  if (op == OP_DGRAD) dgrad_phases(d, ph, &nph);
+  const OpPhases phases(d, op);
   hipStream_t s = as_stream(stream);
   hipEvent_t e0, e1;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
     return fail(JR_ERR_HIP, "autotune: hipEventCreate failed");
-  for (int i = 0; i < nph; ++i) {
-    if (op == OP_DGRAD && (ph[i].na == 0 || ph[i].nb == 0 || ph[i].hc == 0 || ph[i].wc == 0)) continue;
+  for (int i = 0; i < phases.n; ++i) {
+    if (!phase_live(op, phases.ph[i])) continue;
     int M, N, K;
-    gemm_dims(d, op, dtype, op == OP_DGRAD ? &ph[i] : nullptr, &M, &N, &K);
+    gemm_dims(d, op, dtype, phases.ph[i], &M, &N, &K);
     const int ncfg = cfg_count(dtype);
     int best_c = heuristic_cfg(dtype, M, N, K);
+    int best_s = 0;   // the incumbent's split-K slabs (0: none)
     float best_t = 1e30f;
     auto time_cfg = [&](int c) -> float {
-      if (is_halo(dtype, cfg_tile(c)) && !halo_ok(d, op, dtype, cfg_tile(c))) return 1e30f;
+      if (cfg_entry(dtype, cfg_tile(c)).halo && !halo_ok(d, op, dtype, cfg_tile(c))) return 1e30f;
       const Plan pc = plan_with(dtype, c, M, N, K, op);
       // FWD runs with the fused BN statistics: their partials must fit too
       if ((op == OP_FWD ? align256(plan_ws(pc)) + stats_ws(dtype, pc) : plan_ws(pc)) > ws_bytes) return 1e30f;
@@ -1548,10 +1184,8 @@ static int autotune(const jr_conv_desc* d, int op, int dtype, const void* A, con
       // written and re-read through HBM, which a back-to-back timing on a hot
       // L2 undercounts): more splits must win by 2 %, fewer may lose by 2 %
       const int ps = pc.splits > 1 ? pc.splits : 0;
-      const int bs = best_t < 1e29f ? (plan_with(dtype, best_c, M, N, K, op).splits > 1
-                                           ? plan_with(dtype, best_c, M, N, K, op).splits : 0) : 0;
-      const float bar = ps > bs ? 0.98f : ps < bs ? 1.02f : 1.0f;
-      if (ms < best_t * bar) { best_t = ms; best_c = c; }
+      const float bar = ps > best_s ? 0.98f : ps < best_s ? 1.02f : 1.0f;
+      if (ms < best_t * bar) { best_t = ms; best_c = c; best_s = ps; }
       return ms;
     };
     // pass 1: every tile with the planner's split-K factor
@@ -1581,7 +1215,6 @@ static int autotune(const jr_conv_desc* d, int op, int dtype, const void* A, con
       }
     }
     if (rc) break;
-    std::lock_guard<std::mutex> lk(g_tune_mu);
     tune_set(tune_key(dtype, op, M, N, K, d), best_c);
   }
   (void)hipEventDestroy(e0);
@@ -1739,7 +1372,7 @@ JR_API int jr_conv2d_wgrad_seg(const jr_conv_desc* d, int dtype, jr_wgrad_seg* s
   int rc = validate(d, OP_WGRAD, dtype);
   if (rc) return rc;
   if (!seg) return fail(JR_ERR_INVALID, "wgrad_seg: null segment");
-  const Plan p = plan_for(d, OP_WGRAD, dtype, nullptr);
+  const Plan p = plan_for(d, OP_WGRAD, dtype, Phase{});
   seg->m = p.M;
   seg->n = p.N;
   seg->splits = p.splits;
@@ -1758,7 +1391,7 @@ JR_API int jr_conv2d_bwd_filter_slabs(const jr_conv_desc* d, int dtype, const vo
   if (!x || !dy || !slabs) return fail(JR_ERR_INVALID, "bwd_filter_slabs: null tensor pointer");
   if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)slabs) & 15)
     return fail(JR_ERR_INVALID, "bwd_filter_slabs: tensors must be 16-byte aligned");
-  const Plan p = plan_for(d, OP_WGRAD, dtype, nullptr);
+  const Plan p = plan_for(d, OP_WGRAD, dtype, Phase{});
   if (p.splits <= 1) return fail(JR_ERR_INVALID, "bwd_filter_slabs: the plan has no split-K (use jr_conv2d_bwd_filter)");
   // the slab region was sized by jr_conv2d_wgrad_seg for the split count the
   // deferred reduce will sum: a plan that changed since (another caller's
@@ -1767,17 +1400,7 @@ JR_API int jr_conv2d_bwd_filter_slabs(const jr_conv_desc* d, int dtype, const vo
   if (slab_bytes != plan_ws(p))
     return fail(JR_ERR_INVALID, "bwd_filter_slabs: the plan's split-K slab bytes differ from the segment's "
                                 "(tile configuration changed since jr_conv2d_wgrad_seg); re-bind the segment");
-  ConvArgs a{};
-  fill_common(a, d, dtype);
-  fill_scales(a, d, OP_WGRAD, dtype);
-  a.A = static_cast<const float*>(x);
-  a.B = static_cast<const float*>(dy);
-  if (dtype == JR_F32_X8P) {
-    a.a_ps = (long long)d->n * d->h * d->w * d->x_c_stride;
-    a.b_ps = (long long)d->n * d->ho * d->wo * d->y_c_stride;
-  }
-  a.c_off = 0; a.c_stride = d->c_out;
-  return run_gemm<OP_WGRAD>(dtype, a, p, nullptr, slabs, slab_bytes, as_stream(stream), nullptr, true);
+  return run_gemm<OP_WGRAD>(dtype, conv_args(d, OP_WGRAD, dtype, x, dy), p, nullptr, slabs, slab_bytes, as_stream(stream), nullptr, true);
 }
 
 JR_API int jr_wgrad_reduce(const jr_wgrad_seg* segs, int32_t nseg, int32_t total_blocks, void* stream) {
@@ -1808,7 +1431,7 @@ JR_API int jr_conv2d_bn_partials_layout(const jr_conv_desc* d, int dtype, jr_bn_
     conv1_direct_partials(d, &P, &R);
     out->ws_offset = 0;
   } else {
-    const Plan p = plan_for(d, OP_FWD, dtype, nullptr);
+    const Plan p = plan_for(d, OP_FWD, dtype, Phase{});
     stats_geom(dtype, p, &P, &R);
     out->ws_offset = (int64_t)align256(plan_ws(p));
   }
@@ -1862,18 +1485,12 @@ JR_API int jr_conv2d_fwd_bn_stats_grouped(const jr_conv_desc* d, int dtype, int 
     return run_conv1_direct(d, dtype, x, w, y, ws, ws_bytes, as_stream(stream), &st, members, x_member_stride * esz,
                             w_member_stride * wsz, y_member_stride * esz, stats_member_stride * 4);
   }
-  ConvArgs a{};
-  fill_common(a, d, dtype);
-  fill_scales(a, d, OP_FWD, dtype);
-  a.A = static_cast<const float*>(x);
-  a.B = static_cast<const float*>(w);
-  a.accumulate = 0;
+  ConvArgs a = conv_args(d, OP_FWD, dtype, x, w);
   a.a_mb = x_member_stride * esz;
   a.b_mb = w_member_stride * esz;
   a.o_mb = y_member_stride * esz;
-  a.c_off = d->y_c_off; a.c_stride = d->y_c_stride;
   const StatsReq st{eps, mean, invstd};
-  return run_gemm<OP_FWD>(dtype, a, plan_for(d, OP_FWD, dtype, nullptr), y, ws, ws_bytes, as_stream(stream), &st,
+  return run_gemm<OP_FWD>(dtype, a, plan_for(d, OP_FWD, dtype, Phase{}), y, ws, ws_bytes, as_stream(stream), &st,
                           false, members, stats_member_stride * 4);
 }
 
@@ -1902,9 +1519,7 @@ JR_API int jr_conv2d_autotune(const jr_conv_desc* d, int op, int dtype, const vo
   return autotune(d, op, dtype, a, b, c, ws, ws_bytes, stream, 3);
 }
 
-JR_API int jr_conv2d_num_configs(int dtype) {
-  return dtype == JR_BF16 || dtype == JR_F32 || x8_family(dtype) || dtype == JR_F32_X8P ? cfg_count(dtype) : 0;
-}
+JR_API int jr_conv2d_num_configs(int dtype) { return cfg_count(dtype); }
 
 // Diagnostic: time `reps` launches of one FWD GEMM (no split-K) of tile
 // config `cfg` in variant dbg (0 normal, 1 no MFMA, 2 no DMA, 3 no LDS reads;
@@ -1919,11 +1534,9 @@ JR_API int jr_conv2d_debug_time(const jr_conv_desc* d, int cfg, int dbg, const v
   if (cfg < 0 || cfg >= kNumCfgs || dbg < 0 || dbg > (x8 ? 4 : 3)) return fail(JR_ERR_INVALID, "debug_time: bad cfg/dbg");
   if (dbg > 0 && chan_pad(d->c_in, JR_F32) % kCfgs[cfg].bk != 0)
     return fail(JR_ERR_UNSUPPORTED, "debug_time: variants need c_in % BK == 0");
-  ConvArgs a{};
-  fill_common(a, d, JR_F32);
-  a.A = (const float*)x; a.B = (const float*)w; a.C = (float*)y;
-  a.c_off = d->y_c_off; a.c_stride = d->y_c_stride;
-  Plan p = plan_for(d, OP_FWD, JR_F32, nullptr, cfg);
+  ConvArgs a = conv_args(d, OP_FWD, JR_F32, x, w);
+  a.C = (float*)y;
+  Plan p = plan_for(d, OP_FWD, JR_F32, Phase{}, cfg);
   p.splits = 1; p.kt_per_split = p.ktiles;
   a.M = p.M; a.N = p.N; a.K = p.K; a.ktiles = p.ktiles; a.kt_per_split = p.kt_per_split; a.ntn = p.nt;
   hipStream_t s = as_stream(stream);
@@ -1958,31 +1571,20 @@ JR_API int jr_conv2d_set_config(const jr_conv_desc* d, int op, int dtype, int ph
   if (rc) return rc;
   if (cfg < -1 || (cfg >= 0 && (cfg_tile(cfg) >= cfg_count(dtype) || cfg_splits(cfg) > kMaxSplits)))
     return fail(JR_ERR_INVALID, "conv set_config: bad config index");
-  Phase ph[64];
-  int nph = 1;
-  if (op == OP_DGRAD) {
-    dgrad_phases(d, ph, &nph);
-    if (phase < 0 || phase >= nph) return fail(JR_ERR_INVALID, "conv set_config: bad phase");
-  }
+  const OpPhases phases(d, op);
+  const Phase* ph = phases.at(op, phase);
+  if (!ph) return fail(JR_ERR_INVALID, "conv set_config: bad phase");
   int M, N, K;
-  gemm_dims(d, op, dtype, op == OP_DGRAD ? &ph[phase] : nullptr, &M, &N, &K);
-  std::lock_guard<std::mutex> lk(g_tune_mu);
+  gemm_dims(d, op, dtype, *ph, &M, &N, &K);
   tune_set(tune_key(dtype, op, M, N, K, d), cfg);   // cfg < 0: back to the planner's choice
   return JR_OK;
 }
 
-JR_API unsigned long long jr_conv2d_config_generation(void) {
-  std::lock_guard<std::mutex> lk(g_tune_mu);
-  return g_tune_gen;
-}
+JR_API unsigned long long jr_conv2d_config_generation(void) { return tune_generation(); }
 
 JR_API int jr_conv2d_get_config(const jr_conv_desc* d, int op, int dtype, int phase) {
   if (!d || validate(d, op, dtype) != JR_OK) return -1;
-  Phase ph[64];
-  int nph = 1;
-  if (op == OP_DGRAD) {
-    dgrad_phases(d, ph, &nph);
-    if (phase < 0 || phase >= nph) return -1;
-  }
-  return plan_for(d, op, dtype, op == OP_DGRAD ? &ph[phase] : nullptr).cfg;
+  const OpPhases phases(d, op);
+  const Phase* ph = phases.at(op, phase);
+  return ph ? plan_for(d, op, dtype, *ph).cfg : -1;
 }

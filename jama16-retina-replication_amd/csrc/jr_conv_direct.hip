@@ -22,9 +22,6 @@
 
 namespace jr {
 
-constexpr int kD1Rows = 1024;   // output pixels per block (= R of the statistics partials)
-constexpr int kD1Cout = 32;
-
 // Chan combine of (n, mean, M2) partials, fp32 (k_splitk_reduce_stats' form).
 __device__ __forceinline__ void chan_combine(float& na, float& ma, float& qa, float nb, float mb, float qb) {
   const float nn = na + nb;
@@ -179,31 +176,6 @@ __global__ void __launch_bounds__(256) k_conv1_direct(const TX* __restrict__ x, 
     stats[(long long)t * P + blockIdx.x] = ma;
     stats[(long long)(kD1Cout + t) * P + blockIdx.x] = qa;
   }
-}
-
-bool conv1_direct_ok(const jr_conv_desc* d, int dtype) {
-  // opt-in (JR_CONV1_DIRECT=1, read once), fp32 only: per kernel (rocprofv3,
-  // tools/conv1_probe.py, profiles/r05_conv1_kernels.txt) the x8 GEMM + its
-  // two-stage finalize take ~138 us and this kernel ~108 us, but the bf16 GEMM
-  // 68.5 us against 91-103 us; and its summation order moves the chaotic
-  // B=16 100-step fp32 loss curve past test_gpu_golden's 3x-envelope bar at
-  // steps 38-45 (the GEMM path stays inside it) -- off by default
-  static const bool on = [] {
-    const char* e = std::getenv("JR_CONV1_DIRECT");
-    return e && e[0] == '1';
-  }();
-  const int q = 4;
-  return on && (dtype == JR_F32 || dtype == JR_F32_X8) && d->c_in <= 3 &&
-         d->x_c_stride == q && d->x_c_off == 0 && d->c_out == kD1Cout && d->y_c_off == 0 &&
-         d->y_c_stride == kD1Cout && d->kh == 3 && d->kw == 3 && d->stride_h == 2 && d->stride_w == 2 &&
-         d->pad_h == 0 && d->pad_w == 0;
-}
-
-int conv1_direct_partials(const jr_conv_desc* d, int* P, int* R) {
-  const long long M = (long long)d->n * d->ho * d->wo;
-  *R = kD1Rows;
-  *P = (int)ceil_div(M, kD1Rows);
-  return JR_OK;
 }
 
 void launch_conv1_direct(const jr_conv_desc* d, int dtype, const void* x, const void* w, void* y, float* stats,

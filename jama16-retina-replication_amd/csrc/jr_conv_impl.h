@@ -1,17 +1,17 @@
 // jr_conv_impl.h — pieces shared by the fp32 (jr_conv.hip) and bf16
 // (jr_conv_bf16.hip) implicit-GEMM convolution kernels: GEMM arguments,
-// output addressing, counted waits, LDS-DMA, the split-K reduce, and the
-// tile-configuration tables the host planner ranks and autotunes.
+// output addressing, counted waits, LDS-DMA, the stream-K hand-off, the
+// epilogue and the split-K reduce.  The tile tables the kernels are
+// instantiated from are the host planner's (jr_conv_plan.h).
 #pragma once
 #include "jr_common.h"
+#include "jr_conv_plan.h"
 
 #include <type_traits>
 
 namespace jr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-enum { OP_FWD = 0, OP_DGRAD = 1, OP_WGRAD = 2 };
 
 // 64 B of zeros in global memory: the DMA source of out-of-bounds taps.
 static __device__ __attribute__((aligned(64))) float g_zero_page[16];
@@ -693,147 +693,11 @@ __global__ void __launch_bounds__(256) k_stats_finalize(const float* __restrict_
                                                         float* mean, float* invstd, float* out, long long p_mb,
                                                         long long st_mb);
 
-struct TileCfg {
-  int bm, bn, wgm, bk, nbuf;
-  double eff;  // relative MFMA efficiency guess used to rank padded work
-  int nw = 4;  // waves per block (256 or 512 threads)
-};
-
-// Candidate tiles (block BMxBN, WGM waves along M, K-tile BK).  The planner
-// ranks them by padded work / eff; jr_conv2d_autotune times them instead.
-// Keep in sync with launch_op's switch.
-static constexpr TileCfg kCfgs[] = {
-    {128, 128, 2, 16, 3, 1.00},  // 0: wave 64x64, 48 KiB LDS
-    {128, 128, 2, 32, 2, 1.00},  // 1: 64 KiB
-    {256, 64, 4, 16, 3, 1.00},   // 2: wave 64x64, 60 KiB
-    {128, 64, 2, 16, 4, 0.92},   // 3: wave 64x32, 48 KiB
-    {128, 64, 2, 32, 2, 0.92},   // 4: 48 KiB
-    {128, 96, 4, 16, 3, 0.90},   // 5: wave 32x96, 42 KiB
-    {256, 32, 4, 16, 4, 0.85},   // 6: wave 64x32, 72 KiB
-    {64, 64, 2, 32, 3, 0.75},    // 7: wave 32x32, 48 KiB
-    {128, 32, 4, 32, 3, 0.75},   // 8: wave 32x32, 60 KiB
-    {64, 128, 2, 32, 2, 0.80},   // 9: wave 32x64, 48 KiB
-    {128, 64, 2, 16, 2, 0.90},   // 10: wave 64x32, 24 KiB
-    {128, 192, 2, 16, 3, 1.02},  // 11: wave 64x96, 60 KiB (N = 192 layers)
-    {256, 96, 4, 16, 3, 1.02},   // 12: wave 64x96, 66 KiB (N = 96 layers)
-    {256, 128, 2, 16, 3, 1.04},  // 13: wave 128x64, 72 KiB
-};
-constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-
-// bf16 tiles (BK in bf16 elements; MFMA v_mfma_f32_32x32x16_bf16).
-static constexpr TileCfg kCfgsBf16[] = {
-    {128, 128, 2, 32, 3, 1.00},  // 0: wave 64x64, 48 KiB LDS
-    {128, 128, 2, 64, 2, 1.00},  // 1: 64 KiB
-    {256, 128, 2, 32, 3, 1.05},  // 2: wave 128x64, 72 KiB
-    {128, 64, 2, 32, 3, 0.92},   // 3: wave 64x32, 36 KiB
-    {256, 64, 4, 32, 3, 1.00},   // 4: wave 64x64, 60 KiB
-    {128, 192, 2, 32, 3, 1.02},  // 5: wave 64x96, 60 KiB
-    {128, 96, 4, 32, 3, 0.90},   // 6: wave 32x96, 42 KiB
-    {64, 64, 2, 64, 3, 0.75},    // 7: wave 32x32, 48 KiB
-    // one block per CU, wave tiles of 128 x 128 / 128 x 96: 16 / 12 MFMAs per
-    // k-step against 4 DMA pieces per wave (0.25-0.33 DMA per MFMA, where the
-    // 64 x 64 wave tiles issue 0.5: the per-MFMA issue budget is the bound)
-    {256, 256, 2, 32, 3, 1.10},  // 8: wave 128x128, 96 KiB
-    {256, 192, 2, 32, 3, 1.08},  // 9: wave 128x96, 84 KiB
-    // deeper rings for the short-K-loop 17x17 / 8x8 GEMMs, whose K-tiles
-    // carry few MFMAs per wave: NBUF - 2 stages stay in flight under the
-    // compute of one (eff just below the same-shape tile above: the untuned
-    // planner keeps its choice, autotuning / the pinned tables decide)
-    {128, 64, 2, 32, 5, 0.91},   // 10: 60 KiB, 3 stages in flight
-    {128, 128, 2, 32, 4, 0.99},  // 11: 64 KiB, 2 in flight
-    {128, 96, 4, 32, 5, 0.89},   // 12: 70 KiB
-    {128, 64, 2, 64, 3, 0.91},   // 13: 72 KiB, twice the MFMAs per K-tile
-    // N = 32 GEMMs (the stem: conv1 / conv2 fwd and wgrad, conv2 / conv3
-    // dgrad with N = c_in = 32), which the BN >= 64 tiles pad to twice the
-    // MFMA work: four waves stacked along M, wave tile 64 x 32 / 32 x 32
-    {256, 32, 4, 32, 3, 0.85},   // 14: 54 KiB
-    {128, 32, 4, 32, 4, 0.80},   // 15: 40 KiB
-    {256, 32, 4, 64, 3, 0.85},   // 16: 108 KiB
-};
-constexpr int kNumCfgsBf16 = sizeof(kCfgsBf16) / sizeof(kCfgsBf16[0]);
-
-// JR_F32_X8P tiles: the bf16 kernel with three operand planes (h, m, l) and
-// eight MFMAs per k-step, so BK = 16 (one k-step) already gives a wave
-// 8 * TM * TN MFMAs per K-tile; LDS = NBUF * 3 * (BM + BN) * BK * 2 B.
-static constexpr TileCfg kCfgsX8P[] = {
-    {128, 128, 2, 16, 3, 1.00},  // 0: wave 64x64, 72 KiB LDS
-    {128, 128, 2, 16, 4, 1.00},  // 1: 96 KiB
-    {256, 128, 2, 16, 3, 1.05},  // 2: wave 128x64, 108 KiB
-    {128, 64, 2, 16, 3, 0.92},   // 3: wave 64x32, 54 KiB
-    {256, 64, 4, 16, 3, 1.00},   // 4: wave 64x64, 81 KiB
-    {128, 192, 2, 16, 3, 1.02},  // 5: wave 64x96, 90 KiB
-    {128, 96, 4, 16, 3, 0.90},   // 6: wave 32x96, 63 KiB
-    {64, 64, 2, 32, 3, 0.75},    // 7: wave 32x32, 72 KiB
-    {256, 256, 2, 16, 2, 1.10},  // 8: wave 128x128, 96 KiB
-    {256, 192, 2, 16, 3, 1.08},  // 9: wave 128x96, 126 KiB
-    {128, 64, 2, 16, 5, 0.91},   // 10: 90 KiB (deeper rings, as kCfgsBf16 10-13)
-    {128, 128, 2, 16, 5, 0.99},  // 11: 120 KiB
-    {128, 96, 4, 16, 4, 0.89},   // 12: 84 KiB
-    {128, 64, 2, 32, 3, 0.91},   // 13: 108 KiB
-    {256, 32, 4, 16, 3, 0.85},   // 14: 81 KiB (N = 32, as kCfgsBf16 14-16)
-    {128, 32, 4, 16, 4, 0.80},   // 15: 60 KiB
-    {256, 32, 4, 32, 2, 0.85},   // 16: 108 KiB
-};
-constexpr int kNumCfgsX8P = sizeof(kCfgsX8P) / sizeof(kCfgsX8P[0]);
-
-// Wide tiles (round 3): 8 waves (512 threads, two per SIMD) on 256-row
-// blocks, one block per CU.  Per K-tile a block moves (BM + BN) * BK operand
-// elements through L2 -> LDS-DMA for BM * BN * BK MACs: at 128 x 128 that
-// ratio needs ~2x the L2 -> LDS rate a CU sustains (~70 GB/s: the bf16 GEMMs
-// ran at 0.1-0.2 of the MFMA peak and x8p at 0.57 MFMA busy), at 256 x 256
-// half of it.  Two waves per SIMD hide each other's DMA issue, LDS reads and
-// barrier waits.  Selectable config ids FOLLOW every older id (bf16: after
-// the halo configs; x8p: after kCfgsX8P), so the committed tile tables keep
-// their meaning.
-static constexpr TileCfg kCfgsBf16W[] = {
-    {256, 256, 2, 32, 3, 1.20, 8},   // 0: wave 128x64, 96 KiB
-    {256, 192, 4, 32, 3, 1.16, 8},   // 1: wave 64x96, 84 KiB
-    {256, 128, 4, 64, 2, 1.12, 8},   // 2: wave 64x64, 96 KiB
-    {128, 256, 2, 64, 2, 1.12, 8},   // 3: wave 64x64, 96 KiB
-    {256, 256, 2, 64, 2, 1.20, 8},   // 4: wave 128x64, 128 KiB
-    {256, 192, 4, 64, 2, 1.16, 8},   // 5: wave 64x96, 112 KiB
-    {256, 96, 8, 64, 2, 1.00, 8},    // 6: wave 32x96, 88 KiB
-    {256, 64, 8, 64, 3, 0.95, 8},    // 7: wave 32x64, 120 KiB
-};
-constexpr int kNumCfgsBf16W = sizeof(kCfgsBf16W) / sizeof(kCfgsBf16W[0]);
-static constexpr TileCfg kCfgsX8PW[] = {
-    {256, 256, 2, 16, 3, 1.20, 8},   // 0: wave 128x64, 144 KiB
-    {256, 192, 4, 16, 3, 1.16, 8},   // 1: wave 64x96, 126 KiB
-    {256, 128, 4, 16, 3, 1.12, 8},   // 2: wave 64x64, 108 KiB
-    {128, 256, 2, 16, 3, 1.12, 8},   // 3: wave 64x64, 108 KiB
-    {256, 96, 8, 16, 4, 1.00, 8},    // 4: wave 32x96, 132 KiB
-    {256, 64, 8, 16, 4, 0.95, 8},    // 5: wave 32x64, 120 KiB
-    {128, 192, 4, 16, 3, 1.05, 8},   // 6: wave 32x96, 90 KiB
-};
-constexpr int kNumCfgsX8PW = sizeof(kCfgsX8PW) / sizeof(kCfgsX8PW[0]);
-
-// Halo-tiled bf16 FWD configurations (jr_conv_halo.hip), bf16 tile ids
-// kNumCfgsBf16 + i: for stride-1 'same' convs of exactly this kh x kw with
-// c_in % 32 == 0 whose halo (output rows a BM tile spans + kh - 1) x (w + kw -
-// 1) fits in slots - 1 (the last slot stays zero).  t.bk = kh*kw*32 (one
-// K-tile = one 32-channel chunk of every tap), so the planner's ktiles is
-// the chunk count.  LDS per stage: slots x 64 B + kh*kw x BN x 64 B.
-struct HaloCfg {
-  int kh, kw, slots;
-  TileCfg t;
-};
-static constexpr HaloCfg kHaloBf16[] = {
-    {1, 7, 224, {128, 64, 2, 7 * 32, 2, 1.0}},   // 0: 17^2 1x7: 9 x 23 = 207 slots; 2 x 42 KiB
-    {7, 1, 256, {128, 64, 2, 7 * 32, 2, 1.0}},   // 1: 17^2 7x1: 15 x 17 = 255 slots; 2 x 44 KiB
-    {3, 3, 272, {128, 96, 4, 9 * 32, 2, 1.0}},   // 2: 35^2 3x3, N = 96: 7 x 37 = 259 slots; 2 x 71 KiB
-    {3, 3, 272, {128, 64, 2, 9 * 32, 2, 1.0}},   // 3: 3x3, N = 64 tiles (8^2: 19 x 10 = 190 slots); 2 x 53 KiB
-    {1, 3, 176, {128, 64, 2, 3 * 32, 3, 1.0}},   // 4: 8^2 1x3: 17 x 10 = 170 slots; 3 x 23 KiB
-    {3, 1, 160, {128, 64, 2, 3 * 32, 3, 1.0}},   // 5: 8^2 3x1: 19 x 8 = 152 slots; 3 x 22 KiB
-    {1, 7, 224, {128, 64, 2, 7 * 32, 3, 1.0}},   // 6: as 0, three stages (126 KiB)
-    {7, 1, 256, {128, 64, 2, 7 * 32, 3, 1.0}},   // 7: as 1, three stages (132 KiB)
-};
-constexpr int kNumHaloBf16 = sizeof(kHaloBf16) / sizeof(kHaloBf16[0]);
+// halo-tiled bf16 FWD (jr_conv_halo.hip): h = index into kHaloBf16
 void launch_conv_halo(int h, const ConvArgs& a, dim3 grid, hipStream_t s);
-// conv2d_1 as a direct VALU convolution (jr_conv_direct.hip): the geometry
-// test, its statistics partials (P of R rows) and the launch (stats may be
-// nullptr; members > 1: blockIdx.y, byte strides)
-bool conv1_direct_ok(const jr_conv_desc* d, int dtype);
-int conv1_direct_partials(const jr_conv_desc* d, int* P, int* R);
+// conv2d_1 as a direct VALU convolution (jr_conv_direct.hip; the geometry
+// test and partials layout are jr_conv_plan.h's): stats may be nullptr;
+// members > 1: blockIdx.y, byte strides
 void launch_conv1_direct(const jr_conv_desc* d, int dtype, const void* x, const void* w, void* y, float* stats,
                          int members, long long x_mb, long long w_mb, long long y_mb, long long s_mb, hipStream_t s);
 

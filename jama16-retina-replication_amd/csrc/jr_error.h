@@ -4,6 +4,7 @@
 // jr_common.h and by the host-only sources (TFRecord / Example parsing)
 // directly, so those build without HIP (the AddressSanitizer build).
 #pragma once
+#include <cstdint>
 #include <string>
 
 #include "../../include/jr.h"
@@ -13,4 +14,7 @@
 namespace jr {
 void set_error(const std::string& msg);
 int fail(int status, const std::string& msg);
+
+// (here, not in jr_common.h: the host-only conv planner sizes with it too)
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 }  // namespace jr

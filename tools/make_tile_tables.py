@@ -4,7 +4,7 @@ loads: every run on every MI355X then sums in the same order (bit-stable,
 VERDICT r1 item 9) at autotuned speed.  Each workload is tuned REPS times in
 fresh processes' worth of engines and the per-op majority kept (timing noise
 between neighbours).  Regenerate whenever a tile table in
-csrc/jr_conv_impl.h changes (tests/test_tile_tables.py checks every id is in
+csrc/jr_conv_plan.h changes (tests/test_tile_tables.py checks every id is in
 range of jr_conv2d_num_configs).
 
   python tools/make_tile_tables.py [out.json] [conv_math ...]     (GPU box)
