@@ -249,6 +249,26 @@ unsigned long long jr_conv2d_config_generation(void);
 /* ---- BatchNormalization(scale=False, eps) + ReLU, training-mode batch
  *      statistics (Keras conv2d_bn; App. C Q1: always batch stats) ----- */
 size_t jr_bn_workspace_size(int64_t m, int32_t c);
+/* What the BN launches over m rows of c channels use (host only, no device
+ * call): 16-byte vectors of vec_width channels; the reductions sum nchunks
+ * chunks of rows_per_chunk rows each (reduce_grid = nchunks; this grouping
+ * fixes the fp64 summation order); single_stage = nchunks <= 512: the
+ * backward's 8-lane finalize runs, and the layer may join a
+ * jr_bn_relu_bwd_batch; finalize_grid of the backward, stats_finalize_grid of
+ * jr_bn_stats, apply_grid of the elementwise passes; k1_offset: the byte
+ * offset of the backward's k1 / k2 behind the partials in the workspace;
+ * fold_rows x (fold_grid_x, fold_grid_y): rows per block and grid of
+ * jr_bn_relu_apply_stats; workspace_size = jr_bn_workspace_size(m, c).
+ * Returns the status every BN entry point gives these (dtype, m, c):
+ * JR_ERR_INVALID for a bad dtype or channel count, JR_ERR_UNSUPPORTED for
+ * more than 256 vectors per row. */
+typedef struct jr_bn_launch_plan {
+  int32_t vec_width, rows_per_chunk, nchunks, single_stage;
+  int32_t reduce_grid, finalize_grid, stats_finalize_grid, apply_grid;
+  int32_t fold_rows, fold_grid_x, fold_grid_y, reserved;
+  int64_t k1_offset, workspace_size;
+} jr_bn_launch_plan;
+int jr_bn_plan(int dtype, int64_t m, int32_t c, jr_bn_launch_plan* out);
 /* x: raw conv output [m][c] contiguous.  mean/invstd: [c] fp32 outputs.
  * invstd = 1/sqrt(biased_var + eps). */
 int jr_bn_stats(int dtype, const void* x, int64_t m, int32_t c, float eps, float* mean, float* invstd,

@@ -227,9 +227,6 @@ JR_API int jr_image_u8_augment_nhwc(const uint8_t* src, void* dst, int dtype, in
   float* part = (float*)ws;
   hipLaunchKernelGGL(k_aug_sums, dim3(P, n), dim3(256), 0, s, src, params, h * w, part);
   if (int rc = check_launch("image_u8_augment sums")) return rc;
-  if (dtype == JR_F32)
-    launch_apply<float>(src, dst, n, h, w, dst_stride, params, P, part, s);
-  else
-    launch_apply<uint16_t>(src, dst, n, h, w, dst_stride, params, P, part, s);
+  by_dtype(dtype, [&](auto t) { launch_apply<decltype(t)>(src, dst, n, h, w, dst_stride, params, P, part, s); });
   return check_launch("image_u8_augment");
 }

@@ -16,29 +16,24 @@
 // row (4 fp32 or 8 bf16 channels) and keeps several rows in flight.
 // Reductions are per-chunk partial sums in fp64 combined in a fixed chunk
 // order (deterministic, no atomics).
+//
+// This file holds the kernels and their launchers.  Every launch decision --
+// chunk geometry, grids, workspace layout, argument validation, the tunable
+// constants and the kernel-argument structs -- is host-only code in
+// jr_bn_plan.h / jr_bn_plan.cpp.
 #include "jr_common.h"
-
-#include <algorithm>
 
 namespace jr {
 
-#ifndef JR_BN_MAX_CHUNKS
-#define JR_BN_MAX_CHUNKS 1024
-#endif
 #ifndef JR_BN_BWD_ROWS
 #define JR_BN_BWD_ROWS 8
 #endif
-constexpr int kMaxChunks = JR_BN_MAX_CHUNKS;  // partial sums per channel (finalize reads them)
 #ifndef JR_BN_F32_SELECT
 #define JR_BN_F32_SELECT 0
 #endif
 constexpr bool kF32Select = JR_BN_F32_SELECT;  // (diagnostic) fp32 reduce loads in the select form
 // rows in flight per thread in the reductions (16 B per row and operand)
 template <int MODE> constexpr int red_rows() { return MODE == 0 ? 16 : JR_BN_BWD_ROWS; }
-#ifndef JR_BN_APP_UNROLL
-#define JR_BN_APP_UNROLL 4
-#endif
-constexpr int kAppUnroll = JR_BN_APP_UNROLL;  // rows per thread in the elementwise passes
 
 // Pins a loaded vector in registers at this point: hipcc otherwise sinks a
 // load into the conditional block of its only use (one wait per row).
@@ -78,77 +73,10 @@ template <> struct Vec<uint16_t> {
   }
 };
 
-constexpr int kFoldCh = 256 / kStatsLanes;   // channels per folded apply block (32)
-// rows per folded apply block (JR_BN_FOLD_ROWS, read once; A/B knob): each
-// block re-combines its 32 channels' partials, so fewer rows per block means
-// more parallel blocks and more redundant partial reads
-static int fold_rows() {
-  static const int v = [] {
-    const char* e = std::getenv("JR_BN_FOLD_ROWS");
-    const int r = e ? std::atoi(e) : 0;
-    return r > 0 ? r : 256;
-  }();
-  return v;
-}
-// the backward's finalize folded into its apply: opt-in (JR_FOLD_BN_BWD=1,
-// read once) -- measured +0.14 ms/step bf16 against k_bn_finalize8 + apply
-// (profiles/r05_ab_rows_bf16.txt), same arithmetic either way
-static bool fold_bwd() {
-  static const bool on = [] {
-    const char* e = std::getenv("JR_FOLD_BN_BWD");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
-// Thread layout shared by every BN kernel: a row of c channels is tpr =
-// c / VW threads (one vector group q each); a 256-thread block covers rpp =
-// 256 / tpr rows per pass (row phase rr).  No index division in the loops.
-struct ChunkGeom {
-  int rows_per_chunk;
-  int nchunks;
-};
-
-static int vec_width(int dtype) { return dtype == JR_BF16 ? 8 : 4; }
-
-static ChunkGeom chunk_geom(int64_t m, int c, int vw) {
-  const int tpr = c / vw;
-  const int rpp = std::max(1, 256 / tpr);
-  // one unrolled batch of rows per thread at least; at most kMaxChunks chunks
-  // (chunks of fewer rows -- more blocks for the 17x17 / 8x8 layers -- measured
-  // slower: 1.47 -> 1.83 ms of reduce + 0.46 -> 0.65 ms of finalize per step)
-#ifndef JR_BN_MIN_ROWS
-#define JR_BN_MIN_ROWS 16
-#endif
-  // (round 2: a smaller minimum for small m only -- 4 rows per thread below
-  // 32,768 rows -- measured slower too: bf16 step 11.46 vs 11.35 ms)
-  const int un = JR_BN_MIN_ROWS;
-  int64_t rpc = std::max<int64_t>(ceil_div(m, kMaxChunks), (int64_t)rpp * un);
-  rpc = ceil_div(rpc, (int64_t)rpp * un) * rpp * un;
-  ChunkGeom g;
-  g.rows_per_chunk = (int)rpc;
-  g.nchunks = (int)ceil_div(m, rpc);
-  return g;
-}
-
-// Backward inputs of one launch over the c channels of a conv launch's raw
-// output: up to kMaxSegs channel segments (the members of a fused sibling
-// group, jr_bn_relu_bwd_multi), each with its own upstream gradient slice
-// and its own beta / dbeta (the members' tensors are separate).  A thread's
-// channel vector is fixed, so it resolves its segment once.
-constexpr int kMaxSegs = 4;
-struct BnSegs {
-  const void* dy[kMaxSegs];
-  const float* beta[kMaxSegs];
-  float* dbeta[kMaxSegs];
-  int dy_off[kMaxSegs], dy_stride[kMaxSegs];
-  int c0[kMaxSegs + 1];   // first channel of each segment; c0[n] = c
-  int n;
-  // backward apply: NULL, or 64 words that receive max |dx| (atomicMax on the
-  // bits of each block's max into word blockIdx.x % 64; JR_F32_X6H scales)
-  float* absmax;
-};
-
+// (BnSegs: jr_bn_plan.h.  Thread layout shared by every BN kernel: a row of c
+// channels is tpr = c / VW threads (one vector group q each); a 256-thread
+// block covers rpp = 256 / tpr rows per pass (row phase rr).  No index
+// division in the loops.)
 __device__ __forceinline__ int seg_of(const BnSegs& sg, int ch) {
   int s = 0;
 #pragma unroll
@@ -410,14 +338,6 @@ __global__ void __launch_bounds__(256) k_bn_relu_apply(const T* __restrict__ x, 
 // The apply of a fused sibling launch's members in ONE launch
 // (jr_bn_relu_apply_multi): the raw output's c channels, segment i its own
 // output slice and beta; per element exactly k_bn_relu_apply's arithmetic.
-struct ApplySegs {
-  void* y[kMaxSegs];
-  const float* beta[kMaxSegs];
-  int y_off[kMaxSegs], y_stride[kMaxSegs];
-  int c0[kMaxSegs + 1];
-  int n;
-};
-
 template <typename T>
 __global__ void __launch_bounds__(256) k_bn_relu_apply_multi(const T* __restrict__ x, int xs, int64_t m, int c,
                                                              const float* __restrict__ mean,
@@ -749,25 +669,7 @@ __global__ void __launch_bounds__(256) k_bn_relu_bwd_apply_fold(BnSegs sg, const
 // (jr_bn_relu_bwd_batch): layer l owns blocks [b0, b0 + blocks) of each
 // launch and runs exactly the single-layer bodies on them (same chunk
 // geometry, same finalize arithmetic: bitwise jr_bn_relu_bwd_multi per layer).
-constexpr int kBnBatchMax = 8;
-struct BnBatchLayer {
-  BnSegs sg;
-  const void* x;
-  void* dx;
-  const float* mean;
-  const float* invstd;
-  double* part;
-  float* k1;
-  float* k2;
-  int64_t m;
-  int c, xs, rpc, nchunks;
-  int b0[3];   // first block in the reduce / finalize / apply launch
-};
-struct BnBatch {
-  BnBatchLayer L[kBnBatchMax];
-  int n;
-};
-
+// (BnBatch: jr_bn_plan.h)
 // the layer owning block b of launch `which` (wave-uniform linear scan)
 __device__ __forceinline__ int bn_batch_layer(const BnBatch& bt, int which, int b) {
   int l = 0;
@@ -797,40 +699,13 @@ __global__ void __launch_bounds__(256) k_bn_relu_bwd_apply_batch(BnBatch bt) {
                        static_cast<T*>(L.dx), blockIdx.x - L.b0[2]);
 }
 
-static int apply_grid(int64_t m, int c, int vw) {
-  const int rpp = 256 / (c / vw);
-  return (int)ceil_div(m, (int64_t)rpp * kAppUnroll);
-}
-
-static int check_common(int dtype, int64_t m, int c) {
-  if (dtype != JR_F32 && dtype != JR_BF16) return fail(JR_ERR_INVALID, "bn: bad dtype");
-  if (m <= 0 || c <= 0) return fail(JR_ERR_INVALID, "bn: empty tensor");
-  if (c % vec_width(dtype) != 0)
-    return fail(JR_ERR_INVALID, "bn: channel count must be a multiple of 4 (fp32) / 8 (bf16)");
-  if (c / vec_width(dtype) > 256) return fail(JR_ERR_UNSUPPORTED, "bn: more than 256 vectors per row");
-  return JR_OK;
-}
-
-static int check_slice(int dtype, int off, int stride, int c) {
-  const int q = vec_width(dtype);
-  return off >= 0 && off + c <= stride && off % q == 0 && stride % q == 0;
-}
-
-// Partials for either dtype's geometry (the query carries no dtype).
-static size_t ws_need(int64_t m, int c) {
-  size_t n = 0;
-  for (int vw : {4, 8})
-    if (c % vw == 0) n = std::max(n, (size_t)chunk_geom(m, c, vw).nchunks);
-  return n * 2 * c * sizeof(double) + 2 * (size_t)c * sizeof(float);
-}
-
 }  // namespace jr
 
 using namespace jr;
 
-JR_API size_t jr_bn_workspace_size(int64_t m, int32_t c) {
-  if (m <= 0 || c <= 0 || c % 4) return 0;
-  return ws_need(m, c);
+// x moved to the first channel of its slice
+static const void* at_channel(int dtype, const void* x, int32_t c_off) {
+  return static_cast<const char*>(x) + (size_t)c_off * elt_size(dtype);
 }
 
 JR_API int jr_bn_stats(int dtype, const void* x, int64_t m, int32_t c, float eps, float* mean,
@@ -838,34 +713,32 @@ JR_API int jr_bn_stats(int dtype, const void* x, int64_t m, int32_t c, float eps
   int rc = check_common(dtype, m, c);
   if (rc) return rc;
   if (!x || !mean || !invstd) return fail(JR_ERR_INVALID, "bn_stats: null pointer");
-  if (!ws || ws_bytes < ws_need(m, c)) return fail(JR_ERR_WORKSPACE, "bn_stats: workspace too small");
-  const ChunkGeom g = chunk_geom(m, c, vec_width(dtype));
+  const jr_bn_launch_plan p = bn_plan(dtype, m, c);
+  if (!ws || ws_bytes < (size_t)p.workspace_size) return fail(JR_ERR_WORKSPACE, "bn_stats: workspace too small");
   double* part = static_cast<double*>(ws);
   hipStream_t s = as_stream(stream);
   const BnSegs none{};
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL((k_bn_reduce<0, float>), dim3(g.nchunks), dim3(256), 0, s, (const float*)x, c, none, m, c,
-                       g.rows_per_chunk, nullptr, nullptr, part);
-  else
-    hipLaunchKernelGGL((k_bn_reduce<0, uint16_t>), dim3(g.nchunks), dim3(256), 0, s, (const uint16_t*)x, c, none,
-                       m, c, g.rows_per_chunk, nullptr, nullptr, part);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_bn_reduce<0, T>), dim3(p.reduce_grid), dim3(256), 0, s, (const T*)x, c, none, m, c,
+                       p.rows_per_chunk, nullptr, nullptr, part);
+  });
   rc = check_launch("bn_stats reduce");
   if (rc) return rc;
-  hipLaunchKernelGGL((k_bn_finalize<0>), dim3((int)ceil_div(c, 4)), dim3(256), 0, s, part, g.nchunks, c, m,
-                     eps, mean, invstd, none);
+  hipLaunchKernelGGL((k_bn_finalize<0>), dim3(p.stats_finalize_grid), dim3(256), 0, s, part, p.nchunks, c, m, eps,
+                     mean, invstd, none);
   return check_launch("bn_stats finalize");
 }
 
 static int bn_apply_launch(int dtype, int members, const void* x, int32_t x_c_stride, int64_t x_mb, int64_t m,
                            int32_t c, const float* mean, const float* invstd, int64_t st_mb, const float* beta,
                            int64_t be_mb, void* y, int32_t y_c_off, int32_t y_c_stride, int64_t y_mb, hipStream_t s) {
-  const dim3 grid(apply_grid(m, c, vec_width(dtype)), members);
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_bn_relu_apply<float>, grid, dim3(256), 0, s, (const float*)x, x_c_stride, m, c, mean,
-                       invstd, beta, (float*)y, y_c_off, y_c_stride, x_mb, y_mb, st_mb, be_mb);
-  else
-    hipLaunchKernelGGL(k_bn_relu_apply<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)x, x_c_stride, m, c,
-                       mean, invstd, beta, (uint16_t*)y, y_c_off, y_c_stride, x_mb, y_mb, st_mb, be_mb);
+  const dim3 grid(bn_plan(dtype, m, c).apply_grid, members);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_bn_relu_apply<T>, grid, dim3(256), 0, s, (const T*)x, x_c_stride, m, c, mean, invstd, beta,
+                       (T*)y, y_c_off, y_c_stride, x_mb, y_mb, st_mb, be_mb);
+  });
   return check_launch("bn_relu_apply");
 }
 
@@ -876,11 +749,9 @@ JR_API int jr_bn_relu_apply(int dtype, const void* x, int32_t x_c_off, int32_t x
   if (rc) return rc;
   if (!x || !mean || !invstd || !beta || !y) return fail(JR_ERR_INVALID, "bn_relu_apply: null pointer");
   if (!check_slice(dtype, x_c_off, x_c_stride, c)) return fail(JR_ERR_INVALID, "bn_relu_apply: bad input slice");
-  const size_t esz = dtype == JR_BF16 ? 2 : 4;
-  x = static_cast<const char*>(x) + (size_t)x_c_off * esz;
   if (!check_slice(dtype, y_c_off, y_c_stride, c)) return fail(JR_ERR_INVALID, "bn_relu_apply: bad output slice");
-  return bn_apply_launch(dtype, 1, x, x_c_stride, 0, m, c, mean, invstd, 0, beta, 0, y, y_c_off, y_c_stride, 0,
-                         as_stream(stream));
+  return bn_apply_launch(dtype, 1, at_channel(dtype, x, x_c_off), x_c_stride, 0, m, c, mean, invstd, 0, beta, 0, y,
+                         y_c_off, y_c_stride, 0, as_stream(stream));
 }
 
 JR_API int jr_bn_relu_apply_multi(int dtype, int nseg, const jr_bn_apply_seg* segs, const void* x, int32_t x_c_off,
@@ -891,33 +762,17 @@ JR_API int jr_bn_relu_apply_multi(int dtype, int nseg, const jr_bn_apply_seg* se
   if (!segs || nseg < 1 || nseg > kMaxSegs) return fail(JR_ERR_INVALID, "bn_relu_apply_multi: 1..4 segments");
   if (!x || !mean || !invstd) return fail(JR_ERR_INVALID, "bn_relu_apply_multi: null pointer");
   if (!check_slice(dtype, x_c_off, x_c_stride, c)) return fail(JR_ERR_INVALID, "bn_relu_apply_multi: bad input slice");
-  ApplySegs sg{};
-  sg.n = nseg;
-  int c0 = 0;
-  for (int i = 0; i < nseg; ++i) {
-    const jr_bn_apply_seg& e = segs[i];
-    if (!e.y || !e.beta) return fail(JR_ERR_INVALID, "bn_relu_apply_multi: null pointer in a segment");
-    if (e.c <= 0 || e.c % vec_width(dtype) || !check_slice(dtype, e.y_c_off, e.y_c_stride, e.c))
-      return fail(JR_ERR_INVALID, "bn_relu_apply_multi: bad output segment");
-    sg.y[i] = e.y;
-    sg.beta[i] = e.beta;
-    sg.y_off[i] = e.y_c_off;
-    sg.y_stride[i] = e.y_c_stride;
-    sg.c0[i] = c0;
-    c0 += e.c;
-  }
-  if (c0 != c) return fail(JR_ERR_INVALID, "bn_relu_apply_multi: segment channels must sum to c");
-  sg.c0[nseg] = c;
-  const size_t esz = dtype == JR_BF16 ? 2 : 4;
-  x = static_cast<const char*>(x) + (size_t)x_c_off * esz;
-  const dim3 grid(apply_grid(m, c, vec_width(dtype)));
+  ApplySegs sg;
+  rc = apply_segs(dtype, nseg, segs, c, sg);
+  if (rc) return rc;
+  x = at_channel(dtype, x, x_c_off);
+  const dim3 grid(bn_plan(dtype, m, c).apply_grid);
   hipStream_t s = as_stream(stream);
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_bn_relu_apply_multi<float>, grid, dim3(256), 0, s, (const float*)x, x_c_stride, m, c, mean,
-                       invstd, sg);
-  else
-    hipLaunchKernelGGL(k_bn_relu_apply_multi<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)x, x_c_stride, m, c,
-                       mean, invstd, sg);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_bn_relu_apply_multi<T>, grid, dim3(256), 0, s, (const T*)x, x_c_stride, m, c, mean, invstd,
+                       sg);
+  });
   return check_launch("bn_relu_apply_multi");
 }
 
@@ -932,24 +787,17 @@ JR_API int jr_bn_relu_apply_stats(int dtype, const void* x, int32_t x_c_off, int
     return fail(JR_ERR_INVALID, "bn_relu_apply_stats: bad input / output slice");
   if (P < 1 || R < 1 || (int64_t)P * R < m || stat_c_off < 0 || stat_c_off + c > n_total || m >= (1LL << 31))
     return fail(JR_ERR_INVALID, "bn_relu_apply_stats: partials inconsistent with the slice");
-  const size_t esz = dtype == JR_BF16 ? 2 : 4;
-  x = static_cast<const char*>(x) + (size_t)x_c_off * esz;
+  x = at_channel(dtype, x, x_c_off);
   const float* pm = part + (int64_t)stat_c_off * P;
   const float* pq = part + (int64_t)(n_total + stat_c_off) * P;
-  // rows per block: a multiple of one pass x unroll (the 32-channel group's
-  // widest pass), about JR_BN_FOLD_ROWS (each block re-combines its group's
-  // partials: fewer, longer blocks read them fewer times)
-  const int vw = vec_width(dtype);
-  const int step = 256 / (kFoldCh / vw) * kAppUnroll;
-  const int rpb = (int)std::max<int64_t>(step, (int64_t)(fold_rows() + step - 1) / step * step);
-  const dim3 grid((unsigned)ceil_div(m, rpb), (unsigned)ceil_div(c, kFoldCh));
+  const jr_bn_launch_plan p = bn_plan(dtype, m, c);
+  const dim3 grid(p.fold_grid_x, p.fold_grid_y);
   hipStream_t s = as_stream(stream);
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_bn_relu_apply_stats<float>, grid, dim3(256), 0, s, (const float*)x, x_c_stride, m, c, pm, pq,
-                       P, R, eps, mean, invstd, beta, (float*)y, y_c_off, y_c_stride, rpb);
-  else
-    hipLaunchKernelGGL(k_bn_relu_apply_stats<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)x, x_c_stride, m, c,
-                       pm, pq, P, R, eps, mean, invstd, beta, (uint16_t*)y, y_c_off, y_c_stride, rpb);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_bn_relu_apply_stats<T>, grid, dim3(256), 0, s, (const T*)x, x_c_stride, m, c, pm, pq, P, R,
+                       eps, mean, invstd, beta, (T*)y, y_c_off, y_c_stride, p.fold_rows);
+  });
   return check_launch("bn_relu_apply_stats");
 }
 
@@ -966,12 +814,11 @@ JR_API int jr_bn_relu_apply_grouped(int dtype, int32_t members, const void* x, i
     return fail(JR_ERR_INVALID, "bn_relu_apply_grouped: negative member stride");
   if (!check_slice(dtype, x_c_off, x_c_stride, c) || !check_slice(dtype, y_c_off, y_c_stride, c))
     return fail(JR_ERR_INVALID, "bn_relu_apply_grouped: bad input / output slice");
-  const size_t esz = dtype == JR_BF16 ? 2 : 4;
+  const size_t esz = elt_size(dtype);
   if (((x_member_stride * esz) | (y_member_stride * esz)) & 15)
     return fail(JR_ERR_INVALID, "bn_relu_apply_grouped: member strides must be 16-byte multiples");
-  x = static_cast<const char*>(x) + (size_t)x_c_off * esz;
-  return bn_apply_launch(dtype, members, x, x_c_stride, x_member_stride * esz, m, c, mean, invstd,
-                         stats_member_stride * 4, beta, beta_member_stride * 4, y, y_c_off, y_c_stride,
+  return bn_apply_launch(dtype, members, at_channel(dtype, x, x_c_off), x_c_stride, x_member_stride * esz, m, c, mean,
+                         invstd, stats_member_stride * 4, beta, beta_member_stride * 4, y, y_c_off, y_c_stride,
                          y_member_stride * esz, as_stream(stream));
 }
 
@@ -979,13 +826,12 @@ JR_API int jr_bn_relu_apply_grouped(int dtype, int32_t members, const void* x, i
 static int bn_bwd_apply_launch(int dtype, const BnSegs& sg, const void* x, int32_t x_c_stride, int64_t m, int32_t c,
                                const float* mean, const float* invstd, const float* k1, const float* k2, void* dx,
                                hipStream_t s) {
-  const int grid = apply_grid(m, c, vec_width(dtype));
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_bn_relu_bwd_apply<float>, dim3(grid), dim3(256), 0, s, sg, (const float*)x, x_c_stride, m,
-                       c, mean, invstd, k1, k2, (float*)dx);
-  else
-    hipLaunchKernelGGL(k_bn_relu_bwd_apply<uint16_t>, dim3(grid), dim3(256), 0, s, sg, (const uint16_t*)x,
-                       x_c_stride, m, c, mean, invstd, k1, k2, (uint16_t*)dx);
+  const dim3 grid(bn_plan(dtype, m, c).apply_grid);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_bn_relu_bwd_apply<T>, grid, dim3(256), 0, s, sg, (const T*)x, x_c_stride, m, c, mean, invstd,
+                       k1, k2, (T*)dx);
+  });
   return check_launch("bn_bwd apply");
 }
 
@@ -993,39 +839,33 @@ static int bn_bwd_apply_launch(int dtype, const BnSegs& sg, const void* x, int32
 static int bn_bwd_launch(int dtype, const BnSegs& sg, const void* x, int32_t x_c_stride, int64_t m, int32_t c,
                          const float* mean, const float* invstd, void* dx, void* ws, size_t ws_bytes,
                          hipStream_t s) {
-  if (!ws || ws_bytes < ws_need(m, c)) return fail(JR_ERR_WORKSPACE, "bn_relu_bwd: workspace too small");
-  const int vw = vec_width(dtype);
-  const ChunkGeom g = chunk_geom(m, c, vw);
+  const jr_bn_launch_plan p = bn_plan(dtype, m, c);
+  if (!ws || ws_bytes < (size_t)p.workspace_size) return fail(JR_ERR_WORKSPACE, "bn_relu_bwd: workspace too small");
   double* part = static_cast<double*>(ws);
-  float* k1 = reinterpret_cast<float*>(part + (size_t)g.nchunks * 2 * c);
+  float* k1 = reinterpret_cast<float*>(static_cast<char*>(ws) + p.k1_offset);
   float* k2 = k1 + c;
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL((k_bn_reduce<1, float>), dim3(g.nchunks), dim3(256), 0, s, (const float*)x, x_c_stride, sg,
-                       m, c, g.rows_per_chunk, mean, invstd, part);
-  else
-    hipLaunchKernelGGL((k_bn_reduce<1, uint16_t>), dim3(g.nchunks), dim3(256), 0, s, (const uint16_t*)x,
-                       x_c_stride, sg, m, c, g.rows_per_chunk, mean, invstd, part);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_bn_reduce<1, T>), dim3(p.reduce_grid), dim3(256), 0, s, (const T*)x, x_c_stride, sg, m, c,
+                       p.rows_per_chunk, mean, invstd, part);
+  });
   int rc = check_launch("bn_bwd reduce");
   if (rc) return rc;
-  if (g.nchunks <= kFoldMaxP) {
+  if (p.single_stage) {
     if (fold_bwd() && !sg.absmax) {   // the finalize inside the apply: one kernel boundary fewer
-      const int vw = vec_width(dtype);
-      const int step = 256 / (kFoldCh / vw) * kAppUnroll;
-      const int rpb = (int)std::max<int64_t>(step, (int64_t)(fold_rows() + step - 1) / step * step);
-      const dim3 grid((unsigned)ceil_div(m, rpb), (unsigned)ceil_div(c, kFoldCh));
-      if (dtype == JR_F32)
-        hipLaunchKernelGGL(k_bn_relu_bwd_apply_fold<float>, grid, dim3(256), 0, s, sg, (const float*)x, x_c_stride, m,
-                           c, mean, invstd, (const double*)part, g.nchunks, (float*)dx, rpb);
-      else
-        hipLaunchKernelGGL(k_bn_relu_bwd_apply_fold<uint16_t>, grid, dim3(256), 0, s, sg, (const uint16_t*)x,
-                           x_c_stride, m, c, mean, invstd, (const double*)part, g.nchunks, (uint16_t*)dx, rpb);
+      const dim3 grid(p.fold_grid_x, p.fold_grid_y);
+      by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_bn_relu_bwd_apply_fold<T>, grid, dim3(256), 0, s, sg, (const T*)x, x_c_stride, m, c, mean,
+                           invstd, (const double*)part, p.nchunks, (T*)dx, p.fold_rows);
+      });
       return check_launch("bn_bwd apply (fold)");
     }
-    hipLaunchKernelGGL(k_bn_finalize8, dim3((int)ceil_div(c, kFoldCh)), dim3(256), 0, s, (const double*)part,
-                       g.nchunks, c, m, k1, k2, sg);
-  } else {
-    hipLaunchKernelGGL((k_bn_finalize<1>), dim3((int)ceil_div(c, 4)), dim3(256), 0, s, part, g.nchunks, c, m, 0.f,
+    hipLaunchKernelGGL(k_bn_finalize8, dim3(p.finalize_grid), dim3(256), 0, s, (const double*)part, p.nchunks, c, m,
                        k1, k2, sg);
+  } else {
+    hipLaunchKernelGGL((k_bn_finalize<1>), dim3(p.finalize_grid), dim3(256), 0, s, part, p.nchunks, c, m, 0.f, k1, k2,
+                       sg);
   }
   rc = check_launch("bn_bwd finalize");
   if (rc) return rc;
@@ -1038,40 +878,6 @@ JR_API int jr_bn_relu_bwd(int dtype, const void* dy, int32_t dy_c_off, int32_t d
                           void* stream) {
   jr_bn_seg seg{dy, dy_c_off, dy_c_stride, c, beta, dbeta};
   return jr_bn_relu_bwd_multi(dtype, 1, &seg, x, x_c_off, x_c_stride, m, c, mean, invstd, dx, ws, ws_bytes, stream);
-}
-
-// Validates the segments and slices of a backward launch set; on success
-// fills sg and moves x / dx to the slice's first channel.
-static int bwd_setup(int dtype, int nseg, const jr_bn_seg* segs, const void*& x, int32_t x_c_off, int32_t x_c_stride,
-                     int64_t m, int32_t c, const float* mean, const float* invstd, void*& dx, BnSegs& sg) {
-  int rc = check_common(dtype, m, c);
-  if (rc) return rc;
-  if (!segs || nseg < 1 || nseg > kMaxSegs) return fail(JR_ERR_INVALID, "bn_relu_bwd: 1..4 segments");
-  if (!x || !mean || !invstd || !dx) return fail(JR_ERR_INVALID, "bn_relu_bwd: null pointer");
-  if (!check_slice(dtype, x_c_off, x_c_stride, c)) return fail(JR_ERR_INVALID, "bn_relu_bwd: bad x / dx slice");
-  const size_t esz = dtype == JR_BF16 ? 2 : 4;
-  sg = BnSegs{};
-  sg.n = nseg;
-  int c0 = 0;
-  for (int i = 0; i < nseg; ++i) {
-    const jr_bn_seg& e = segs[i];
-    if (!e.dy || !e.beta || !e.dbeta) return fail(JR_ERR_INVALID, "bn_relu_bwd: null pointer in a segment");
-    if (e.c <= 0 || e.c % vec_width(dtype) != 0)
-      return fail(JR_ERR_INVALID, "bn_relu_bwd: segment channels must be a positive multiple of 4 (fp32) / 8 (bf16)");
-    if (!check_slice(dtype, e.dy_c_off, e.dy_c_stride, e.c)) return fail(JR_ERR_INVALID, "bn_relu_bwd: bad dy slice");
-    sg.dy[i] = e.dy;
-    sg.dy_off[i] = e.dy_c_off;
-    sg.dy_stride[i] = e.dy_c_stride;
-    sg.beta[i] = e.beta;
-    sg.dbeta[i] = e.dbeta;
-    sg.c0[i] = c0;
-    c0 += e.c;
-  }
-  if (c0 != c) return fail(JR_ERR_INVALID, "bn_relu_bwd: segment channels must sum to c");
-  sg.c0[nseg] = c;
-  x = static_cast<const char*>(x) + (size_t)x_c_off * esz;
-  dx = static_cast<char*>(dx) + (size_t)x_c_off * esz;
-  return JR_OK;
 }
 
 JR_API int jr_bn_relu_bwd_multi(int dtype, int nseg, const jr_bn_seg* segs, const void* x, int32_t x_c_off,
@@ -1092,71 +898,26 @@ JR_API int jr_bn_relu_bwd_multi_absmax(int dtype, int nseg, const jr_bn_seg* seg
   return bn_bwd_launch(dtype, sg, x, x_c_stride, m, c, mean, invstd, dx, ws, ws_bytes, as_stream(stream));
 }
 
-// workspace of a batched backward: each layer's ws_need, 256-byte aligned
-static size_t batch_ws(int n, const jr_bn_bwd_layer* layers) {
-  size_t off = 0;
-  for (int l = 0; l < n; ++l) off += (ws_need(layers[l].m, layers[l].c) + 255) / 256 * 256;
-  return off;
-}
-
-JR_API size_t jr_bn_relu_bwd_batch_workspace_size(int32_t n, const jr_bn_bwd_layer* layers) {
-  if (n < 1 || n > kBnBatchMax || !layers) return 0;
-  return batch_ws(n, layers);
-}
-
 JR_API int jr_bn_relu_bwd_batch(int dtype, int32_t n, const jr_bn_bwd_layer* layers, void* ws, size_t ws_bytes,
                                 void* stream) {
-  if (n < 1 || n > kBnBatchMax || !layers) return fail(JR_ERR_INVALID, "bn_relu_bwd_batch: 1..8 layers");
-  if (!ws || ws_bytes < batch_ws(n, layers)) return fail(JR_ERR_WORKSPACE, "bn_relu_bwd_batch: workspace too small");
-  const int vw = vec_width(dtype);
-  BnBatch bt{};
-  bt.n = n;
-  int blocks[3] = {0, 0, 0};
-  size_t off = 0;
-  for (int l = 0; l < n; ++l) {
-    const jr_bn_bwd_layer& e = layers[l];
-    BnBatchLayer& L = bt.L[l];
-    const void* x = e.x;
-    void* dx = e.dx;
-    const int rc = bwd_setup(dtype, e.nseg, e.segs, x, e.x_c_off, e.x_c_stride, e.m, e.c, e.mean, e.invstd, dx, L.sg);
-    if (rc) return rc;
-    const ChunkGeom g = chunk_geom(e.m, e.c, vw);
-    if (g.nchunks > kFoldMaxP)
-      return fail(JR_ERR_UNSUPPORTED, "bn_relu_bwd_batch: a layer with more than 512 reduce chunks (use jr_bn_relu_bwd_multi)");
-    L.x = x;
-    L.dx = dx;
-    L.mean = e.mean;
-    L.invstd = e.invstd;
-    L.part = reinterpret_cast<double*>(static_cast<char*>(ws) + off);
-    L.k1 = reinterpret_cast<float*>(L.part + (size_t)g.nchunks * 2 * e.c);
-    L.k2 = L.k1 + e.c;
-    L.m = e.m;
-    L.c = e.c;
-    L.xs = e.x_c_stride;
-    L.rpc = g.rows_per_chunk;
-    L.nchunks = g.nchunks;
-    L.b0[0] = blocks[0];
-    L.b0[1] = blocks[1];
-    L.b0[2] = blocks[2];
-    blocks[0] += g.nchunks;
-    blocks[1] += (int)ceil_div(e.c, kFoldCh);
-    blocks[2] += apply_grid(e.m, e.c, vw);
-    off += (ws_need(e.m, e.c) + 255) / 256 * 256;
-  }
+  BnBatch bt;
+  int blocks[3];
+  int rc = bwd_batch_setup(dtype, n, layers, ws, ws_bytes, bt, blocks);
+  if (rc) return rc;
   hipStream_t s = as_stream(stream);
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_bn_reduce_batch<float>, dim3(blocks[0]), dim3(256), 0, s, bt);
-  else
-    hipLaunchKernelGGL(k_bn_reduce_batch<uint16_t>, dim3(blocks[0]), dim3(256), 0, s, bt);
-  int rc = check_launch("bn_bwd batch reduce");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_bn_reduce_batch<T>, dim3(blocks[0]), dim3(256), 0, s, bt);
+  });
+  rc = check_launch("bn_bwd batch reduce");
   if (rc) return rc;
   hipLaunchKernelGGL(k_bn_finalize8_batch, dim3(blocks[1]), dim3(256), 0, s, bt);
   rc = check_launch("bn_bwd batch finalize");
   if (rc) return rc;
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_bn_relu_bwd_apply_batch<float>, dim3(blocks[2]), dim3(256), 0, s, bt);
-  else
-    hipLaunchKernelGGL(k_bn_relu_bwd_apply_batch<uint16_t>, dim3(blocks[2]), dim3(256), 0, s, bt);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_bn_relu_bwd_apply_batch<T>, dim3(blocks[2]), dim3(256), 0, s, bt);
+  });
   return check_launch("bn_bwd batch apply");
 }
 
@@ -1293,11 +1054,6 @@ __global__ void __launch_bounds__(256) k_maxpool_bwd_bn(jr_pool_desc d, const ui
   }
 }
 
-JR_API size_t jr_bn_relu_bwd_maxpool_workspace_size(const jr_pool_desc* d) {
-  if (!d || d->c <= 0) return 0;
-  return (size_t)4096 * 2 * d->c * sizeof(double) + 2 * (size_t)d->c * sizeof(float);
-}
-
 JR_API int jr_bn_relu_bwd_maxpool(int dtype, const jr_pool_desc* d, const uint8_t* argmax, const void* pooled_dy,
                                   void* dy, const void* x, int32_t x_c_stride, const float* mean,
                                   const float* invstd, const float* beta, void* dx, float* dbeta, void* ws,
@@ -1322,27 +1078,23 @@ JR_API int jr_bn_relu_bwd_maxpool_absmax(int dtype, const jr_pool_desc* d, const
   if (!check_slice(dtype, d->y_c_off, d->y_c_stride, c) || !check_slice(dtype, d->x_c_off, d->x_c_stride, c) ||
       !check_slice(dtype, 0, x_c_stride, c))
     return fail(JR_ERR_INVALID, "bn_relu_bwd_maxpool: bad slice");
-  if (!ws || ws_bytes < jr_bn_relu_bwd_maxpool_workspace_size(d))
-    return fail(JR_ERR_WORKSPACE, "bn_relu_bwd_maxpool: workspace too small");
+  if (!ws || ws_bytes < pool_bwd_ws(c)) return fail(JR_ERR_WORKSPACE, "bn_relu_bwd_maxpool: workspace too small");
   hipStream_t s = as_stream(stream);
-  const int64_t cells = (int64_t)d->n * ((d->h + 1) / 2) * ((d->w + 1) / 2) * (c / 4);
-  const int bs = 256 / (c / 4) * (c / 4);        // a whole number of channel-quad rows per block
-  const int grid = (int)std::min<int64_t>(std::max<int64_t>(ceil_div(cells, bs), 1), 4096);
+  const PoolBwdGeom g = pool_bwd_geom(d);
+  const jr_bn_launch_plan p = bn_plan(dtype, m, c);
   double* part = static_cast<double*>(ws);
-  float* k1 = reinterpret_cast<float*>(part + (size_t)grid * 2 * c);
+  float* k1 = reinterpret_cast<float*>(part + (size_t)g.grid * 2 * c);
   float* k2 = k1 + c;
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_maxpool_bwd_bn<float>, dim3(grid), dim3(bs), 0, s, *d, argmax, (const float*)pooled_dy,
-                       (float*)dy, (const float*)x, x_c_stride, mean, invstd, beta, part);
-  else
-    hipLaunchKernelGGL(k_maxpool_bwd_bn<uint16_t>, dim3(grid), dim3(bs), 0, s, *d, argmax,
-                       (const uint16_t*)pooled_dy, (uint16_t*)dy, (const uint16_t*)x, x_c_stride, mean, invstd, beta,
-                       part);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_maxpool_bwd_bn<T>, dim3(g.grid), dim3(g.block), 0, s, *d, argmax, (const T*)pooled_dy, (T*)dy,
+                       (const T*)x, x_c_stride, mean, invstd, beta, part);
+  });
   rc = check_launch("maxpool_bwd + bn reduce");
   if (rc) return rc;
   BnSegs sg{};
   sg.n = 1;
-  sg.dy[0] = static_cast<const char*>(dy) + (size_t)d->x_c_off * (dtype == JR_BF16 ? 2 : 4);
+  sg.dy[0] = at_channel(dtype, dy, d->x_c_off);
   sg.dy_off[0] = 0;
   sg.dy_stride[0] = d->x_c_stride;
   sg.beta[0] = beta;
@@ -1350,8 +1102,8 @@ JR_API int jr_bn_relu_bwd_maxpool_absmax(int dtype, const jr_pool_desc* d, const
   sg.c0[0] = 0;
   sg.c0[1] = c;
   sg.absmax = dx_absmax;
-  hipLaunchKernelGGL((k_bn_finalize<1>), dim3((int)ceil_div(c, 4)), dim3(256), 0, s, part, grid, c, m, 0.f, k1, k2,
-                     sg);
+  hipLaunchKernelGGL((k_bn_finalize<1>), dim3(p.stats_finalize_grid), dim3(256), 0, s, part, g.grid, c, m, 0.f, k1,
+                     k2, sg);
   rc = check_launch("bn_bwd finalize");
   if (rc) return rc;
   return bn_bwd_apply_launch(dtype, sg, x, x_c_stride, m, c, mean, invstd, k1, k2, dx, s);

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "jr_bn_plan.h"   // kStatsLanes, kFoldMaxP: the host-only BN planner sizes with them too
 #include "jr_error.h"
 
 namespace jr {
@@ -65,8 +66,7 @@ __device__ __forceinline__ float bn_pre(float x, float mean, float invstd, float
 // k_stats_finalize8 (jr_conv.hip) and jr_bn_relu_apply_stats (jr_bn.hip, the
 // finalize folded into the BN apply) both call this, so they give bitwise the
 // same statistics.  Every lane of the group returns the result.
-constexpr int kStatsLanes = 8;
-constexpr int kFoldMaxP = 512;   // partials per channel that this combine (and so the fold) takes
+// (kStatsLanes lanes, at most kFoldMaxP partials per channel: jr_bn_plan.h)
 __device__ __forceinline__ void stats_combine8(const float* __restrict__ pm, const float* __restrict__ pq, int P,
                                                int R, int M, float eps, int j, float* mean, float* invstd) {
   const double K = pm[0];
@@ -102,6 +102,28 @@ __device__ __forceinline__ void stats_combine8(const float* __restrict__ pm, con
   const double m2 = fmax(sq - sn * dm * dm, 0.0);
   *mean = (float)(K + dm);
   *invstd = (float)(1.0 / sqrt(m2 / (double)M + (double)eps));
+}
+
+// One launch expression for both path dtypes: calls f with a value of the
+// element type, uint16_t (the bf16 bits) for JR_BF16 and float for every
+// other dtype (JR_F32 and the fp32-tensor conv dtypes) -- in f,
+// `using T = decltype(t);`.  A caller that takes only JR_F32 / JR_BF16
+// rejects the rest before.  The call written first is instantiated first,
+// and a translation unit's kernels sit in its code object in that order:
+// kBf16First keeps the order of the conv sites, which always named bf16 first.
+template <bool kBf16First = false, typename F>
+inline void by_dtype(int dtype, F&& f) {
+  if constexpr (kBf16First) {
+    if (dtype == JR_BF16)
+      f(uint16_t{});
+    else
+      f(float{});
+  } else {
+    if (dtype != JR_BF16)
+      f(float{});
+    else
+      f(uint16_t{});
+  }
 }
 
 // Element load/store of an activation in the path dtype.

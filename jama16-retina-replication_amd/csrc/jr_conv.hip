@@ -1085,12 +1085,11 @@ static int run_gemm(int dtype, ConvArgs a, const Plan& p, void* out, void* ws, s
   if (st) {
     if (p.splits > 1) {
       const dim3 rg(sP, (int)ceil_div(p.N, 1024), members);
-      if (dtype == JR_BF16)
-        hipLaunchKernelGGL((k_splitk_reduce_stats<uint16_t>), rg, dim3(256), 0, s, (const float*)ws, p.splits, a,
-                           static_cast<uint16_t*>(out), sR);
-      else
-        hipLaunchKernelGGL((k_splitk_reduce_stats<float>), rg, dim3(256), 0, s, (const float*)ws, p.splits, a,
-                           static_cast<float*>(out), sR);
+      by_dtype<true>(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_splitk_reduce_stats<T>), rg, dim3(256), 0, s, (const float*)ws, p.splits, a,
+                           static_cast<T*>(out), sR);
+      });
       rc = check_launch("conv split-k reduce + stats");
       if (rc) return rc;
     }
@@ -1102,12 +1101,12 @@ static int run_gemm(int dtype, ConvArgs a, const Plan& p, void* out, void* ws, s
   const int G = reduce_lanes(p);                       // z-lanes per column
   const long long cols = 256 / G;
   const int blocks = (int)std::min<long long>(ceil_div(total, cols), 8192);
-  if (dtype == JR_BF16 && OP != OP_WGRAD)   // bf16 activations / activation grads; dW stays fp32
-    hipLaunchKernelGGL((k_splitk_reduce<OP, uint16_t>), dim3(blocks), dim3(256), 0, s, (const float*)ws, p.splits,
-                       G, a, static_cast<uint16_t*>(out));
-  else
-    hipLaunchKernelGGL((k_splitk_reduce<OP, float>), dim3(blocks), dim3(256), 0, s, (const float*)ws, p.splits, G,
-                       a, static_cast<float*>(out));
+  // bf16 activations / activation grads; dW stays fp32
+  by_dtype<true>(OP != OP_WGRAD ? dtype : JR_F32, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_splitk_reduce<OP, T>), dim3(blocks), dim3(256), 0, s, (const float*)ws, p.splits, G, a,
+                       static_cast<T*>(out));
+  });
   return check_launch("conv split-k reduce");
 }
 

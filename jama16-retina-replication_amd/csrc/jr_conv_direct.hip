@@ -185,14 +185,11 @@ void launch_conv1_direct(const jr_conv_desc* d, int dtype, const void* x, const 
   conv1_direct_partials(d, &P, &R);
   const dim3 grid((unsigned)P, (unsigned)members);
   const int c8 = (d->c_in + 7) / 8 * 8;
-  if (dtype == JR_BF16)
-    hipLaunchKernelGGL((k_conv1_direct<uint16_t, uint16_t>), grid, dim3(256), 0, s, (const uint16_t*)x, d->x_c_stride,
-                       (const uint16_t*)w, (uint16_t*)y, d->n, d->h, d->w, d->ho, d->wo, d->c_in, c8, stats, P, x_mb,
-                       w_mb, y_mb, s_mb);
-  else
-    hipLaunchKernelGGL((k_conv1_direct<float, float>), grid, dim3(256), 0, s, (const float*)x, d->x_c_stride,
-                       (const float*)w, (float*)y, d->n, d->h, d->w, d->ho, d->wo, d->c_in, c8, stats, P, x_mb, w_mb,
-                       y_mb, s_mb);
+  by_dtype<true>(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_conv1_direct<T, T>), grid, dim3(256), 0, s, (const T*)x, d->x_c_stride, (const T*)w, (T*)y,
+                       d->n, d->h, d->w, d->ho, d->wo, d->c_in, c8, stats, P, x_mb, w_mb, y_mb, s_mb);
+  });
 }
 
 }  // namespace jr

@@ -427,13 +427,11 @@ JR_API int jr_cast_bf16_to_f32(const void* src, float* dst, int64_t n, void* str
 JR_API int jr_u8_to_f32_scaled(const uint8_t* src, void* dst, int dtype, int64_t n, void* stream) {
   if (!src || !dst || n < 0) return fail(JR_ERR_INVALID, "u8_scale: bad arguments");
   if (n == 0) return JR_OK;
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_u8_scale<float>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), src, (float*)dst, n);
-  else if (dtype == JR_BF16)
-    hipLaunchKernelGGL(k_u8_scale<uint16_t>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), src,
-                       (uint16_t*)dst, n);
-  else
-    return fail(JR_ERR_INVALID, "u8_scale: bad dtype");
+  if (dtype != JR_F32 && dtype != JR_BF16) return fail(JR_ERR_INVALID, "u8_scale: bad dtype");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_u8_scale<T>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), src, (T*)dst, n);
+  });
   return check_launch("u8_scale");
 }
 
@@ -442,14 +440,12 @@ JR_API int jr_image_u8_to_nhwc(const uint8_t* src, void* dst, int dtype, int64_t
   if (!src || !dst || pixels < 0 || c <= 0 || dst_stride < c) return fail(JR_ERR_INVALID, "image_u8: bad arguments");
   if (pixels == 0) return JR_OK;
   const int64_t n = pixels * dst_stride;
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_image_u8<float>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), src, (float*)dst,
-                       pixels, c, dst_stride);
-  else if (dtype == JR_BF16)
-    hipLaunchKernelGGL(k_image_u8<uint16_t>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), src,
-                       (uint16_t*)dst, pixels, c, dst_stride);
-  else
-    return fail(JR_ERR_INVALID, "image_u8: bad dtype");
+  if (dtype != JR_F32 && dtype != JR_BF16) return fail(JR_ERR_INVALID, "image_u8: bad dtype");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_image_u8<T>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), src, (T*)dst, pixels, c,
+                       dst_stride);
+  });
   return check_launch("image_u8");
 }
 

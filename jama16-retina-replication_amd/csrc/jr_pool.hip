@@ -350,12 +350,10 @@ JR_API int jr_maxpool3x3s2_fwd(const jr_pool_desc* d, int dtype, const void* x, 
   if (rc) return rc;
   if (!x || !y) return fail(JR_ERR_INVALID, "maxpool_fwd: null pointer");
   const int g = grid_for((int64_t)d->n * d->ho * d->wo * (d->c / 4));
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_maxpool_fwd<float>, dim3(g), dim3(256), 0, as_stream(stream), *d, (const float*)x,
-                       (float*)y, argmax);
-  else
-    hipLaunchKernelGGL(k_maxpool_fwd<uint16_t>, dim3(g), dim3(256), 0, as_stream(stream), *d,
-                       (const uint16_t*)x, (uint16_t*)y, argmax);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_maxpool_fwd<T>, dim3(g), dim3(256), 0, as_stream(stream), *d, (const T*)x, (T*)y, argmax);
+  });
   return check_launch("maxpool_fwd");
 }
 
@@ -369,14 +367,12 @@ JR_API int jr_bn_relu_maxpool3x3s2_fwd_grouped(const jr_pool_desc* d, int dtype,
   if (images_per_member < 1 || d->n % images_per_member != 0 || stats_member_stride < 0 || beta_member_stride < 0)
     return fail(JR_ERR_INVALID, "bn_relu_maxpool_fwd: images_per_member must divide n; strides >= 0");
   const int g = grid_for((int64_t)d->n * d->ho * d->wo * (d->c / 4));
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_bn_relu_maxpool_fwd<float>, dim3(g), dim3(256), 0, as_stream(stream), *d,
-                       (const float*)raw, mean, invstd, beta, (float*)y, argmax, images_per_member,
-                       (long long)stats_member_stride, (long long)beta_member_stride);
-  else
-    hipLaunchKernelGGL(k_bn_relu_maxpool_fwd<uint16_t>, dim3(g), dim3(256), 0, as_stream(stream), *d,
-                       (const uint16_t*)raw, mean, invstd, beta, (uint16_t*)y, argmax, images_per_member,
-                       (long long)stats_member_stride, (long long)beta_member_stride);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_bn_relu_maxpool_fwd<T>, dim3(g), dim3(256), 0, as_stream(stream), *d, (const T*)raw, mean,
+                       invstd, beta, (T*)y, argmax, images_per_member, (long long)stats_member_stride,
+                       (long long)beta_member_stride);
+  });
   return check_launch("bn_relu_maxpool_fwd");
 }
 
@@ -394,12 +390,11 @@ JR_API int jr_maxpool3x3s2_bwd(const jr_pool_desc* d, int dtype, const uint8_t* 
   if (rc) return rc;
   if (!argmax || !dy || !dx) return fail(JR_ERR_INVALID, "maxpool_bwd: null pointer");
   const int g = grid_for((int64_t)d->n * ((d->h + 1) / 2) * ((d->w + 1) / 2) * (d->c / 4));
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_maxpool_bwd<float>, dim3(g), dim3(256), 0, as_stream(stream), *d, argmax,
-                       (const float*)dy, (float*)dx, accumulate);
-  else
-    hipLaunchKernelGGL(k_maxpool_bwd<uint16_t>, dim3(g), dim3(256), 0, as_stream(stream), *d, argmax,
-                       (const uint16_t*)dy, (uint16_t*)dx, accumulate);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_maxpool_bwd<T>, dim3(g), dim3(256), 0, as_stream(stream), *d, argmax, (const T*)dy, (T*)dx,
+                       accumulate);
+  });
   return check_launch("maxpool_bwd");
 }
 
@@ -408,12 +403,11 @@ JR_API int jr_avgpool3x3s1_fwd(const jr_pool_desc* d, int dtype, const void* x, 
   if (rc) return rc;
   if (!x || !y) return fail(JR_ERR_INVALID, "avgpool_fwd: null pointer");
   const int g = grid_for((int64_t)d->n * ceil_div(d->h, kStrip) * d->w * (d->c / 4));
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL((k_avgpool_box<float, false>), dim3(g), dim3(256), 0, as_stream(stream), *d, (const float*)x,
-                       (float*)y, 0);
-  else
-    hipLaunchKernelGGL((k_avgpool_box<uint16_t, false>), dim3(g), dim3(256), 0, as_stream(stream), *d,
-                       (const uint16_t*)x, (uint16_t*)y, 0);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_avgpool_box<T, false>), dim3(g), dim3(256), 0, as_stream(stream), *d, (const T*)x, (T*)y,
+                       0);
+  });
   return check_launch("avgpool_fwd");
 }
 
@@ -423,25 +417,22 @@ JR_API int jr_avgpool3x3s1_bwd(const jr_pool_desc* d, int dtype, const void* dy,
   if (rc) return rc;
   if (!dy || !dx) return fail(JR_ERR_INVALID, "avgpool_bwd: null pointer");
   const int g = grid_for((int64_t)d->n * ceil_div(d->h, kStrip) * d->w * (d->c / 4));
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL((k_avgpool_box<float, true>), dim3(g), dim3(256), 0, as_stream(stream), *d, (const float*)dy,
-                       (float*)dx, accumulate);
-  else
-    hipLaunchKernelGGL((k_avgpool_box<uint16_t, true>), dim3(g), dim3(256), 0, as_stream(stream), *d,
-                       (const uint16_t*)dy, (uint16_t*)dx, accumulate);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_avgpool_box<T, true>), dim3(g), dim3(256), 0, as_stream(stream), *d, (const T*)dy,
+                       (T*)dx, accumulate);
+  });
   return check_launch("avgpool_bwd");
 }
 
 JR_API int jr_gap_fwd(int dtype, const void* x, int32_t n, int32_t hw, int32_t c, float* y, void* stream) {
   if (!x || !y || n <= 0 || hw <= 0 || c <= 0 || c % 4) return fail(JR_ERR_INVALID, "gap_fwd: bad arguments");
   const int g = (int)ceil_div((int64_t)n * (c / 4), 256);
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_gap_fwd<float>, dim3(g), dim3(256), 0, as_stream(stream), (const float*)x, n, hw, c, y);
-  else if (dtype == JR_BF16)
-    hipLaunchKernelGGL(k_gap_fwd<uint16_t>, dim3(g), dim3(256), 0, as_stream(stream), (const uint16_t*)x, n, hw,
-                       c, y);
-  else
-    return fail(JR_ERR_INVALID, "gap_fwd: bad dtype");
+  if (dtype != JR_F32 && dtype != JR_BF16) return fail(JR_ERR_INVALID, "gap_fwd: bad dtype");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_gap_fwd<T>, dim3(g), dim3(256), 0, as_stream(stream), (const T*)x, n, hw, c, y);
+  });
   return check_launch("gap_fwd");
 }
 
@@ -449,12 +440,10 @@ JR_API int jr_gap_bwd(int dtype, const float* dy, int32_t n, int32_t hw, int32_t
   if (!dy || !dx || n <= 0 || hw <= 0 || c <= 0 || c % 4) return fail(JR_ERR_INVALID, "gap_bwd: bad arguments");
   if ((int64_t)n * hw * (c / 4) >= (1LL << 30)) return fail(JR_ERR_UNSUPPORTED, "gap_bwd: more than 2^30 channel quads");
   const int g = grid_for((int64_t)n * hw * (c / 4));
-  if (dtype == JR_F32)
-    hipLaunchKernelGGL(k_gap_bwd<float>, dim3(g), dim3(256), 0, as_stream(stream), dy, n, hw, c, (float*)dx);
-  else if (dtype == JR_BF16)
-    hipLaunchKernelGGL(k_gap_bwd<uint16_t>, dim3(g), dim3(256), 0, as_stream(stream), dy, n, hw, c,
-                       (uint16_t*)dx);
-  else
-    return fail(JR_ERR_INVALID, "gap_bwd: bad dtype");
+  if (dtype != JR_F32 && dtype != JR_BF16) return fail(JR_ERR_INVALID, "gap_bwd: bad dtype");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_gap_bwd<T>, dim3(g), dim3(256), 0, as_stream(stream), dy, n, hw, c, (T*)dx);
+  });
   return check_launch("gap_bwd");
 }

@@ -85,6 +85,14 @@ class BnPartials(Structure):
                 ("single_stage", c_int32)]
 
 
+class BnLaunchPlan(Structure):
+    """include/jr.h jr_bn_launch_plan: what the BN launches over (dtype, m, c) use."""
+    _fields_ = [(n, c_int32) for n in (
+        "vec_width", "rows_per_chunk", "nchunks", "single_stage", "reduce_grid", "finalize_grid",
+        "stats_finalize_grid", "apply_grid", "fold_rows", "fold_grid_x", "fold_grid_y", "reserved")] + [
+        ("k1_offset", c_int64), ("workspace_size", c_int64)]
+
+
 class AugmentParam(Structure):
     """include/jr.h jr_augment_param: one image's augmentation (jr.augment builds the tables)."""
     _fields_ = [("hue_delta", c_float), ("sat_factor", c_float), ("contrast_factor", c_float),
@@ -149,6 +157,7 @@ _SIGS = {
     "jr_comm_world": (c_int, [c_void_p]),
     "jr_comm_destroy": (c_int, [c_void_p]),
     "jr_bn_workspace_size": (c_size_t, [c_int64, c_int32]),
+    "jr_bn_plan": (c_int, [c_int, c_int64, c_int32, POINTER(BnLaunchPlan)]),
     "jr_bn_relu_bwd_batch_workspace_size": (c_size_t, [c_int32, c_void_p]),
     "jr_bn_relu_apply_multi": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32,
                                        c_void_p, c_void_p, c_void_p]),
@@ -310,6 +319,23 @@ def call(name: str, *args) -> int:
                                             "jr_conv_weights_bf16_tiles"):
         check(name, rc)
     return rc
+
+
+def bn_plan(dtype: int, m: int, c: int):
+    """jr_bn_plan: the BnLaunchPlan of the BN launches over m rows of c
+    channels (host only, no device), or None where one launch set does not
+    take c channels (more than 256 vectors per row: JR_ERR_UNSUPPORTED)."""
+    p = BnLaunchPlan()
+    rc = load().jr_bn_plan(dtype, m, c, ctypes.byref(p))
+    if rc == JR_ERR_UNSUPPORTED:
+        return None
+    check("jr_bn_plan", rc)
+    return p
+
+
+def bn_one_launch(dtype: int, c: int) -> bool:
+    """One BN launch set covers c channels of this dtype (any row count)."""
+    return bn_plan(dtype, 1, c) is not None
 
 
 _inited = set()

@@ -36,7 +36,7 @@ from . import _ffi
 from .inception import BN_EPS, Graph, PoolNode, build_inception_v3
 from .init import init_params
 from .lanes import Build, Call, Lanes, node_lanes, schedule
-from .plan import ConvUnit, build_plan
+from .plan import ConvUnit, bn_batch_groups, build_plan
 
 DTYPES = {"f32": _ffi.JR_F32, "bf16": _ffi.JR_BF16}
 
@@ -432,7 +432,8 @@ class Engine(Replica):
             self.dfeat = self._t(B * feat_c)
             # the batched block-output BN backwards' raw gradients live in two
             # alternating sets of per-layer buffers
-            self.bn_batch = self._bn_batch_groups(B) if self.bn_batch_on else []
+            self.bn_batch = (bn_batch_groups(g, self.plan, B, self._vw, self.fused_bufs)
+                             if self.bn_batch_on else [])
             slots = max((len(grp) for grp in self.bn_batch), default=0)
             self.drawb = [[self._t(max(B * grp[k].ho * grp[k].wo * grp[k].cout
                                        for grp in self.bn_batch if k < len(grp)), at) for k in range(slots)]
@@ -463,38 +464,6 @@ class Engine(Replica):
 
     def _dmax(self, u: ConvUnit) -> int:
         return self.absmax.data_ptr() + 4 * 64 * (len(self.cunits) + self._arow[u.first.idx])
-
-    def _bn_batch_groups(self, B: int):
-        """Conv launches whose BN backwards become due together: every member
-        writes a slice of one block buffer (several producing launches: the
-        branch-final layers of an Inception block), one launch set per launch
-        (c / vector width <= 256), at most 512 reduce chunks (jr_bn.hip
-        chunk_geom), not the stem's pooled layers; blocks with two or more."""
-        g, vw = self.g, self._vw
-        producers: Dict[int, set] = {}
-        for u in self.cunits:
-            for m in u.members:
-                producers.setdefault(m.y.buf, set()).add(u.first.idx)
-        for n in g.nodes:
-            if n.kind != "conv":
-                producers.setdefault(n.y.buf, set()).add(("pool", id(n)))
-        fused = set(self.pool_fused.values())
-        groups: Dict[int, list] = {}
-        for u in self.cunits:
-            bufs = {m.y.buf for m in u.members}
-            if len(bufs) != 1:
-                continue
-            buf = next(iter(bufs))
-            M, c = B * u.ho * u.wo, u.cout
-            tpr = c // vw
-            rpp = max(1, 256 // tpr)
-            step = rpp * 16
-            rpc = -(-max(-(-M // 1024), step) // step) * step
-            if (len(producers[buf]) < 2 or buf in fused or buf == g.output_buf or tpr > 256
-                    or -(-M // rpc) > 512):
-                continue
-            groups.setdefault(buf, []).append(u)
-        return [grp for grp in groups.values() if len(grp) >= 2]
 
     def _alloc_planes(self) -> None:
         """JR_F32_X8P operand planes (jr.h): the exact bf16 h/m/l split of
@@ -706,7 +675,7 @@ class Engine(Replica):
         the launch's channels fit one 256-thread row (jr_bn: <= 256 vectors of
         4 fp32 / 8 bf16), else one set per member.  [(member, col_off), ...]"""
         groups = [list(zip(u.members, u.col_off))]
-        if u.cout // self._vw > 256:
+        if not _ffi.bn_one_launch(self.dt, u.cout):
             groups = [[mc] for mc in groups[0]]
         return groups
 
@@ -830,7 +799,7 @@ class Engine(Replica):
         b.add(b.fwd, L.jr_conv2d_fwd_bn_stats,
               (ctypes.byref(d), self.cdt, self._AX(u.x), self._wf(u), raw, BN_EPS, mean, invstd, ws, b.wsb, s),
               "conv_fwd", ln, reads, [("r", uid), ("ws", ln)])
-        if self.apply_multi and len(u.members) > 1 and u.cout // self._vw <= 256 and unfused:
+        if self.apply_multi and len(u.members) > 1 and _ffi.bn_one_launch(self.dt, u.cout) and unfused:
             # every member's BN + ReLU in one launch (jr_bn_relu_apply_multi)
             segs = (_ffi.BnApplySeg * len(u.members))(*[
                 _ffi.BnApplySeg(self._A(m.y.buf), m.y.c_off, g.bufs[m.y.buf].c, m.cout, self._beta(m))

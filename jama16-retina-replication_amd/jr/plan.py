@@ -30,6 +30,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
+from . import _ffi
 from .inception import ConvNode, Graph
 from .init import ALIGN, param_layout
 
@@ -172,3 +173,32 @@ def build_plan(g: Graph, fuse_siblings: bool = True) -> Plan:
         if n is not None and name.endswith("/kernel"):
             unit_of[n.idx].koff = o
     return Plan(units, unit_of, layout, off, poff, kview)
+
+
+def bn_batch_groups(g: Graph, plan: Plan, batch: int, vec_width: int, fused_bufs) -> List[List[ConvUnit]]:
+    """Conv launches whose BN backwards become due together: every member
+    writes a slice of one block buffer (several producing launches: the
+    branch-final layers of an Inception block), one launch set per launch
+    and at most 512 reduce chunks (jr_bn_plan: single_stage), not the stem's
+    pooled layers (fused_bufs); blocks with two or more.  vec_width: 4 (fp32)
+    or 8 (bf16) channels per 16-byte vector."""
+    dtype = _ffi.JR_BF16 if vec_width == 8 else _ffi.JR_F32
+    producers: Dict[int, set] = {}
+    for u in plan.units:
+        for m in u.members:
+            producers.setdefault(m.y.buf, set()).add(u.first.idx)
+    for n in g.nodes:
+        if n.kind != "conv":
+            producers.setdefault(n.y.buf, set()).add(("pool", id(n)))
+    fused = set(fused_bufs)
+    groups: Dict[int, list] = {}
+    for u in plan.units:
+        bufs = {m.y.buf for m in u.members}
+        if len(bufs) != 1:
+            continue
+        buf = next(iter(bufs))
+        p = _ffi.bn_plan(dtype, batch * u.ho * u.wo, u.cout)    # None: more than one launch set
+        if len(producers[buf]) < 2 or buf in fused or buf == g.output_buf or p is None or not p.single_stage:
+            continue
+        groups.setdefault(buf, []).append(u)
+    return [grp for grp in groups.values() if len(grp) >= 2]
