@@ -42,17 +42,13 @@
 // deferred filter-gradient reduce kernels.  What to launch -- the config-id
 // space, tile and split-K choice, workspace sizes, descriptor validation, the
 // tune cache -- is decided by the host-only planner (jr_conv_plan.h).
-#include "jr_conv_impl.h"
+#include "jr_conv_loop.h"
 
 #include <algorithm>
 #include <type_traits>
 #include <vector>
 
 namespace jr {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t pk_bf16(float a, float b) {   // v_cvt_pk_bf16_f32 (RNE), a in the low half
   const bf16x2 r = {(__bf16)a, (__bf16)b};
@@ -132,8 +128,6 @@ struct SplitFrag {
 // (fp16 subnormals keep the rest down to 2^-24).  Six f16 MFMAs per
 // product (hh hm mh mm hl lh); dropped: ml + lm (< 2^-32 |a b|) and ll, the
 // x8 class.  acc is scaled back by 2^-(ka+kb) (exact) after the K loop.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ uint32_t pkrtz_f16(float a, float b) {   // v_cvt_pkrtz_f16_f32, a in the low half
   return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
@@ -220,20 +214,13 @@ struct SplitFrag16 {
 template <int OP, int BM, int BN, int WGM, int BK, int NBUF, bool UT, bool X8, int DBG = 0, bool SK = false,
           bool H6 = false>
 __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
-  constexpr int WGN = 4 / WGM;
-  constexpr int WM = BM / WGM, WN = BN / WGN;
-  constexpr int TM = WM / 32, TN = WN / 32;
-  static_assert(WM % 32 == 0 && WN % 32 == 0, "wave tile must be a multiple of 32x32");
-  constexpr int QPR = BK / 4;                 // 16 B quads per KC row
-  constexpr int RPI = 64 / QPR;               // KC rows per DMA instruction
-  constexpr int SWZ = 16 / QPR;               // rows sharing one swizzle value
+  using G = TileGeom<BM, BN, WGM, 4, BK, 4>;    // 16 B pieces of 4 floats
+  constexpr int WGN = G::WGN, WM = G::WM, WN = G::WN, TM = G::TM, TN = G::TN;
+  constexpr int QPR = G::QPR, RPI = G::RPI, SWZ = G::SWZ, ASZ = G::ASZ, BSZ = G::BSZ;
+  constexpr int A_INSTR = G::A_INSTR, B_INSTR = G::B_INSTR, A_PW = G::A_PW, B_PW = G::B_PW;
   constexpr int HALF = BK / 2;                // k per lane half
   constexpr bool A_KC = (OP != OP_WGRAD);
   constexpr bool B_KC = (OP == OP_DGRAD);
-  constexpr int ASZ = BM * BK, BSZ = BN * BK;  // floats per image
-  constexpr int A_INSTR = ASZ / 256, B_INSTR = BSZ / 256;
-  constexpr int A_PW = (A_INSTR + 3) / 4, B_PW = (B_INSTR + 3) / 4;  // per wave
-  static_assert(ASZ % 256 == 0 && BSZ % 256 == 0, "tile must be whole DMA instructions");
   constexpr int SMEM = NBUF * (ASZ + BSZ) > 4 * stage_floats<WN>() ? NBUF * (ASZ + BSZ) : 4 * stage_floats<WN>();
   __shared__ __attribute__((aligned(1024))) float smem[SMEM];
   JR_ST(Stamps stamp; stamp.start();)
@@ -624,78 +611,30 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
           ++piece;
         }
       };
-      auto mma = [&](int i, int j, const bf16x8& x, const bf16x8& y) {
-        if constexpr (DBG == 1) {   // diagnostic: no MFMA (keeps the operands live)
+      // one MFMA of the fragments' element type (X6H: f16, X8: bf16)
+      auto mma = [&](int i, int j, const auto& x, const auto& y) {
+        if constexpr (H6) {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, acc[i][j], 0, 0, 0);
+        } else if constexpr (DBG == 1) {   // diagnostic: no MFMA (keeps the operands live)
           const f32x4 t = __builtin_bit_cast(f32x4, x) + __builtin_bit_cast(f32x4, y);
           acc[i][j][0] += t[0]; acc[i][j][1] += t[1]; acc[i][j][2] += t[2]; acc[i][j][3] += t[3];
         } else {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc[i][j], 0, 0, 0);
         }
       };
-      if constexpr (H6) {
-        auto mmh = [&](int i, int j, const f16x8& x, const f16x8& y) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, acc[i][j], 0, 0, 0);
-        };
-#pragma unroll
-        for (int g8 = 0; g8 < G8; ++g8) {
-          SplitFrag16 sa[TM], sb[TN];
-#pragma unroll
-          for (int i = 0; i < TM; ++i) sa[i].init(&af[i][8 * g8], h_sa);
-#pragma unroll
-          for (int j = 0; j < TN; ++j) sb[j].init(&bfr[j][8 * g8], h_sb);
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) mmh(i, j, sa[i].h(), sb[j].h());
-#pragma unroll
-          for (int i = 0; i < TM; ++i) sa[i].stage2(h_one);
-          next_piece();
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) mmh(i, j, sa[i].m(), sb[j].h());
-#pragma unroll
-          for (int j = 0; j < TN; ++j) sb[j].stage2(h_one);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-              mmh(i, j, sa[i].h(), sb[j].m());
-              mmh(i, j, sa[i].m(), sb[j].m());
-            }
-#pragma unroll
-          for (int i = 0; i < TM; ++i) sa[i].stage3(h_one);
-          next_piece();
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) mmh(i, j, sa[i].l(), sb[j].h());
-#pragma unroll
-          for (int j = 0; j < TN; ++j) sb[j].stage3(h_one);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) mmh(i, j, sa[i].h(), sb[j].l());
-          next_piece();
-        }
-        if constexpr (DO_ISSUE && DBG != 2) {
-#pragma unroll
-          for (int d = 3 * G8; d < NPIECE; ++d) issue_piece(kt + NBUF - 1, d, wA, wB);
-          advance();
-        }
-        return;
-      }
+      // the fragment type and what its init / stage calls take: X6H the
+      // operand scales and the hidden 1.0, X8 the DBG 4 skip flag
+      using Frag = std::conditional_t<H6, SplitFrag16, SplitFrag>;
+      const auto in_a = [&] { if constexpr (H6) return h_sa; else return DBG == 4; }();
+      const auto in_b = [&] { if constexpr (H6) return h_sb; else return DBG == 4; }();
+      const auto st = [&] { if constexpr (H6) return h_one; else return DBG == 4; }();
 #pragma unroll
       for (int g8 = 0; g8 < G8; ++g8) {
-        SplitFrag sa[TM], sb[TN];
+        Frag sa[TM], sb[TN];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) sa[i].init(&af[i][8 * g8], DBG == 4);
+        for (int i = 0; i < TM; ++i) sa[i].init(&af[i][8 * g8], in_a);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) sb[j].init(&bfr[j][8 * g8], DBG == 4);
+        for (int j = 0; j < TN; ++j) sb[j].init(&bfr[j][8 * g8], in_b);
         // (sched_barrier closes each region even when this wave has no DMA
         // piece left to issue)
 #pragma unroll
@@ -703,7 +642,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
 #pragma unroll
           for (int j = 0; j < TN; ++j) mma(i, j, sa[i].h(), sb[j].h());
 #pragma unroll
-        for (int i = 0; i < TM; ++i) sa[i].stage2(DBG == 4);
+        for (int i = 0; i < TM; ++i) sa[i].stage2(st);
         next_piece();
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -711,7 +650,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
 #pragma unroll
           for (int j = 0; j < TN; ++j) mma(i, j, sa[i].m(), sb[j].h());
 #pragma unroll
-        for (int j = 0; j < TN; ++j) sb[j].stage2(DBG == 4);
+        for (int j = 0; j < TN; ++j) sb[j].stage2(st);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -721,7 +660,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
             mma(i, j, sa[i].m(), sb[j].m());
           }
 #pragma unroll
-        for (int i = 0; i < TM; ++i) sa[i].stage3(DBG == 4);
+        for (int i = 0; i < TM; ++i) sa[i].stage3(st);
         next_piece();
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -729,14 +668,14 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
 #pragma unroll
           for (int j = 0; j < TN; ++j) mma(i, j, sa[i].l(), sb[j].h());
 #pragma unroll
-        for (int j = 0; j < TN; ++j) sb[j].stage3(DBG == 4);
+        for (int j = 0; j < TN; ++j) sb[j].stage3(st);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int j = 0; j < TN; ++j) {
             mma(i, j, sa[i].h(), sb[j].l());
-            if constexpr (kSplitTerms == 8) {
+            if constexpr (!H6 && kSplitTerms == 8) {   // X6H drops ml + lm (SplitFrag16)
               mma(i, j, sa[i].m(), sb[j].l());
               mma(i, j, sa[i].l(), sb[j].m());
             }

@@ -24,13 +24,9 @@
 // accumulate hh mh hm mm lh hl ml lm (A plane x B plane) in fp32 — the
 // products and per-accumulator order of the JR_F32_X8 kernel (jr_conv.hip),
 // without its in-register split VALU.  Outputs are fp32 as for JR_F32.
-#include "jr_conv_impl.h"
+#include "jr_conv_loop.h"
 
 namespace jr {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 // ds_read_b64_tr_b16: lane 4q+p of each 16-lane group passes the address of
 // row q, columns 4p..4p+3 of the group's 4x16 block; lane i gets column i.
@@ -50,19 +46,12 @@ template <int OP, int BM, int BN, int WGM, int BK, int NBUF, int AM, int NP, int
 __global__ void __launch_bounds__(NW * 64) k_conv_bf16(ConvArgs g) {
   static_assert(NP == 1 || NP == 3, "one bf16 plane, or the h / m / l planes of X8P");
   static_assert(NW == 4 || NW == 8, "4 or 8 waves per block");
-  constexpr int WGN = NW / WGM;
-  constexpr int WM = BM / WGM, WN = BN / WGN;
-  constexpr int TM = WM / 32, TN = WN / 32;
-  static_assert(WM % 32 == 0 && WN % 32 == 0, "wave tile must be a multiple of 32x32");
-  constexpr int QPR = BK / 8;                 // 16 B quads per KC row
-  constexpr int RPI = 64 / QPR;               // KC rows per DMA instruction
-  constexpr int SWZ = 16 / QPR;               // rows sharing one swizzle value
+  using G = TileGeom<BM, BN, WGM, NW, BK, 8>;   // 16 B pieces of 8 bf16
+  constexpr int WGN = G::WGN, WM = G::WM, WN = G::WN, TM = G::TM, TN = G::TN;
+  constexpr int QPR = G::QPR, RPI = G::RPI, SWZ = G::SWZ, ASZ = G::ASZ, BSZ = G::BSZ;
+  constexpr int A_INSTR = G::A_INSTR, B_INSTR = G::B_INSTR, A_PW = G::A_PW, B_PW = G::B_PW;
   constexpr int KSTEPS = BK / 16;             // MFMA k-steps per tile
   constexpr bool MC = (OP == OP_WGRAD);       // both operands MC (else both KC)
-  constexpr int ASZ = BM * BK, BSZ = BN * BK;  // bf16 elements per image
-  constexpr int A_INSTR = ASZ / 512, B_INSTR = BSZ / 512;
-  constexpr int A_PW = (A_INSTR + NW - 1) / NW, B_PW = (B_INSTR + NW - 1) / NW;  // per wave
-  static_assert(ASZ % 512 == 0 && BSZ % 512 == 0, "tile must be whole DMA instructions");
   static_assert(BK % 16 == 0 && QPR <= 8, "BK must be 16..64");
   constexpr int STAGE = NP * (ASZ + BSZ);    // one ring slot: NP A planes, then NP B planes
   constexpr int SMEM = NBUF * STAGE > 2 * NW * stage_floats<WN>() ? NBUF * STAGE : 2 * NW * stage_floats<WN>();

@@ -21,20 +21,16 @@
 // statistics, staged row-vector stores) and split-K slabs as the GEMM kernel.
 // Selected per layer as extra bf16 tile configurations (kHaloBf16: tile ids
 // kNumCfgsBf16...), so autotuning and the pinned tables decide where it runs.
-#include "jr_conv_impl.h"
+#include "jr_conv_loop.h"
 
 namespace jr {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 template <int KH, int KW, int BM, int BN, int WGM, int NBUF, int SLOTS>
 __global__ void __launch_bounds__(256) k_conv_halo(ConvArgs g) {
   constexpr int BK = 32;                       // channels per chunk: 4 x 16 B pieces per slot
   constexpr int TAPS = KH * KW;
-  constexpr int WGN = 4 / WGM;
-  constexpr int WM = BM / WGM, WN = BN / WGN;
-  constexpr int TM = WM / 32, TN = WN / 32;
-  static_assert(WM % 32 == 0 && WN % 32 == 0, "wave tile must be a multiple of 32x32");
+  using G = WaveTile<BM, BN, WGM, 4>;
+  constexpr int WGN = G::WGN, WM = G::WM, WN = G::WN, TM = G::TM, TN = G::TN;
   static_assert(SLOTS % 16 == 0 && (TAPS * BN) % 16 == 0, "images must be whole DMA instructions");
   constexpr int A_INSTR = SLOTS / 16, B_INSTR = TAPS * BN / 16;
   constexpr int A_PW = (A_INSTR + 3) / 4, B_PW = (B_INSTR + 3) / 4;

@@ -82,7 +82,8 @@ def _weights(ffi, L, wt):
     return hwio, wtt
 
 
-def _run_all(ffi, L, case, seed, cfg=None, extra_ws=0):
+def _run_all(ffi, L, case, seed, cfg=None, extra_ws=0, raw=None):
+    """raw: a dict that receives the output tensors themselves (test_gpu_conv_bits.py)."""
     n, h, w, cin, cout, kh, kw, s, pad = case
     rng = np.random.default_rng(seed)
     x = bf16_round(rng.standard_normal((n, h, w, cin)))
@@ -109,6 +110,8 @@ def _run_all(ffi, L, case, seed, cfg=None, extra_ws=0):
     ffi.check("fwd", L.jr_conv2d_fwd(ctypes.byref(d), 1, X.data_ptr(), wtt.data_ptr(), Y.data_ptr(),
                                      ws.data_ptr(), wsb, None))
     out["fwd"] = relerr(host(Y).reshape(ref.shape), ref)
+    if raw is not None:
+        raw["fwd"] = Y
     dy = bf16_round(rng.standard_normal(ref.shape))
     DY = dev_bf16(dy)
     if cin % 8 == 0:
@@ -117,14 +120,20 @@ def _run_all(ffi, L, case, seed, cfg=None, extra_ws=0):
         ffi.check("dgrad", L.jr_conv2d_bwd_data(ctypes.byref(d), 1, DY.data_ptr(), hwio.data_ptr(), DX.data_ptr(),
                                                 0, ws.data_ptr(), wsb, None))
         out["dgrad"] = relerr(host(DX).reshape(x.shape), ref_dx)
+        if raw is not None:
+            raw["dgrad"] = DX.clone()
         ffi.check("dgrad acc", L.jr_conv2d_bwd_data(ctypes.byref(d), 1, DY.data_ptr(), hwio.data_ptr(),
                                                     DX.data_ptr(), 1, ws.data_ptr(), wsb, None))
         out["dgrad_acc"] = relerr(host(DX).reshape(x.shape), 2 * ref_dx)
+        if raw is not None:
+            raw["dgrad_acc"] = DX
     ref_dw = R.conv2d_bwd_filter(x, dy, wt.shape, s, pad)
     DW = torch.zeros(wt.size, device="cuda")
     ffi.check("wgrad", L.jr_conv2d_bwd_filter(ctypes.byref(d), 1, X.data_ptr(), DY.data_ptr(), DW.data_ptr(),
                                               ws.data_ptr(), wsb, None))
     out["wgrad"] = relerr(host(DW).reshape(wt.shape), ref_dw)
+    if raw is not None:
+        raw["wgrad"] = DW
     return out
 
 

@@ -127,6 +127,27 @@ def test_conv_fwd_dgrad_wgrad(case, dt):
     assert relerr(got, ref_dw) < 1e-5, relerr(got, ref_dw)
 
 
+def _sweep_setup(ffi, L, case, dt):
+    """Operands of the every-config sweep (also test_gpu_conv_bits.py): the
+    descriptor, host (x, wt, dy), device (X, W, DY) and a workspace that also
+    holds forced splits of 3."""
+    n, h, w, cin, cout, kh, kw, s, pad = case
+    rng = np.random.default_rng(7)
+    x = rng.standard_normal((n, h, w, cin)).astype(np.float32)
+    wt = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
+    cs = (cin + 3) // 4 * 4
+    xp = np.zeros((n, h, w, cs), np.float32)
+    xp[..., :cin] = x
+    d, ho, wo = _desc(ffi, n, h, w, cin, cout, kh, kw, s, pad, x_stride=cs)
+    dy = rng.standard_normal((n, ho, wo, cout)).astype(np.float32)
+    X, W, DY = dev(xp), dev(wt), dev(dy)
+    wsb = max(L.jr_conv2d_workspace_size(ctypes.byref(d), op, dt) for op in range(3))
+    wsb += 3 * 4 * max(n * ho * wo * cout, kh * kw * cs * cout, n * h * w * cs)   # forced splits of 3
+    ws = torch.zeros(wsb // 4 + 4, device="cuda")
+    _KEEP.append(ws)
+    return d, (x, wt, dy), (X, W, DY), (ws, wsb)
+
+
 @pytest.mark.parametrize("dt", CONV_DT)
 @pytest.mark.parametrize("case", [(2, 17, 17, 64, 96, 3, 3, 1, "same"), (2, 17, 17, 48, 64, 3, 3, 2, "valid"),
                                   (2, 11, 11, 3, 32, 3, 3, 2, "valid")])
@@ -136,21 +157,10 @@ def test_conv_every_tile_config(case, dt):
     ffi = _lib()
     L = ffi.load()
     n, h, w, cin, cout, kh, kw, s, pad = case
-    rng = np.random.default_rng(7)
-    x = rng.standard_normal((n, h, w, cin)).astype(np.float32)
-    wt = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
-    cs = (cin + 3) // 4 * 4
-    xp = np.zeros((n, h, w, cs), np.float32)
-    xp[..., :cin] = x
-    d, ho, wo = _desc(ffi, n, h, w, cin, cout, kh, kw, s, pad, x_stride=cs)
+    d, (x, wt, dy), (X, W, DY), (ws, wsb) = _sweep_setup(ffi, L, case, dt)
     ref = R.conv2d(x, wt, s, pad)
-    dy = rng.standard_normal(ref.shape).astype(np.float32)
     ref_dx = R.conv2d_bwd_data(dy, wt, x.shape, s, pad) if cin % 4 == 0 else None
     ref_dw = R.conv2d_bwd_filter(x, dy, wt.shape, s, pad)
-    X, W, DY = dev(xp), dev(wt), dev(dy)
-    wsb = max(L.jr_conv2d_workspace_size(ctypes.byref(d), op, dt) for op in range(3))
-    wsb += 3 * 4 * max(n * ho * wo * cout, kh * kw * cs * cout, n * h * w * cs)   # forced splits of 3
-    ws = torch.zeros(wsb // 4 + 4, device="cuda")
     cfgs = [t | (sp << 8) for t in range(L.jr_conv2d_num_configs(dt)) for sp in (0, 1, 3)]  # forced split-K
     for cfg in cfgs:
         ffi.check("set", L.jr_conv2d_set_config(ctypes.byref(d), 0, dt, 0, cfg))

@@ -140,7 +140,8 @@ CASES = [
 ]
 
 
-def _run(ffi, L, case, seed, cfg=None, extra_ws=0):
+def _run(ffi, L, case, seed, cfg=None, extra_ws=0, raw=None):
+    """raw: a dict that receives the output tensors themselves (test_gpu_conv_bits.py)."""
     n, h, w, cin, cout, kh, kw, s, pad = case
     rng = np.random.default_rng(seed)
     x = rng.standard_normal((n, h, w, cin)).astype(np.float32)
@@ -163,6 +164,8 @@ def _run(ffi, L, case, seed, cfg=None, extra_ws=0):
     ffi.check("fwd", L.jr_conv2d_fwd(ctypes.byref(d), X8P, XP.data_ptr(), WT.data_ptr(), Y.data_ptr(),
                                      ws.data_ptr(), wsb, None))
     out["fwd"] = relerr(host(Y).reshape(ref.shape), ref)
+    if raw is not None:
+        raw["fwd"] = Y
     dy = rng.standard_normal(ref.shape).astype(np.float32)
     DYP = split_planes(ffi, L, dy.reshape(-1, cout))
     if cin % 8 == 0:
@@ -171,14 +174,20 @@ def _run(ffi, L, case, seed, cfg=None, extra_ws=0):
         ffi.check("dgrad", L.jr_conv2d_bwd_data(ctypes.byref(d), X8P, DYP.data_ptr(), HW.data_ptr(), DX.data_ptr(),
                                                 0, ws.data_ptr(), wsb, None))
         out["dgrad"] = relerr(host(DX).reshape(x.shape), ref_dx)
+        if raw is not None:
+            raw["dgrad"] = DX.clone()
         ffi.check("dgrad acc", L.jr_conv2d_bwd_data(ctypes.byref(d), X8P, DYP.data_ptr(), HW.data_ptr(),
                                                     DX.data_ptr(), 1, ws.data_ptr(), wsb, None))
         out["dgrad_acc"] = relerr(host(DX).reshape(x.shape), 2 * ref_dx)
+        if raw is not None:
+            raw["dgrad_acc"] = DX
     ref_dw = R.conv2d_bwd_filter(x, dy, wt.shape, s, pad)
     DW = zeros(wt.size)
     ffi.check("wgrad", L.jr_conv2d_bwd_filter(ctypes.byref(d), X8P, XP.data_ptr(), DYP.data_ptr(), DW.data_ptr(),
                                               ws.data_ptr(), wsb, None))
     out["wgrad"] = relerr(host(DW).reshape(wt.shape), ref_dw)
+    if raw is not None:
+        raw["wgrad"] = DW
     if cfg is not None:
         for op in (0, 2):
             ffi.check("reset", L.jr_conv2d_set_config(ctypes.byref(d), op, X8P, 0, -1))
