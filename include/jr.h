@@ -480,6 +480,50 @@ typedef struct jr_absmax_seg {
 int jr_absmax_prep(const float* src, const jr_absmax_seg* segs, int32_t nseg, float* out, int64_t zero_floats,
                    void* stream);
 
+/* ---- moving averages of the BN statistics, frozen inference ----------
+ * The engines keep every conv launch's batch statistics in one flat fp32
+ * "stats" buffer, [mean(c) | invstd(c)] per launch.  These two entry points
+ * maintain Keras-style moving averages of them, layout [moving_mean(c) |
+ * moving_var(c)] per launch, and turn the averages back into the stats layout
+ * ("frozen") for a forward that does not depend on the batch.  Each is ONE
+ * launch over a device table of segments, grid (ceil(max_c / 256), nseg,
+ * members), member i at + i * its member stride (floats); no atomics, no host
+ * sync, capturable.  max_c >= every segment's c.
+ *
+ * jr_bn_moving_update, per channel of a segment (mean_b, invstd from stats):
+ *   1. v = 1.0 / ((double)invstd * (double)invstd) - (double)eps
+ *   2. v = max(v, 0)
+ *   3. v *= (double)rows / (double)(rows - 1)     (TF FusedBatchNorm feeds the
+ *      running update the unbiased variance of the rows = n*ho*wo samples)
+ *   4. var_b = (float)v
+ *   5. fp32, every operation rounded on its own, d = 1.0f - momentum
+ *      (TF assign_moving_average):
+ *        mm = mm - (mm - mean_b) * d
+ *        mv = mv - (mv - var_b) * d
+ * A segment with rows < 2 has no unbiased variance: it is left untouched
+ * (callers refuse to build such a table).
+ *
+ * jr_bn_moving_freeze, per channel:
+ *   frozen_mean = mm
+ *   frozen_invstd = (float)(1.0 / sqrt((double)mv + (double)eps))
+ *
+ * JR_ERR_INVALID (before any HIP call): a null pointer, nseg or members
+ * outside 1..65535, max_c < 1, momentum outside [0, 1], eps <= 0, a negative
+ * member stride. */
+typedef struct jr_bn_moving_seg {
+  int64_t stats_off;    /* the launch's [mean | invstd] in stats / frozen (floats) */
+  int64_t moving_off;   /* the launch's [moving_mean | moving_var] in moving (floats) */
+  int64_t rows;         /* n * ho * wo of the current batch */
+  int32_t c;
+  int32_t reserved;     /* must be 0 */
+} jr_bn_moving_seg;
+int jr_bn_moving_update(const jr_bn_moving_seg* segs, int32_t nseg, int32_t max_c, int32_t members,
+                        const float* stats, int64_t stats_member_stride, float* moving,
+                        int64_t moving_member_stride, float momentum, float eps, void* stream);
+int jr_bn_moving_freeze(const jr_bn_moving_seg* segs, int32_t nseg, int32_t max_c, int32_t members,
+                        const float* moving, int64_t moving_member_stride, float* frozen,
+                        int64_t frozen_member_stride, float eps, void* stream);
+
 /* ---- dtype helpers --------------------------------------------------- */
 int jr_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 int jr_cast_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream);

@@ -69,6 +69,16 @@ def build_parser():
     p.add_argument("--per_member", action="store_true",
                    help="one engine per ensemble member (default: every member's layers in one grouped launch, "
                         "jr.ensemble; predictions are bitwise the same)")
+    # batch-independent inference (not in the reference, whose BN always uses batch statistics)
+    p.add_argument("--bn", default="batch", choices=["batch", "moving"],
+                   help="BN statistics: batch (the reference's: every prediction depends on its evaluation batch; "
+                        "default) or moving (the moving averages saved by train.py --bn_moving, frozen: an image's "
+                        "prediction depends on that image alone)")
+    p.add_argument("--bn_calibrate_dir", default=None, metavar="DIR",
+                   help="with --bn moving: instead of saved statistics, average the batch statistics of the first "
+                        "--bn_calibrate_batches batches of the tfrecords in DIR (for checkpoints trained without "
+                        "--bn_moving; in memory, nothing is written)")
+    p.add_argument("--bn_calibrate_batches", type=int, default=16, metavar="K")
     return p
 
 
@@ -109,10 +119,53 @@ def make_engines(paths, meta, batch_size, device=0, conv_math="x6h", dtype="f32"
     return engines
 
 
-def predict_all(engines, data_dir, batch_size, rank=0, world=1):
+def load_bn_stats(paths, graph):
+    """Every member's saved moving BN statistics and the meta entry of the
+    first; SystemExit naming the first member that has none."""
+    from jr import checkpoint
+    stats = []
+    for path in paths:
+        st = checkpoint.load_bn_moving(path, graph)
+        if st is None:
+            raise SystemExit(f"{path}: checkpoint carries no moving BN statistics (trained without train.py "
+                             "--bn_moving); --bn_calibrate_dir DIR computes them from the tfrecords in DIR")
+        stats.append(st)
+    return stats, checkpoint.read_meta(paths[0])["bn_moving"]
+
+
+def freeze_engines(engines, stats=None, calibrate_dir=None, batches=16, batch_size=DEFAULT_BATCH_SIZE):
+    """Frozen BN for every member: from saved statistics (one dict per
+    member), or calibrated on the first `batches` batches of calibrate_dir
+    (jr.Engine.calibrate_bn).  Returns the number of calibration batches."""
+    grouped = hasattr(engines, "members")
+    every = [engines] if grouped else engines
+    k = 0
+    if calibrate_dir is not None:
+        g = every[0].g
+        for e in every:
+            dataset = lib.dataset.initialize_dataset(
+                calibrate_dir, batch_size, num_workers=NUM_WORKERS, prefetch_buffer_size=2 * batch_size,
+                image_data_format="channels_last", num_channels=NUM_CHANNELS, image_dim=[g.height, g.width],
+                decode_dtype="uint8", shard=(0, 1))
+            it = iter(dataset)
+            try:
+                k = e.calibrate_bn(x for j, (x, _) in zip(range(batches), it))
+            finally:
+                lib.dataset.close_iterator(it)
+    elif grouped:
+        engines.load_bn_moving(stats)
+    else:
+        for e, st in zip(engines, stats):
+            e.load_bn_moving(st)
+    for e in every:
+        e.freeze_bn("moving")
+    return k
+
+
+def predict_all(engines, data_dir, batch_size, rank=0, world=1, bn="batch"):
     """Per-member predictions over this rank's batches: ([M][n_r, 1], [n_r, 1],
     batch indices).  Each batch is decoded once (this rank's batches only)
-    and run through every member."""
+    and run through every member.  bn: "batch", or "frozen" (freeze_engines)."""
     import torch
     grouped = hasattr(engines, "members")      # jr.ensemble.EnsembleEngine
     g = engines.g if grouped else engines[0].g
@@ -133,7 +186,7 @@ def predict_all(engines, data_dir, batch_size, rank=0, world=1):
             # decoder threads already work on the next batches
             if grouped:       # every member's layer in one launch
                 n = engines.set_batch(x, y)
-                engines.forward(n)
+                engines.forward(n, bn=bn)
                 for m, p in enumerate(engines.predictions(n)):
                     preds[m].append(p)
                 continue
@@ -143,7 +196,7 @@ def predict_all(engines, data_dir, batch_size, rank=0, world=1):
             n = 0
             for e in engines:
                 n = e.set_batch(xd, y)
-                e.forward(n)
+                e.forward(n, bn=bn)
             for m, e in enumerate(engines):
                 preds[m].append(e.predictions(n))
     finally:
@@ -227,9 +280,27 @@ Using operating treshold: {},
 
     thresholds = lib.metrics.generate_thresholds(NUM_THRESHOLDS, KEPSILON) + [operating_threshold]
     meta = checkpoint.read_meta(load_model_paths[0])
-    engines = make_engines(load_model_paths, meta, batch_size, device=local, conv_math=args.conv_math,
+    conv_math, bn_stats, bn_info = args.conv_math, None, None
+    if args.bn == "moving":
+        if args.bn_calibrate_dir is None:       # before any engine is built
+            from jr.inception import build_inception_v3
+            bn_stats, bn_info = load_bn_stats(load_model_paths, build_inception_v3(
+                meta["height"], meta["width"], meta.get("units", 1)))
+        if args.dtype == "f32" and conv_math == "x6h":
+            conv_math = "x8"
+            if rank == 0:
+                print("--bn moving: conv_math x8 is used instead of x6h (x6h scales activations by a bound that "
+                      "holds only for values standardised by their own batch's statistics)")
+    engines = make_engines(load_model_paths, meta, batch_size, device=local, conv_math=conv_math,
                            dtype=args.dtype, grouped=not args.per_member)
-    preds, labels, order = predict_all(engines, data_dir, batch_size, rank, world)
+    if args.bn == "moving":
+        k = freeze_engines(engines, bn_stats, args.bn_calibrate_dir, args.bn_calibrate_batches, batch_size)
+        if rank == 0 and bn_info is not None:
+            print(f"BN statistics: moving (momentum {bn_info['momentum']}, {bn_info['updates']} updates)")
+        elif rank == 0:
+            print(f"BN statistics: moving (calibrated on {k} batches of {args.bn_calibrate_dir})")
+    preds, labels, order = predict_all(engines, data_dir, batch_size, rank, world,
+                                       bn="frozen" if args.bn == "moving" else "batch")
 
     if dist:   # gather every rank's batches to rank 0, restore dataset order
         gathered = [None] * world

@@ -93,6 +93,12 @@ class BnLaunchPlan(Structure):
         ("k1_offset", c_int64), ("workspace_size", c_int64)]
 
 
+class BnMovingSeg(Structure):
+    """include/jr.h jr_bn_moving_seg: one conv launch of jr_bn_moving_update / jr_bn_moving_freeze."""
+    _fields_ = [("stats_off", c_int64), ("moving_off", c_int64), ("rows", c_int64), ("c", c_int32),
+                ("reserved", c_int32)]
+
+
 class AugmentParam(Structure):
     """include/jr.h jr_augment_param: one image's augmentation (jr.augment builds the tables)."""
     _fields_ = [("hue_delta", c_float), ("sat_factor", c_float), ("contrast_factor", c_float),
@@ -177,6 +183,10 @@ _SIGS = {
     "jr_bn_relu_bwd_multi_absmax": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "jr_absmax_prep": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    "jr_bn_moving_update": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_float, c_float, c_void_p]),
+    "jr_bn_moving_freeze": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_float, c_void_p]),
     "jr_maxpool3x3s2_fwd": (c_int, [POINTER(PoolDesc), c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
     "jr_bn_relu_maxpool3x3s2_fwd": (c_int, [POINTER(PoolDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -10,23 +10,38 @@ recovers `path` exactly as it does for TF's `.meta/.index/.data-*` trio:
   <path>.data-00000-of-00001    raw little-endian float32, the flat
                                 parameter buffer (jr.init.param_layout)
 Loading executes nothing from the files (JSON + raw floats only).
+
+A checkpoint saved with moving BN statistics (train.py --bn_moving) has a
+fourth file, and its .meta a "bn_moving" entry (momentum, updates, channels
+per layer, sha256 of the file); checkpoints without them are unchanged:
+  <path>.bnstats                raw little-endian float32: per conv2d_bn layer
+                                in graph order, moving_mean[c] then
+                                moving_variance[c]
 """
 from __future__ import annotations
 
 import hashlib
 import json
 import os
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 
 from .init import param_layout
 
 DATA_SUFFIX = ".data-00000-of-00001"
+BN_SUFFIX = ".bnstats"
 FORMAT = "jr-checkpoint-v1"
 
 
-def save(path: str, graph, flat: np.ndarray, extra: dict | None = None) -> None:
+def _bn_names(graph):
+    return [(f"batch_normalization_{n.idx + 1}/moving_mean", f"batch_normalization_{n.idx + 1}/moving_variance",
+             n.cout) for n in graph.convs]
+
+
+def save(path: str, graph, flat: np.ndarray, extra: dict | None = None, bn_moving: dict | None = None) -> None:
+    """bn_moving: None, or {"stats": {Keras name: values} (Engine.bn_moving_numpy),
+    "momentum": float, "updates": int} -- written as <path>.bnstats."""
     layout, total = param_layout(graph.params)
     flat = np.ascontiguousarray(flat, dtype="<f4")
     if flat.size != total:
@@ -36,12 +51,31 @@ def save(path: str, graph, flat: np.ndarray, extra: dict | None = None) -> None:
     raw = flat.tobytes()
     meta = {"format": FORMAT, "height": graph.height, "width": graph.width, "units": graph.units,
             "model": "inception_v3", "num_params": graph.num_params(), **(extra or {})}
+    bn_raw = None
+    if bn_moving is not None:
+        parts = []
+        for mean, var, c in _bn_names(graph):
+            for key in (mean, var):
+                v = np.ascontiguousarray(bn_moving["stats"][key], dtype="<f4").reshape(-1)
+                if v.size != c:
+                    raise ValueError(f"{key}: {v.size} values, the layer has {c} channels")
+                parts.append(v)
+        bn_raw = np.concatenate(parts).tobytes()
+        meta["bn_moving"] = {"momentum": float(bn_moving["momentum"]), "updates": int(bn_moving["updates"]),
+                             "channels": [c for _, _, c in _bn_names(graph)],
+                             "sha256": hashlib.sha256(bn_raw).hexdigest()}
     index = {"format": FORMAT, "total": total, "sha256": hashlib.sha256(raw).hexdigest(),
              "tensors": [{"name": n, "shape": list(s), "offset": o, "size": z} for n, s, o, z in layout]}
     tmp = path + DATA_SUFFIX + ".tmp"
     with open(tmp, "wb") as f:
         f.write(raw)
     os.replace(tmp, path + DATA_SUFFIX)
+    if bn_raw is not None:
+        with open(path + BN_SUFFIX + ".tmp", "wb") as f:
+            f.write(bn_raw)
+        os.replace(path + BN_SUFFIX + ".tmp", path + BN_SUFFIX)
+    elif os.path.exists(path + BN_SUFFIX):      # statistics of a checkpoint this one replaces
+        os.remove(path + BN_SUFFIX)
     with open(path + ".index", "w") as f:
         json.dump(index, f)
     with open(path + ".meta", "w") as f:
@@ -84,3 +118,29 @@ def read_meta(path: str) -> dict:
 
 def exists(path: str) -> bool:
     return all(os.path.exists(path + s) for s in (".meta", ".index", DATA_SUFFIX))
+
+
+def load_bn_moving(path: str, graph) -> Optional[dict]:
+    """The moving BN statistics of a checkpoint by Keras name
+    (Engine.load_bn_moving), or None when it carries none (saved without
+    train.py --bn_moving, or before they existed).  A size or checksum
+    mismatch of <path>.bnstats raises."""
+    info = read_meta(path).get("bn_moving")
+    if info is None:
+        return None
+    names = _bn_names(graph)
+    if list(info.get("channels", [])) != [c for _, _, c in names]:
+        raise ValueError(f"{path}: BN statistics do not match the model graph")
+    if not os.path.exists(path + BN_SUFFIX):
+        raise ValueError(f"{path}: .meta names BN statistics but {path + BN_SUFFIX} is missing")
+    raw = open(path + BN_SUFFIX, "rb").read()
+    if len(raw) != 8 * sum(c for _, _, c in names):
+        raise ValueError(f"{path}: BN statistics size mismatch")
+    if hashlib.sha256(raw).hexdigest() != info["sha256"]:
+        raise ValueError(f"{path}: BN statistics checksum mismatch")
+    flat = np.frombuffer(raw, dtype="<f4").astype(np.float32)
+    out, off = {}, 0
+    for mean, var, c in names:
+        out[mean], out[var] = flat[off:off + c].copy(), flat[off + c:off + 2 * c].copy()
+        off += 2 * c
+    return out

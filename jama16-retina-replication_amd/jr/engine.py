@@ -17,6 +17,10 @@ that step, MI355X-native:
 * Calls are pre-bound (ctypes function + argument tuple) into call lists, so a
   step is a flat loop of C calls on one HIP stream, and the whole step can be
   captured into a HIP graph (jr_graph_*) and replayed.
+* Optional (bn_moving=momentum): one more launch per step keeps Keras-style
+  moving averages of every BN layer's batch statistics (jr_bn_moving_update);
+  freeze_bn() + forward(bn="frozen") then normalise with fixed statistics, so
+  an image's output depends on that image alone.
 * Data parallel: gradients are all-reduced (torch.distributed backend 'nccl' =
   RCCL over xGMI) in buckets issued during the backward pass, in reverse layer
   order, so communication overlaps the remaining backward kernels.
@@ -36,7 +40,7 @@ from . import _ffi
 from .inception import BN_EPS, Graph, PoolNode, build_inception_v3
 from .init import init_params
 from .lanes import Build, Call, Lanes, node_lanes, schedule
-from .plan import ConvUnit, bn_batch_groups, build_plan
+from .plan import ConvUnit, bn_batch_groups, bn_moving_segments, build_plan
 
 DTYPES = {"f32": _ffi.JR_F32, "bf16": _ffi.JR_BF16}
 
@@ -260,6 +264,139 @@ class Replica:
         if tuple(images.shape[1:]) != (ib.h, ib.w, ib.c):
             raise ValueError(f"images must be [B,{ib.h},{ib.w},{ib.c}] NHWC, got {tuple(images.shape)}")
 
+    # ------------------------------------------- moving BN statistics, frozen BN
+    def _alloc_bn_moving(self) -> None:
+        """Beside self.stats ([mean(c) | invstd(c)] per conv launch, member
+        stride self.stats_ms): `moving` ([moving_mean(c) | moving_var(c)] at the
+        same offsets, mean 0 and variance 1 as Keras initialises them) and
+        `frozen` (the statistics layout a frozen forward reads)."""
+        self.moving = self._t(self.members * self.stats_ms)
+        self.frozen = self._t(self.members * self.stats_ms)
+        self._bn_tables: Dict[int, tuple] = {}
+        self._reset_bn_moving()
+        self.frozen_source = None       # what freeze_bn last froze ("moving" / "batch")
+        self.updates = 0                # jr_bn_moving_update launches since the statistics were set
+
+    def _reset_bn_moving(self, var: float = 1.0) -> None:
+        """moving_mean = 0, moving_var = var, on self.stream (in order with the launches that update them)."""
+        host = np.zeros((self.members, self.stats_ms), np.float32)
+        off = 0
+        for u in self.cunits:
+            host[:, off + u.cout:off + 2 * u.cout] = var
+            off += 2 * u.cout
+        with torch.cuda.stream(self.stream):
+            self.moving.copy_(torch.from_numpy(host.reshape(-1)).to(self.device))
+
+    def _bn_table(self, B: int) -> tuple:
+        """(device segment table, nseg, max_c) of the jr_bn_moving_* launches at batch B."""
+        if B not in self._bn_tables:
+            segs = [_ffi.BnMovingSeg(so, mo, rows, c, 0) for so, mo, rows, c in bn_moving_segments(self.cunits, B)]
+            self._bn_tables[B] = (self._table(_ffi.BnMovingSeg, segs), len(segs), max(u.cout for u in self.cunits))
+        return self._bn_tables[B]
+
+    def _bn_update_args(self, B: int, momentum: float, s) -> tuple:
+        table, nseg, max_c = self._bn_table(B)
+        return (table.data_ptr(), nseg, max_c, self.members, self.stats.data_ptr(), self.stats_ms,
+                self.moving.data_ptr(), self.stats_ms, float(momentum), BN_EPS, s)
+
+    def _bn_layers(self):
+        """(conv2d_bn layer, offset of its mean / moving_mean, offset of its invstd / moving_var)."""
+        off = 0
+        for u in self.cunits:
+            for n, co in zip(u.members, u.col_off):
+                yield n, off + co, off + u.cout + co
+            off += 2 * u.cout
+
+    def _bn_moving_get(self) -> List[dict]:
+        self.synchronize()
+        host = self.moving.cpu().numpy().reshape(self.members, self.stats_ms)
+        out = []
+        for m in range(self.members):
+            d = {}
+            for n, om, ov in sorted(self._bn_layers(), key=lambda t: t[0].idx):
+                d[f"batch_normalization_{n.idx + 1}/moving_mean"] = host[m, om:om + n.cout].copy()
+                d[f"batch_normalization_{n.idx + 1}/moving_variance"] = host[m, ov:ov + n.cout].copy()
+            out.append(d)
+        return out
+
+    def _bn_moving_set(self, dicts) -> None:
+        if len(dicts) != self.members:
+            raise ValueError(f"expected {self.members} members' BN statistics, got {len(dicts)}")
+        host = np.zeros((self.members, self.stats_ms), np.float32)
+        for m, d in enumerate(dicts):
+            for n, om, ov in self._bn_layers():
+                for key, o, kind in ((f"batch_normalization_{n.idx + 1}/moving_mean", om, "mean"),
+                                     (f"batch_normalization_{n.idx + 1}/moving_variance", ov, "var")):
+                    if key not in d:
+                        raise ValueError(f"BN statistics lack {key}")
+                    v = np.asarray(d[key], np.float32).reshape(-1)
+                    if v.size != n.cout:
+                        raise ValueError(f"{key}: {v.size} values, the layer has {n.cout} channels")
+                    if not np.all(np.isfinite(v)):
+                        raise ValueError(f"{key}: non-finite values")
+                    if kind == "var" and np.any(v < 0):
+                        raise ValueError(f"{key}: negative variance")
+                    host[m, o:o + n.cout] = v
+        with torch.cuda.stream(self.stream):
+            self.moving.copy_(torch.from_numpy(host.reshape(-1)).to(self.device))
+        self.stream.synchronize()
+
+    def freeze_bn(self, source: str = "moving") -> None:
+        """Fill the statistics a frozen forward (forward(bn="frozen"))
+        normalises with: "moving" = from the moving averages
+        (jr_bn_moving_freeze), "batch" = a device copy of the batch statistics
+        of the last forward (bit for bit what that forward applied)."""
+        if source == "moving":
+            table, nseg, max_c = self._bn_table(self.batch)
+            _ffi.check("jr_bn_moving_freeze", self.lib.jr_bn_moving_freeze(
+                table.data_ptr(), nseg, max_c, self.members, self.moving.data_ptr(), self.stats_ms,
+                self.frozen.data_ptr(), self.stats_ms, BN_EPS, self._s))
+        elif source == "batch":
+            with torch.cuda.stream(self.stream):
+                self.frozen.copy_(self.stats)
+        else:
+            raise ValueError("freeze_bn: source is 'moving' or 'batch'")
+        self.frozen_source = source
+
+    def calibrate_bn(self, batches) -> int:
+        """Moving statistics for parameters trained without them: a forward
+        with batch statistics over every batch of `batches` (image arrays, or
+        (images, labels) pairs), and after batch k one jr_bn_moving_update with
+        momentum 1 - 1/k -- the cumulative mean of the batches' means and
+        unbiased variances (started from zero, so the first batch's statistics
+        are taken exactly).  Eager.  Returns the number of batches."""
+        self._reset_bn_moving(0.0)
+        k = 0
+        for item in batches:
+            images = item[0] if isinstance(item, (tuple, list)) else item
+            B = self.set_batch(images)
+            self.forward(B)
+            k += 1
+            _ffi.check("jr_bn_moving_update",
+                       self.lib.jr_bn_moving_update(*self._bn_update_args(B, 1.0 - 1.0 / k, self._s)))
+        if k == 0:
+            self._reset_bn_moving()
+            raise ValueError("calibrate_bn: no batches")
+        self.updates = k
+        return k
+
+    def _check_frozen(self, bn: str) -> bool:
+        """forward's bn argument -> frozen?; the refusals of the frozen mode."""
+        if bn == "batch":
+            return False
+        if bn != "frozen":
+            raise ValueError("forward: bn is 'batch' or 'frozen'")
+        if self.x6h:
+            raise ValueError("bn='frozen' is not available with conv_math='x6h': its activation scale rests on the "
+                             "bound |relu(xhat + beta)| <= sqrt(N - 1) + max |beta| of values standardised by their "
+                             "own batch, which frozen statistics void; use x8, x8p, f32 or bf16")
+        if getattr(self, "fold_stats", False):
+            raise ValueError("bn='frozen' is not available with fold_stats=True: that BN apply computes the batch "
+                             "statistics itself")
+        if self.frozen_source is None:
+            raise ValueError("bn='frozen' before freeze_bn()")
+        return True
+
 
 class Engine(Replica):
     """One model replica on one GPU (one process per GPU)."""
@@ -270,7 +407,12 @@ class Engine(Replica):
                  head: str = "sigmoid", seed: int = 0, graph: Optional[Graph] = None,
                  autotune: bool = False, tiles: str = "pinned", fuse_siblings: bool = True, lanes: int = 2,
                  conv_math: Optional[str] = None, defer_wgrad: Optional[bool] = None, fuse_pool: Optional[bool] = None,
-                 fold_stats: Optional[bool] = None):
+                 fold_stats: Optional[bool] = None, bn_moving: Optional[float] = None):
+        # bn_moving: None, or the momentum of the moving averages of the BN
+        # statistics every training step then updates (Keras: 0.99)
+        if bn_moving is not None and not 0.0 <= float(bn_moving) <= 1.0:
+            raise ValueError("bn_moving: None or a momentum in [0, 1]")
+        self.bn_momentum = None if bn_moving is None else float(bn_moving)
         # JR_LANE_PRIORITY="p0,p1,...": HIP stream priority per lane (lower =
         # higher priority). Default: lane 0 (the trunk) high for fp32 steps,
         # measured 0.1 ms/step faster over 6 interleaved rounds on two boxes
@@ -388,7 +530,9 @@ class Engine(Replica):
         # raw (pre-BN) output and BN statistics per conv launch; a fused
         # group's members see channel slices of them
         self.raw_unit = {u.first.idx: self._t(B * u.ho * u.wo * u.cout, at) for u in self.cunits}
-        self.stats = self._t(2 * sum(u.cout for u in self.cunits))
+        self.stats_ms = 2 * sum(u.cout for u in self.cunits)
+        self.stats = self._t(self.stats_ms)
+        self._alloc_bn_moving()
         self.raw, self.mean, self.invstd = {}, {}, {}
         self.mean_unit, self.invstd_unit = {}, {}
         off = 0
@@ -650,6 +794,17 @@ class Engine(Replica):
         torch.cuda.synchronize(self.device)
         return self.plan.to_keras(self.g, self.params.cpu().numpy())
 
+    def bn_moving_numpy(self) -> dict:
+        """The moving BN statistics by Keras name, per conv2d_bn layer
+        (batch_normalization_k/moving_mean, .../moving_variance)."""
+        return self._bn_moving_get()[0]
+
+    def load_bn_moving(self, stats: dict, updates: int = 0) -> None:
+        """Moving BN statistics by Keras name (bn_moving_numpy, jr.checkpoint);
+        non-finite values and negative variances are refused."""
+        self._bn_moving_set([stats])
+        self.updates = int(updates)
+
     def grads_numpy(self) -> np.ndarray:
         """Gradients of the last backward in the Keras layout."""
         torch.cuda.synchronize(self.device)
@@ -679,19 +834,22 @@ class Engine(Replica):
             groups = [[mc] for mc in groups[0]]
         return groups
 
-    def _build_calls(self, B: int, nl: Optional[int] = None):
+    def _build_calls(self, B: int, nl: Optional[int] = None, frozen: bool = False):
         """Pre-bound Calls (jr.lanes) for forward, backward, update on nl
         lanes (default self.nlanes), with their cross-lane waits:
-        (fwd, bwd, opt, keep, None)."""
+        (fwd, bwd, opt, keep, None).  frozen: the forward alone, every BN
+        apply and fused stem pool reading self.frozen (its own key)."""
         self._ensure_tiles()
         nl = self.nlanes if nl is None else max(1, min(int(nl), self.nlanes))
-        key = (B, nl)
+        key = (B, nl, "frozen") if frozen else (B, nl)
         if key in self._calls:
             return self._calls[key]
         if B > self.batch or B <= 0:
             raise ValueError(f"batch {B} outside 1..{self.batch}")
         g, unit_of = self.g, self.plan.unit_of
         b = Build(B, self.lanes, nl, self.ws_lane, self.ws_bytes, node_lanes(g, self.plan, nl), self._flush_points)
+        if frozen:
+            b.stats_shift = self.frozen.data_ptr() - self.stats.data_ptr()
         self._fwd_prep(b)
         for i, n in enumerate(g.nodes):
             if n.kind != "conv":
@@ -699,7 +857,7 @@ class Engine(Replica):
             elif unit_of[n.idx].first is n:     # a group is emitted with its first member
                 self._fwd_conv(b, b.lane_of[i], unit_of[n.idx])
         self._fwd_head(b)
-        if self.train_mode:
+        if self.train_mode and not frozen:
             if self.defer_wgrad:
                 self._bwd_slab_arena(b)
             self._bwd_head(b)
@@ -806,7 +964,8 @@ class Engine(Replica):
                 for m in u.members])
             b.keep.append(segs)
             b.add(b.fwd, L.jr_bn_relu_apply_multi,
-                  (dt, len(u.members), ctypes.byref(segs), raw, 0, u.cout, M, u.cout, mean, invstd, s),
+                  (dt, len(u.members), ctypes.byref(segs), raw, 0, u.cout, M, u.cout, mean + b.stats_shift,
+                   invstd + b.stats_shift, s),
                   "bn_relu", ln, [("r", uid), ("p",)], [("a", m.y.buf, m.y.c_off) for m in u.members],
                   nbytes=2 * M * u.cout * self.esz)
             return
@@ -814,8 +973,9 @@ class Engine(Replica):
             if m.y.buf in self.fused_bufs:
                 continue        # applied inside its max-pool
             b.add(b.fwd, L.jr_bn_relu_apply,
-                  (dt, raw, co, u.cout, M, m.cout, self.mean[m.idx].data_ptr(), self.invstd[m.idx].data_ptr(),
-                   self._beta(m), self._A(m.y.buf), m.y.c_off, g.bufs[m.y.buf].c, s),
+                  (dt, raw, co, u.cout, M, m.cout, self.mean[m.idx].data_ptr() + b.stats_shift,
+                   self.invstd[m.idx].data_ptr() + b.stats_shift, self._beta(m), self._A(m.y.buf), m.y.c_off,
+                   g.bufs[m.y.buf].c, s),
                   "bn_relu", ln, [("r", uid), ("p",)], [("a", m.y.buf, m.y.c_off)], nbytes=2 * M * m.cout * self.esz)
 
     def _fwd_pool(self, b: Build, i: int, n: PoolNode) -> None:
@@ -828,8 +988,9 @@ class Engine(Replica):
             d.x_c_off, d.x_c_stride = 0, pn.cout                       # its raw output
             puid = self.plan.unit_of[pn.idx].first.idx
             b.add(b.fwd, L.jr_bn_relu_maxpool3x3s2_fwd,
-                  (ctypes.byref(d), dt, self.raw_unit[puid].data_ptr(), self.mean[pn.idx].data_ptr(),
-                   self.invstd[pn.idx].data_ptr(), self._beta(pn), self._A(n.y.buf), self.argmax[i].data_ptr(), s),
+                  (ctypes.byref(d), dt, self.raw_unit[puid].data_ptr(), self.mean[pn.idx].data_ptr() + b.stats_shift,
+                   self.invstd[pn.idx].data_ptr() + b.stats_shift, self._beta(pn), self._A(n.y.buf),
+                   self.argmax[i].data_ptr(), s),
                   "bn_relu_maxpool_fwd", ln, [("r", puid), ("p",)], out + [("am", i)],
                   nbytes=B * n.c * (n.h * n.w * self.esz + n.ho * n.wo * (self.esz + 1)))
         elif n.kind == "maxpool":
@@ -1064,6 +1225,10 @@ class Engine(Replica):
         else:   # adam: lr_t of the step is filled in by apply_update
             b.add(b.opt, L.jr_adam_update, (P, G, acc, self.adam_v.data_ptr(), n, self.lr, self.adam_b1, self.adam_b2,
                                             self.adam_eps, 1.0, s0), "adam", 0, greads, [("p",), ("acc",)])
+        if self.bn_momentum is not None:
+            # the moving averages of this step's batch statistics (one launch; jr.h)
+            b.add(b.opt, L.jr_bn_moving_update, self._bn_update_args(b.B, self.bn_momentum, s0), "bn_moving", 0,
+                  [("r", u.first.idx) for u in self.cunits], [("bn_moving",)], nbytes=4 * 2 * self.stats_ms)
 
     def fence_lanes(self, stream) -> None:
         """`stream` (the gradient all-reduce's) waits for the work enqueued on
@@ -1104,8 +1269,10 @@ class Engine(Replica):
         return B
 
     # ------------------------------------------------------------------- runs
-    def forward(self, B: Optional[int] = None) -> None:
-        fwd = self._build_calls(B or self.batch)[0]
+    def forward(self, B: Optional[int] = None, bn: str = "batch") -> None:
+        """bn="frozen": normalise with the statistics of freeze_bn() instead
+        of this batch's (every image's output then depends on that image alone)."""
+        fwd = self._build_calls(B or self.batch, frozen=self._check_frozen(bn))[0]
         self.lanes.fork()
         self.lanes.run(fwd)
         self.lanes.join()
@@ -1132,8 +1299,10 @@ class Engine(Replica):
                 args[5] = float(f(alpha))
                 self.adam_b1p = f(self.adam_b1p * f(self.adam_b1))
                 self.adam_b2p = f(self.adam_b2p * f(self.adam_b2))
-            opt = [dataclasses.replace(c, args=tuple(args))]
+            opt = [dataclasses.replace(c, args=tuple(args))] + list(opt[1:])
         self.lanes.run(opt)
+        if self.bn_momentum is not None:
+            self.updates += 1
 
     def train_step(self, B: Optional[int] = None, allreduce=None) -> None:
         """fwd + bwd (+ bucketed all-reduce) + optimizer, enqueued on the lanes;
@@ -1184,6 +1353,8 @@ class Engine(Replica):
     def replay(self, B: Optional[int] = None) -> None:
         B = B or self.batch
         _ffi.check("jr_graph_launch", self.lib.jr_graph_launch(ctypes.c_void_p(self._graphs[B]), self._s))
+        if self.bn_momentum is not None:
+            self.updates += 1
 
     def synchronize(self) -> None:
         """Wait for every lane, then jr_device_check: a device-side failure

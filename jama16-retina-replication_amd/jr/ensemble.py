@@ -76,6 +76,7 @@ class EnsembleEngine(Replica):
         self.raw_unit = {k: self._t(M * n, at) for k, n in self.raw_ms.items()}
         self.stats_ms = 2 * sum(u.cout for u in self.cunits)
         self.stats = self._t(M * self.stats_ms)
+        self._alloc_bn_moving()
         self.stat_off, off = {}, 0
         for u in self.cunits:
             self.stat_off[u.first.idx] = off
@@ -129,19 +130,23 @@ class EnsembleEngine(Replica):
                                                                    cfgs[u.name][0]))
 
     # ------------------------------------------------------------- call list
-    def _build_calls(self, B: int):
+    def _build_calls(self, B: int, frozen: bool = False):
         """(calls, keep): the forward of every member as Calls (jr.lanes) --
         resources: activation channel slices, a launch's raw output +
-        statistics, the lane's workspace."""
+        statistics, the lane's workspace.  frozen: every BN apply and fused
+        stem pool reads self.frozen (a list of its own)."""
         if self._cfgs is not None and self.lib.jr_conv2d_config_generation() != self._gen:
             self._apply_configs(self._cfgs)        # another caller moved this geometry's tiles
             self._calls.clear()
             self._gen = self.lib.jr_conv2d_config_generation()
-        if B in self._calls:
-            return self._calls[B]
+        key = (B, "frozen") if frozen else B
+        if key in self._calls:
+            return self._calls[key]
         if B > self.batch or B <= 0:
             raise ValueError(f"batch {B} outside 1..{self.batch}")
         b = Build(B, self.lanes, self.nlanes, self.ws_lane, self.ws_bytes, node_lanes(self.g, self.plan, self.nlanes))
+        if frozen:
+            b.stats_shift = self.frozen.data_ptr() - self.stats.data_ptr()
         for i, n in enumerate(self.g.nodes):
             if n.kind != "conv":
                 self._fwd_pool(b, i, n)
@@ -149,8 +154,8 @@ class EnsembleEngine(Replica):
                 self._fwd_conv(b, b.lane_of[i], self.plan.unit_of[n.idx])
         self._fwd_head(b)
         schedule(b.seq)
-        self._calls[B] = (b.fwd, b.keep)
-        return self._calls[B]
+        self._calls[key] = (b.fwd, b.keep)
+        return self._calls[key]
 
     def _A(self, bid: int, m: int = 0) -> int:
         return self.acts[bid].data_ptr() + self.esz * m * self.act_ms[bid]
@@ -177,9 +182,10 @@ class EnsembleEngine(Replica):
             if mem.y.buf in self.fused_bufs:
                 continue        # applied inside its max-pool
             b.add(b.fwd, L.jr_bn_relu_apply_grouped,
-                  (self.dt, M, raw, co, u.cout, self.raw_ms[uid], rows, mem.cout, mean + 4 * co, inv + 4 * co,
-                   self.stats_ms, self._beta(mem), self.nparam, self._A(mem.y.buf), mem.y.c_off, g.bufs[mem.y.buf].c,
-                   self.act_ms[mem.y.buf], s), "bn_relu", ln, [("r", uid)], [("a", mem.y.buf, mem.y.c_off)])
+                  (self.dt, M, raw, co, u.cout, self.raw_ms[uid], rows, mem.cout, mean + 4 * co + b.stats_shift,
+                   inv + 4 * co + b.stats_shift, self.stats_ms, self._beta(mem), self.nparam, self._A(mem.y.buf),
+                   mem.y.c_off, g.bufs[mem.y.buf].c, self.act_ms[mem.y.buf], s),
+                  "bn_relu", ln, [("r", uid)], [("a", mem.y.buf, mem.y.c_off)])
 
     def _fwd_pool(self, b: Build, i: int, n) -> None:
         """Pools: the member-major buffers of a full batch are one batch of
@@ -194,7 +200,7 @@ class EnsembleEngine(Replica):
             if i in self.pool_fused:    # BN + ReLU of the producing layer on the fly
                 pn = self._pool_producer(n)
                 puid = self.plan.unit_of[pn.idx].first.idx
-                mean = self.stats.data_ptr() + 4 * (self.stat_off[puid] + m * self.stats_ms)
+                mean = self.stats.data_ptr() + 4 * (self.stat_off[puid] + m * self.stats_ms) + b.stats_shift
                 b.add(b.fwd, L.jr_bn_relu_maxpool3x3s2_fwd_grouped,
                       (ctypes.byref(d), self.dt, B, self.raw_unit[puid].data_ptr() + self.esz * m * self.raw_ms[puid],
                        mean, mean + 4 * pn.cout, self.stats_ms, self._beta(pn, m), self.nparam, yo, None, s),
@@ -239,8 +245,17 @@ class EnsembleEngine(Replica):
                 dst[m * n:m * n + k].copy_(dst[:k])
         return B
 
-    def forward(self, B: Optional[int] = None) -> None:
-        calls, _ = self._build_calls(B or self.batch)
+    def bn_moving_numpy(self) -> List[dict]:
+        """Every member's moving BN statistics by Keras name (jr.Engine.bn_moving_numpy)."""
+        return self._bn_moving_get()
+
+    def load_bn_moving(self, stats: List[dict]) -> None:
+        """Every member's moving BN statistics (jr.checkpoint.load_bn_moving);
+        non-finite values and negative variances are refused."""
+        self._bn_moving_set(stats)
+
+    def forward(self, B: Optional[int] = None, bn: str = "batch") -> None:
+        calls, _ = self._build_calls(B or self.batch, frozen=self._check_frozen(bn))
         self.lanes.fork()            # every lane after the batch upload on lane 0
         self.lanes.run(calls)
         self.lanes.join()

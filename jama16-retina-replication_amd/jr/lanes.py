@@ -159,6 +159,9 @@ class Build:
         self.flush_at = list(flush_points)
         self.sbuf = self.bset = 0       # alternating raw-gradient buffers: the stem's, the batched BN backwards'
         self.batch_draw: Dict[int, tuple] = {}      # batched BN backwards: launch -> (raw gradient, its resource)
+        # frozen BN (forward(bn="frozen")): byte distance from the batch statistics
+        # to the frozen ones, added to what every BN apply and fused pool reads
+        self.stats_shift = 0
 
     def add(self, lst, fn, args, name, lane, reads=(), writes=(), nbytes=0) -> None:
         c = Call(fn, args, name, lane, tuple(reads), tuple(writes), nbytes=int(nbytes))

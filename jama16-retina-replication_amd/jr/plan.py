@@ -175,6 +175,23 @@ def build_plan(g: Graph, fuse_siblings: bool = True) -> Plan:
     return Plan(units, unit_of, layout, off, poff, kview)
 
 
+def bn_moving_segments(units: List[ConvUnit], batch: int) -> List[Tuple[int, int, int, int]]:
+    """(stats offset, moving offset, rows, c) per conv launch: the segment
+    table of jr_bn_moving_update / jr_bn_moving_freeze at this batch.  The
+    statistics layout [mean(c) | invstd(c)] and the moving layout
+    [moving_mean(c) | moving_var(c)] share their offsets.  A launch with fewer
+    than two rows (n * ho * wo) has no unbiased variance: refused."""
+    segs, off = [], 0
+    for u in units:
+        rows = int(batch) * u.ho * u.wo
+        if rows < 2:
+            raise ValueError(f"BN moving statistics need at least 2 rows per channel: {u.name} has "
+                             f"{rows} at batch {batch} ({u.ho}x{u.wo} outputs)")
+        segs.append((off, off, rows, u.cout))
+        off += 2 * u.cout
+    return segs
+
+
 def bn_batch_groups(g: Graph, plan: Plan, batch: int, vec_width: int, fused_bufs) -> List[List[ConvUnit]]:
     """Conv launches whose BN backwards become due together: every member
     writes a slice of one block buffer (several producing launches: the

@@ -103,6 +103,12 @@ def build_parser():
     p.add_argument("--augment_brightness", type=float, default=None,
                    help="brightness shift range +-B of the [0, 1] pixel range (default 0.125)")
     p.add_argument("--no_augment_flip", action="store_true", help="no random left-right / up-down flips")
+    # moving averages of the BN statistics (not updated by the reference's graph: off by default)
+    p.add_argument("--bn_moving", type=float, nargs="?", const=0.99, default=None, metavar="MOMENTUM",
+                   help="keep Keras-style moving averages of the BN batch statistics (momentum 0.99 when given "
+                        "bare) and save them beside every checkpoint (<path>.bnstats) for evaluate.py --bn moving; "
+                        "training and validation still normalise with batch statistics.  Under torchrun every rank "
+                        "keeps the averages of its own batches (they match its own BN); rank 0's are saved")
     return p
 
 
@@ -222,7 +228,8 @@ Use SGD: {bool(args.vanilla_sgd)}
                     device=local, optimizer="sgd" if args.vanilla_sgd else ("nesterov" if USE_NESTEROV else "momentum"),
                     lr=LEARNING_RATE, momentum=MOMENTUM, seed=args.seed, dtype=args.dtype,
                     conv_math=args.conv_math if args.dtype == "f32" else "bf16",
-                    tiles="pinned" if args.tiles == "pinned" else "heuristic")
+                    tiles="pinned" if args.tiles == "pinned" else "heuristic",
+                    **({} if args.bn_moving is None else {"bn_moving": args.bn_moving}))
     table = None
     if args.tile_table:
         table = load_tile_table(args.tile_table)
@@ -269,6 +276,13 @@ Use SGD: {bool(args.vanilla_sgd)}
             dist.all_gather_object(got, digest)
             if len(set(got)) != 1:
                 raise RuntimeError(f"data-parallel replicas diverged after epoch {epoch}: {got}")
+
+    def bn_state():
+        """checkpoint.save's bn_moving argument (--bn_moving), else nothing."""
+        if args.bn_moving is None:
+            return {}
+        return {"bn_moving": {"stats": engine.bn_moving_numpy(), "momentum": args.bn_moving,
+                              "updates": engine.updates}}
     train_writer = FileWriter(os.path.join(args.save_summaries_dir, "train")) if rank == 0 else None
 
     latest_peak_auc = 0.0
@@ -320,7 +334,8 @@ Use SGD: {bool(args.vanilla_sgd)}
             if rank == 0:
                 print(f"New peak auc reached: {val_auc:10.8}")
                 checkpoint.save(args.save_model_path, engine.g, engine.params_numpy(),
-                                {"epoch": epoch, "val_auc": float(val_auc), "tile_table": engine.tile_table(), **aug_meta})
+                                {"epoch": epoch, "val_auc": float(val_auc), "tile_table": engine.tile_table(),
+                                 **aug_meta}, **bn_state())
             saved = True
             waited_epochs = 0
 
@@ -331,6 +346,10 @@ Use SGD: {bool(args.vanilla_sgd)}
     if saved:
         flat, _ = checkpoint.load(args.save_model_path, engine.g)
         engine.load_params(flat)
+        if args.bn_moving is not None:      # the statistics saved with those weights
+            stats = checkpoint.load_bn_moving(args.save_model_path, engine.g)
+            if stats is not None:
+                engine.load_bn_moving(stats, checkpoint.read_meta(args.save_model_path)["bn_moving"]["updates"])
     sess.reset("tp", "fp", "fn", "tn")
     it = iter(train_dataset)
     try:
