@@ -6,7 +6,7 @@ before applying BN + ReLU.  Checked here:
   * per launch, against jr_conv2d_fwd_bn_stats + jr_bn_relu_apply on the
     same inputs: raw output, every member slice's activation, mean and
     invstd BITWISE equal -- planner tiles, a forced split-K factor (partials
-    from the split-K reduce) and a stream-K grid (x8), fp32 (x8) and bf16;
+    from the split-K reduce) and a stream-K grid (x8, x6h), fp32 (x8, x6h) and bf16;
   * the engine with the fold on and off: three training steps bitwise equal
     (loss, parameters) and the forward of an eval engine equal, f32 and bf16;
   * the layout query's geometry (P partials of R rows cover M)."""
@@ -33,7 +33,7 @@ CASES = [  # n, h, w, cin, members' cout, kh, kw, stride, pad
 ]
 
 
-@pytest.mark.parametrize("dt", ["x8", "bf16"])
+@pytest.mark.parametrize("dt", ["x8", "x6h", "bf16"])
 @pytest.mark.parametrize("cfg", [None, "split", "sk"])
 @pytest.mark.parametrize("case", CASES)
 def test_fold_equals_separate_finalize(case, cfg, dt):
@@ -41,9 +41,9 @@ def test_fold_equals_separate_finalize(case, cfg, dt):
     L = ffi.load()
     n, h, w, cin, couts, kh, kw, s, pad = case
     cout = sum(couts)
-    code = ffi.JR_F32_X8 if dt == "x8" else ffi.JR_BF16
-    adt = ffi.JR_F32 if dt == "x8" else ffi.JR_BF16
-    et = torch.float32 if dt == "x8" else torch.bfloat16
+    code = {"x8": ffi.JR_F32_X8, "x6h": ffi.JR_F32_X6H, "bf16": ffi.JR_BF16}[dt]
+    adt = ffi.JR_BF16 if dt == "bf16" else ffi.JR_F32
+    et = torch.bfloat16 if dt == "bf16" else torch.float32
     ph, pw = (0, pad) if kh == 1 else (pad, 0) if kw == 1 else (pad, pad)
     ho, wo = (h + 2 * ph - kh) // s + 1, (w + 2 * pw - kw) // s + 1
     d = ffi.ConvDesc(n, h, w, cin, cout, kh, kw, s, s, ph, pw, ho, wo, 0, cin, 0, cout)
@@ -60,6 +60,10 @@ def test_fold_equals_separate_finalize(case, cfg, dt):
         else:
             wt = torch.randn(kh * kw * cin * cout, device="cuda", generator=g) * 0.05
         beta = torch.randn(cout, device="cuda", generator=g) * 0.1
+        if dt == "x6h":       # operand magnitudes as test_gpu_x6h.py: a host bound for x, device words for w
+            wm = torch.zeros(64, device="cuda")
+            wm[5] = float(wt.abs().max())
+            d.x_bound, d.w_absmax = float(x.abs().max()) * 1.5, wm.data_ptr()
         M = n * ho * wo
         wsb = L.jr_conv2d_workspace_size(ctypes.byref(d), 0, code)
         lay = ffi.BnPartials()

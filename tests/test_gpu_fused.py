@@ -1,6 +1,6 @@
 """jr_conv2d_fwd_bn_stats: conv forward fused with the training-mode
 BatchNormalization statistics of its output (Keras conv2d_bn, App. C Q1),
-through the C-ABI, fp32 and bf16, with the statistics produced by the GEMM
+through the C-ABI, fp32 (JR_F32, JR_F32_X8, JR_F32_X6H) and bf16, with the statistics produced by the GEMM
 epilogue (no split-K) and by the split-K reduce (forced split factors).
 
 Checks: the raw output equals the oracle conv (fp32 1e-5 / bf16 8e-3 of
@@ -45,13 +45,13 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("dtype", ["f32", "f32x8", "bf16"])
+@pytest.mark.parametrize("dtype", ["f32", "f32x8", "f32x6h", "bf16"])
 @pytest.mark.parametrize("case", CASES)
 def test_conv_fwd_bn_stats(case, dtype):
     from jr import _ffi
     _ffi.init(0)
     L = _ffi.load()
-    dt = {"f32": 0, "bf16": 1, "f32x8": 2}[dtype]
+    dt = {"f32": 0, "bf16": 1, "f32x8": 2, "f32x6h": 4}[dtype]
     f32 = dtype != "bf16"
     tdt = torch.float32 if f32 else torch.bfloat16
     q = 4 if f32 else 8
@@ -76,6 +76,11 @@ def test_conv_fwd_bn_stats(case, dtype):
     ph, pw = ((kh - 1) // 2, (kw - 1) // 2) if pad == "same" else (0, 0)
     ho, wo = (h + 2 * ph - kh) // s + 1, (w + 2 * pw - kw) // s + 1
     d = _ffi.ConvDesc(n, h, w, cin, cout, kh, kw, s, s, ph, pw, ho, wo, 0, cq, 0, cout)
+    if dtype == "f32x6h":     # operand magnitudes as test_gpu_x6h.py: a host bound for x, device words for w
+        wm = torch.zeros(64, device="cuda")
+        wm[5], wm[12] = float(np.abs(wt).max()), float(np.abs(wt).max()) / 3
+        _KEEP.append(wm)
+        d.x_bound, d.w_absmax = float(np.abs(xr).max()) * 1.5, wm.data_ptr()
     ref = R.conv2d(xr, wr, s, pad)
     # + room for the forced split-K factors below (beyond the planner's own)
     wsb = L.jr_conv2d_workspace_size(ctypes.byref(d), 0, dt) + 5 * n * ho * wo * cout * 4 + (1 << 20)
