@@ -95,7 +95,13 @@ typedef struct jr_conv_desc {
    * operand's power-of-two scale.  *_absmax: NULL, or 64 device floats whose
    * maximum is (an upper bound of) max |tensor| -- jr_absmax_prep for
    * filters, jr_bn_relu_bwd_multi_absmax / jr_bn_relu_bwd_maxpool_absmax for
-   * a data gradient; when NULL, *_bound is a host upper bound (0: 2^14). */
+   * a data gradient; when NULL, *_bound is a host upper bound.  A stated
+   * magnitude m > 0 gives the scale s = 2^k with m s in [2^14, 2^15) (k <=
+   * 100), exactly 2^14 when m is a power of two: values up to twice a
+   * power-of-two bound still split exactly.  A bound (or a words' maximum) of
+   * 0 -- or negative, inf or NaN -- gives s = 1: the operand is split as it
+   * is, which is right for magnitudes below 2^15, exact from 2^-1 up and to
+   * 2^-24 absolute below. */
   const float* x_absmax;
   const float* w_absmax;
   const float* dy_absmax;

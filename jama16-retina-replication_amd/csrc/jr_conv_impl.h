@@ -58,7 +58,8 @@ struct ConvArgs {
   unsigned* sk_err;
   // JR_F32_X6H: magnitude bounds of the A / B operands for their
   // power-of-two scales: 64 device floats whose max is max |operand|
-  // (nullptr: the host bound a_bnd / b_bnd; 0 = 2^14, scale 1)
+  // (nullptr: the host bound a_bnd / b_bnd; 0 = scale 1, for magnitudes
+  // below 2^15)
   const float* a_max;
   const float* b_max;
   float a_bnd, b_bnd;
