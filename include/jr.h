@@ -575,6 +575,40 @@ size_t jr_augment_workspace_size(int32_t n, int32_t h, int32_t w);
 int jr_image_u8_augment_nhwc(const uint8_t* src, void* dst, int dtype, int32_t n, int32_t h, int32_t w,
                              int32_t c, int32_t dst_stride, const jr_augment_param* params,
                              void* ws, size_t ws_bytes, void* stream);
+/* The same transform with a per-image affine resampling (rotation, zoom,
+ * shift) in stage 1; also the input kernel of test-time augmentation.  The
+ * arguments, their validation and the workspace are jr_image_u8_augment_nhwc's,
+ * plus warps: n entries in DEVICE memory.  Stages 0, 2, 3, 4 and the clamp are
+ * unchanged; fp32, every operation rounded on its own.  Stage 1 of destination
+ * pixel (x, y) of image i, m = warps[i].m:
+ *  1a. x' = w-1-x if flags & 1, else x;  y' = h-1-y if flags & 2, else y
+ *  1b. u = (m0 f32(x') + m1 f32(y')) + m2,  v = (m3 f32(x') + m4 f32(y')) + m5:
+ *      the source position in pixel-index units
+ *  1c. unless u > -1 && u < w && v > -1 && v < h (false for NaN and +-inf as
+ *      well) the stage-1 value is (0, 0, 0); no address is formed from such a
+ *      u or v
+ *  1d. x0 = floor(u), fx = u - x0, y0 = floor(v), fy = v - y0; tap p(i, j) is
+ *      the stage-0 value of source pixel (x0 + i, y0 + j) inside the image,
+ *      else 0; per channel top = p00 + fx (p10 - p00), bot = p01 + fx (p11 -
+ *      p01), out = top + fy (bot - top)
+ * The contrast mean of stage 3 is taken over all h*w destination pixels after
+ * stages 1 - 2 (fill pixels count): fp32 partials, their number a function of
+ * (h, w) alone, combined in fp64 in a fixed order, no atomics -- an image's
+ * result is bitwise reproducible and independent of n and of its slot.  The
+ * partials take the pixels in the order of (x', y') (a flip permutes the terms
+ * of the sum, not their values), 2048 to a partial as above: at the identity
+ * matrix the mean is jr_image_u8_augment_nhwc's bit for bit.
+ * With fx = fy = 0 the lerps return p00 bit for bit, so a matrix that maps the
+ * pixel lattice onto itself is a pure permutation: the identity (1, 0, 0, 0,
+ * 1, 0) gives jr_image_u8_augment_nhwc's output, (-1, 0, w-1, 0, 1, 0) the
+ * left-right flip, the quarter turns of a square image its rotations. */
+typedef struct jr_warp_param {   /* 32 bytes, one per image */
+  float m[6];                    /* destination pixel (x, y) -> source position (u, v), pixel-index units */
+  uint32_t reserved[2];          /* must be 0 */
+} jr_warp_param;
+int jr_image_u8_warp_augment_nhwc(const uint8_t* src, void* dst, int dtype, int32_t n, int32_t h, int32_t w,
+                                  int32_t c, int32_t dst_stride, const jr_augment_param* params,
+                                  const jr_warp_param* warps, void* ws, size_t ws_bytes, void* stream);
 /* acc[0] += sum (p - y)^2, acc[1] += n   (tf.metrics.mean_squared_error,
  * train.py:175-177) */
 int jr_brier_accumulate(const float* probs, const float* labels, int32_t n, double* acc, void* stream);

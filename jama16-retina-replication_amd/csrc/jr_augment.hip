@@ -23,6 +23,22 @@
 // jr_image_u8_to_nhwc's output bit for bit.  Compiled with -ffp-contract=off
 // (Makefile): each multiply and add rounds on its own, the IEEE fp32
 // evaluation of the formulas in jr.h.
+//
+// jr_image_u8_warp_augment_nhwc adds a per-image affine resampling (rotation,
+// zoom, shift: a jr_warp_param per image) in front of the HSV stage.  It is a
+// gather: a row of destination pixels reads a slanted line of the source.
+//   k_warp_sums   k_aug_sums over DESTINATION pixels after the warp and the HSV
+//                 stage (fill pixels count): the same slots, the same pixel
+//                 order and lane assignment, so at the identity matrix the
+//                 mean is k_aug_sums' bit for bit; a block's 2048 pixels are a
+//                 band of a few rows, its source footprint a slanted band
+//   k_warp_apply  walks 16 x 16 destination tiles, one pixel per lane, so a
+//                 block's source footprint is a compact patch that L1 / L2
+//                 serve (no LDS staging; timings in DESIGN.md): flip, source position, outside
+//                 test, four guarded taps, the two lerps, then the stages and
+//                 the stores of k_aug_apply
+// With fx == fy == 0 the lerps return the first tap bit for bit, so a matrix
+// that maps the pixel lattice onto itself is a pure permutation.
 #include "jr_common.h"
 
 namespace jr {
@@ -78,6 +94,28 @@ __device__ __forceinline__ void load_pixel(const uint8_t* __restrict__ s, bool h
   if (hsv) hue_sat(r, g, b, hd, sf);
 }
 
+// one block's channel sums into its partial slot: thread -> wave shuffle -> LDS
+// -> three stores (every thread of the 256 calls)
+__device__ __forceinline__ void block_partial(float sr, float sg, float sb, float* __restrict__ slot) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    sr = __fadd_rn(sr, __shfl_xor(sr, o, 64));
+    sg = __fadd_rn(sg, __shfl_xor(sg, o, 64));
+    sb = __fadd_rn(sb, __shfl_xor(sb, o, 64));
+  }
+  __shared__ float red[4][3];
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6][0] = sr;
+    red[threadIdx.x >> 6][1] = sg;
+    red[threadIdx.x >> 6][2] = sb;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int c = threadIdx.x;
+    slot[c] = __fadd_rn(__fadd_rn(red[0][c], red[1][c]), __fadd_rn(red[2][c], red[3][c]));
+  }
+}
+
 // grid (P, n): block (p, i) sums source pixels [p * kAugChunk, ...) of image i
 __global__ void __launch_bounds__(256) k_aug_sums(const uint8_t* __restrict__ src,
                                                   const jr_augment_param* __restrict__ params, int hw,
@@ -100,29 +138,58 @@ __global__ void __launch_bounds__(256) k_aug_sums(const uint8_t* __restrict__ sr
       sb = __fadd_rn(sb, b);
     }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    sr = __fadd_rn(sr, __shfl_xor(sr, o, 64));
-    sg = __fadd_rn(sg, __shfl_xor(sg, o, 64));
-    sb = __fadd_rn(sb, __shfl_xor(sb, o, 64));
-  }
-  __shared__ float red[4][3];
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6][0] = sr;
-    red[threadIdx.x >> 6][1] = sg;
-    red[threadIdx.x >> 6][2] = sb;
+  block_partial(sr, sg, sb, part + ((int64_t)img * P + blockIdx.x) * 4);
+}
+
+// the contrast mean of one image from its P partial triples, in slot order in
+// fp64 (block-uniform `contrast`; every thread of the block calls)
+__device__ __forceinline__ void image_mean(bool contrast, const float* __restrict__ part, int P, int hw,
+                                           float (&mean)[3]) {
+  __shared__ float s_mean[3];
+  mean[0] = mean[1] = mean[2] = 0.f;
+  if (!contrast) return;
+  if (threadIdx.x < 3) {
+    const float* q = part + threadIdx.x;
+    double a = 0.0;
+    for (int i = 0; i < P; ++i) a += (double)q[(int64_t)i * 4];
+    s_mean[threadIdx.x] = (float)(a / (double)hw);
   }
   __syncthreads();
-  if (threadIdx.x < 3) {
-    const int c = threadIdx.x;
-    part[((int64_t)img * P + blockIdx.x) * 4 + c] =
-        __fadd_rn(__fadd_rn(red[0][c], red[1][c]), __fadd_rn(red[2][c], red[3][c]));
+  mean[0] = s_mean[0];
+  mean[1] = s_mean[1];
+  mean[2] = s_mean[2];
+}
+
+// stages 3 - 5 of one pixel after stage 2 and its store at o
+// VEC = dst_stride when one aligned vector store covers the pixel (4: fp32 16 B
+// or bf16 8 B; 8: bf16 16 B, the engine's bf16 input), 0: element stores
+template <typename T, int VEC>
+__device__ __forceinline__ void finish_pixel(float (&v)[3], const jr_augment_param& pr, bool contrast, bool bright,
+                                             const float (&mean)[3], T* __restrict__ o, int ds) {
+  if (contrast) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = __fadd_rn(__fmul_rn(__fsub_rn(v[c], mean[c]), pr.contrast_factor), mean[c]);
+  }
+  if (bright) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = __fadd_rn(v[c], pr.brightness_delta);
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = clamp01(v[c]);
+  if constexpr (VEC == 4 && sizeof(T) == 4) {
+    *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], 0.f);
+  } else if constexpr (VEC == 4) {
+    *reinterpret_cast<uint2*>(o) = make_uint2(f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16), f2bf(v[2]));
+  } else if constexpr (VEC == 8) {
+    *reinterpret_cast<uint4*>(o) = make_uint4(f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16), f2bf(v[2]), 0u, 0u);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Elt<T>::st(o + c, v[c]);
+    for (int c = 3; c < ds; ++c) Elt<T>::st(o + c, 0.f);
   }
 }
 
 // grid (blocks per image, n), grid-stride over the image's destination pixels
-// VEC = dst_stride when one aligned vector store covers the pixel (4: fp32 16 B
-// or bf16 8 B; 8: bf16 16 B, the engine's bf16 input), 0: element stores
 template <typename T, int VEC>
 __global__ void __launch_bounds__(256) k_aug_apply(const uint8_t* __restrict__ src, T* __restrict__ dst,
                                                    const jr_augment_param* __restrict__ params, int h, int w, int ds,
@@ -132,22 +199,8 @@ __global__ void __launch_bounds__(256) k_aug_apply(const uint8_t* __restrict__ s
   const bool hsv = !(pr.hue_delta == 0.f && pr.sat_factor == 1.f);
   const bool contrast = pr.contrast_factor != 1.f, bright = pr.brightness_delta != 0.f;
   const bool flip_lr = pr.flags & 1u, flip_ud = pr.flags & 2u;
-  __shared__ float s_mean[3];
-  if (contrast) {   // block-uniform
-    if (threadIdx.x < 3) {
-      const float* q = part + (int64_t)img * P * 4 + threadIdx.x;
-      double a = 0.0;
-      for (int i = 0; i < P; ++i) a += (double)q[(int64_t)i * 4];
-      s_mean[threadIdx.x] = (float)(a / (double)hw);
-    }
-    __syncthreads();
-  }
-  float mr = 0.f, mg = 0.f, mb = 0.f;
-  if (contrast) {
-    mr = s_mean[0];
-    mg = s_mean[1];
-    mb = s_mean[2];
-  }
+  float mean[3];
+  image_mean(contrast, part + (int64_t)img * P * 4, P, hw, mean);
   const uint8_t* s = src + (int64_t)img * hw * 3;
   T* d = dst + (int64_t)img * hw * ds;
   for (int p = blockIdx.x * 256 + (int)threadIdx.x; p < hw; p += (int)gridDim.x * 256) {
@@ -155,29 +208,7 @@ __global__ void __launch_bounds__(256) k_aug_apply(const uint8_t* __restrict__ s
     const int sy = flip_ud ? h - 1 - y : y, sx = flip_lr ? w - 1 - x : x;
     float v[3];
     load_pixel(s + ((int64_t)sy * w + sx) * 3, hsv, pr.hue_delta, pr.sat_factor, v[0], v[1], v[2]);
-    if (contrast) {
-      v[0] = __fadd_rn(__fmul_rn(__fsub_rn(v[0], mr), pr.contrast_factor), mr);
-      v[1] = __fadd_rn(__fmul_rn(__fsub_rn(v[1], mg), pr.contrast_factor), mg);
-      v[2] = __fadd_rn(__fmul_rn(__fsub_rn(v[2], mb), pr.contrast_factor), mb);
-    }
-    if (bright) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = __fadd_rn(v[c], pr.brightness_delta);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = clamp01(v[c]);
-    T* o = d + (int64_t)p * ds;
-    if constexpr (VEC == 4 && sizeof(T) == 4) {
-      *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], 0.f);
-    } else if constexpr (VEC == 4) {
-      *reinterpret_cast<uint2*>(o) = make_uint2(f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16), f2bf(v[2]));
-    } else if constexpr (VEC == 8) {
-      *reinterpret_cast<uint4*>(o) = make_uint4(f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16), f2bf(v[2]), 0u, 0u);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) Elt<T>::st(o + c, v[c]);
-      for (int c = 3; c < ds; ++c) Elt<T>::st(o + c, 0.f);
-    }
+    finish_pixel<T, VEC>(v, pr, contrast, bright, mean, d + (int64_t)p * ds, ds);
   }
 }
 
@@ -195,6 +226,121 @@ static void launch_apply(const uint8_t* src, void* dst, int n, int h, int w, int
     hipLaunchKernelGGL((k_aug_apply<T, 0>), grid, dim3(256), 0, s, src, (T*)dst, params, h, w, ds, P, part);
 }
 
+constexpr int kWarpTile = 16;          // destination tile edge: 16 x 16 pixels, one per lane
+
+// tap (x, y) of the bilinear footprint: the stage-0 value of that source pixel,
+// 0 outside the image (no address is formed there)
+__device__ __forceinline__ void warp_tap(const uint8_t* __restrict__ s, int h, int w, int x, int y, float (&p)[3]) {
+  const float scale = 1.0f / 255.0f;
+  p[0] = p[1] = p[2] = 0.f;
+  if ((unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h) {
+    const uint8_t* q = s + ((int64_t)y * w + x) * 3;
+    p[0] = __fmul_rn((float)q[0], scale);
+    p[1] = __fmul_rn((float)q[1], scale);
+    p[2] = __fmul_rn((float)q[2], scale);
+  }
+}
+
+__device__ __forceinline__ float lerp_rn(float a, float b, float f) { return __fadd_rn(a, __fmul_rn(f, __fsub_rn(b, a))); }
+
+// stages 0 - 2 of destination pixel (x, y) of the warp entry point (jr.h 1a - 1d, then hue / saturation)
+__device__ __forceinline__ void warp_pixel(const uint8_t* __restrict__ s, int h, int w, const jr_augment_param& pr,
+                                           const jr_warp_param& wp, bool hsv, int x, int y, float (&v)[3]) {
+  const float xf = (float)((pr.flags & 1u) ? w - 1 - x : x), yf = (float)((pr.flags & 2u) ? h - 1 - y : y);
+  const float u = __fadd_rn(__fadd_rn(__fmul_rn(wp.m[0], xf), __fmul_rn(wp.m[1], yf)), wp.m[2]);
+  const float t = __fadd_rn(__fadd_rn(__fmul_rn(wp.m[3], xf), __fmul_rn(wp.m[4], yf)), wp.m[5]);
+  v[0] = v[1] = v[2] = 0.f;
+  if (u > -1.f && u < (float)w && t > -1.f && t < (float)h) {   // false for NaN and +-inf too
+    const float x0f = floorf(u), y0f = floorf(t);
+    const float fx = __fsub_rn(u, x0f), fy = __fsub_rn(t, y0f);
+    const int x0 = (int)x0f, y0 = (int)y0f;                     // in [-1, w - 1] x [-1, h - 1]
+    float p00[3], p10[3], p01[3], p11[3];
+    warp_tap(s, h, w, x0, y0, p00);
+    warp_tap(s, h, w, x0 + 1, y0, p10);
+    warp_tap(s, h, w, x0, y0 + 1, p01);
+    warp_tap(s, h, w, x0 + 1, y0 + 1, p11);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = lerp_rn(lerp_rn(p00[c], p10[c], fx), lerp_rn(p01[c], p11[c], fx), fy);
+  }
+  if (hsv) hue_sat(v[0], v[1], v[2], pr.hue_delta, pr.sat_factor);
+}
+
+// grid (P, n): block (p, i) sums destination pixels [p * kAugChunk, ...) of
+// image i after stages 0 - 2, in the pixel order and lane assignment of
+// k_aug_sums: at the identity matrix the partials, and so the mean, are its
+// bits.  The flips permute the destination pixels and leave their sum's terms
+// alone, so the walk is over (x', y') of jr.h 1a, whatever the flags.
+__global__ void __launch_bounds__(256) k_warp_sums(const uint8_t* __restrict__ src,
+                                                   const jr_augment_param* __restrict__ params,
+                                                   const jr_warp_param* __restrict__ warps, int h, int w,
+                                                   float* __restrict__ part) {
+  const int img = blockIdx.y, P = gridDim.x, hw = h * w;
+  jr_augment_param pr = params[img];
+  if (pr.contrast_factor == 1.f) return;
+  pr.flags = 0;
+  const jr_warp_param wp = warps[img];
+  const bool hsv = !(pr.hue_delta == 0.f && pr.sat_factor == 1.f);
+  const uint8_t* s = src + (int64_t)img * hw * 3;
+  const int p0 = blockIdx.x * kAugChunk;
+  float sr = 0.f, sg = 0.f, sb = 0.f;
+#pragma unroll 2
+  for (int k = 0; k < kAugChunk / 256; ++k) {
+    const int p = p0 + k * 256 + (int)threadIdx.x;
+    if (p < hw) {
+      const int y = p / w;
+      float v[3];
+      warp_pixel(s, h, w, pr, wp, hsv, p - y * w, y, v);
+      sr = __fadd_rn(sr, v[0]);
+      sg = __fadd_rn(sg, v[1]);
+      sb = __fadd_rn(sb, v[2]);
+    }
+  }
+  block_partial(sr, sg, sb, part + ((int64_t)img * P + blockIdx.x) * 4);
+}
+
+// grid (blocks per image, n), grid-stride over the image's T destination tiles
+template <typename T_, int VEC>
+__global__ void __launch_bounds__(256) k_warp_apply(const uint8_t* __restrict__ src, T_* __restrict__ dst,
+                                                    const jr_augment_param* __restrict__ params,
+                                                    const jr_warp_param* __restrict__ warps, int h, int w, int ds,
+                                                    int tx, int T, int P, const float* __restrict__ part) {
+  const int img = blockIdx.y, hw = h * w;
+  const jr_augment_param pr = params[img];
+  const jr_warp_param wp = warps[img];
+  const bool hsv = !(pr.hue_delta == 0.f && pr.sat_factor == 1.f);
+  const bool contrast = pr.contrast_factor != 1.f, bright = pr.brightness_delta != 0.f;
+  float mean[3];
+  image_mean(contrast, part + (int64_t)img * P * 4, P, hw, mean);
+  const uint8_t* s = src + (int64_t)img * hw * 3;
+  T_* d = dst + (int64_t)img * hw * ds;
+  const int lx = threadIdx.x % kWarpTile, ly = threadIdx.x / kWarpTile;
+  for (int t = blockIdx.x; t < T; t += (int)gridDim.x) {
+    const int ty = t / tx, x = (t - ty * tx) * kWarpTile + lx, y = ty * kWarpTile + ly;
+    if (x < w && y < h) {
+      float v[3];
+      warp_pixel(s, h, w, pr, wp, hsv, x, y, v);
+      finish_pixel<T_, VEC>(v, pr, contrast, bright, mean, d + ((int64_t)y * w + x) * ds, ds);
+    }
+  }
+}
+
+template <typename T>
+static void launch_warp_apply(const uint8_t* src, void* dst, int n, int h, int w, int ds,
+                              const jr_augment_param* params, const jr_warp_param* warps, int tx, int tiles, int P,
+                              const float* part, hipStream_t s) {
+  const dim3 grid(std::min(tiles, std::max(1, kAugMaxBlocks / n)), n);
+  const bool aligned = ((uintptr_t)dst & ((size_t)ds * sizeof(T) - 1)) == 0;
+  if (ds == 4 && aligned)
+    hipLaunchKernelGGL((k_warp_apply<T, 4>), grid, dim3(256), 0, s, src, (T*)dst, params, warps, h, w, ds, tx, tiles, P,
+                       part);
+  else if (ds == 8 && sizeof(T) == 2 && aligned)
+    hipLaunchKernelGGL((k_warp_apply<T, 8>), grid, dim3(256), 0, s, src, (T*)dst, params, warps, h, w, ds, tx, tiles, P,
+                       part);
+  else
+    hipLaunchKernelGGL((k_warp_apply<T, 0>), grid, dim3(256), 0, s, src, (T*)dst, params, warps, h, w, ds, tx, tiles, P,
+                       part);
+}
+
 // geometry both entry points accept: the batch is the grid's y extent and an
 // image's pixel count stays far inside int32
 static bool aug_geometry_ok(int32_t n, int32_t h, int32_t w) {
@@ -210,18 +356,28 @@ JR_API size_t jr_augment_workspace_size(int32_t n, int32_t h, int32_t w) {
   return (size_t)n * aug_partials(h, w) * 4 * sizeof(float);
 }
 
+// what both entry points check before they launch (`null`: one of their
+// pointers is); JR_OK to go on -- n == 0 passes and launches nothing
+static int aug_check(const std::string& who, bool null, int dtype, int32_t n, int32_t h, int32_t w, int32_t c,
+                     int32_t dst_stride, const void* ws, size_t ws_bytes) {
+  if (null) return fail(JR_ERR_INVALID, who + ": null pointer");
+  if (c != 3) return fail(JR_ERR_INVALID, who + ": c must be 3 (RGB)");
+  if (dst_stride < 3) return fail(JR_ERR_INVALID, who + ": dst_stride must be >= 3");
+  if (dtype != JR_F32 && dtype != JR_BF16) return fail(JR_ERR_INVALID, who + ": dtype must be JR_F32 or JR_BF16");
+  if (n == 0) return JR_OK;
+  if (!aug_geometry_ok(n, h, w)) return fail(JR_ERR_INVALID, who + ": bad n / h / w");
+  if (ws_bytes < jr_augment_workspace_size(n, h, w))
+    return fail(JR_ERR_INVALID, who + ": workspace smaller than jr_augment_workspace_size");
+  if ((uintptr_t)ws & 3) return fail(JR_ERR_INVALID, who + ": workspace must be 4-byte aligned");
+  return JR_OK;
+}
+
 JR_API int jr_image_u8_augment_nhwc(const uint8_t* src, void* dst, int dtype, int32_t n, int32_t h, int32_t w,
                                     int32_t c, int32_t dst_stride, const jr_augment_param* params, void* ws,
                                     size_t ws_bytes, void* stream) {
-  if (!src || !dst || !params || !ws) return fail(JR_ERR_INVALID, "image_u8_augment: null pointer");
-  if (c != 3) return fail(JR_ERR_INVALID, "image_u8_augment: c must be 3 (RGB)");
-  if (dst_stride < 3) return fail(JR_ERR_INVALID, "image_u8_augment: dst_stride must be >= 3");
-  if (dtype != JR_F32 && dtype != JR_BF16) return fail(JR_ERR_INVALID, "image_u8_augment: dtype must be JR_F32 or JR_BF16");
+  if (int rc = aug_check("image_u8_augment", !src || !dst || !params || !ws, dtype, n, h, w, c, dst_stride, ws, ws_bytes))
+    return rc;
   if (n == 0) return JR_OK;
-  if (!aug_geometry_ok(n, h, w)) return fail(JR_ERR_INVALID, "image_u8_augment: bad n / h / w");
-  if (ws_bytes < jr_augment_workspace_size(n, h, w))
-    return fail(JR_ERR_INVALID, "image_u8_augment: workspace smaller than jr_augment_workspace_size");
-  if ((uintptr_t)ws & 3) return fail(JR_ERR_INVALID, "image_u8_augment: workspace must be 4-byte aligned");
   hipStream_t s = as_stream(stream);
   const int P = aug_partials(h, w);
   float* part = (float*)ws;
@@ -229,4 +385,24 @@ JR_API int jr_image_u8_augment_nhwc(const uint8_t* src, void* dst, int dtype, in
   if (int rc = check_launch("image_u8_augment sums")) return rc;
   by_dtype(dtype, [&](auto t) { launch_apply<decltype(t)>(src, dst, n, h, w, dst_stride, params, P, part, s); });
   return check_launch("image_u8_augment");
+}
+
+JR_API int jr_image_u8_warp_augment_nhwc(const uint8_t* src, void* dst, int dtype, int32_t n, int32_t h, int32_t w,
+                                         int32_t c, int32_t dst_stride, const jr_augment_param* params,
+                                         const jr_warp_param* warps, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = aug_check("image_u8_warp_augment", !src || !dst || !params || !warps || !ws, dtype, n, h, w, c,
+                         dst_stride, ws, ws_bytes))
+    return rc;
+  if (n == 0) return JR_OK;
+  hipStream_t s = as_stream(stream);
+  const int P = aug_partials(h, w);
+  // (h w <= 2^28: the tile count stays inside int32)
+  const int tx = (int)ceil_div(w, kWarpTile), tiles = tx * (int)ceil_div(h, kWarpTile);
+  float* part = (float*)ws;
+  hipLaunchKernelGGL(k_warp_sums, dim3(P, n), dim3(256), 0, s, src, params, warps, h, w, part);
+  if (int rc = check_launch("image_u8_warp_augment sums")) return rc;
+  by_dtype(dtype, [&](auto t) {
+    launch_warp_apply<decltype(t)>(src, dst, n, h, w, dst_stride, params, warps, tx, tiles, P, part, s);
+  });
+  return check_launch("image_u8_warp_augment");
 }

@@ -79,7 +79,18 @@ def build_parser():
                         "--bn_calibrate_batches batches of the tfrecords in DIR (for checkpoints trained without "
                         "--bn_moving; in memory, nothing is written)")
     p.add_argument("--bn_calibrate_batches", type=int, default=16, metavar="K")
+    # test-time augmentation (not in the reference, which scores one view of every image)
+    p.add_argument("--tta", default="none", choices=["none", "flips", "d4"],
+                   help="average every member's prediction over views of each test batch, resampled on the GPU: "
+                        "flips (4 views: the two mirrors and both) or d4 (8 views: the quarter turns, plain and "
+                        "mirrored; square images); default none (one view, the reference's)")
     return p
+
+
+def tta_views(tta, height, width):
+    """The (flags, matrix) views of a --tta mode, in the order they are averaged (jr.augment)."""
+    from jr import augment
+    return {"flips": augment.flip_views, "d4": lambda: augment.d4_views(height, width)}[tta]()
 
 
 def expand_model_paths(load_model_path: str):
@@ -162,10 +173,34 @@ def freeze_engines(engines, stats=None, calibrate_dir=None, batches=16, batch_si
     return k
 
 
-def predict_all(engines, data_dir, batch_size, rank=0, world=1, bn="batch"):
+def predict_views(engines, x, y, views, bn="batch"):
+    """[M][n, 1]: every member's prediction of one uint8 batch, averaged over
+    `views` ((flags, matrix) pairs of jr.augment) in their order.  The batch
+    crosses PCIe once; each view re-runs the input kernel from the device
+    copy (jr_image_u8_warp_augment_nhwc), then every member's forward."""
+    import torch
+    from jr import augment
+    grouped = hasattr(engines, "members")
+    every = [engines] if grouped else engines
+    xd = torch.as_tensor(x).to(every[0].device)
+    torch.cuda.current_stream(every[0].device).synchronize()
+    seen = []       # [view][member][n, 1]
+    for view in views:
+        tab, warp = augment.view_tables(view, len(x))
+        n = 0
+        for e in every:
+            n = e.set_batch(xd, y, augment=tab, warp=warp)
+            e.forward(n, bn=bn)
+        seen.append(list(engines.predictions(n)) if grouped else [e.predictions(n) for e in every])
+    return [np.mean(np.array([v[m] for v in seen]), axis=0) for m in range(len(seen[0]))]
+
+
+def predict_all(engines, data_dir, batch_size, rank=0, world=1, bn="batch", tta="none"):
     """Per-member predictions over this rank's batches: ([M][n_r, 1], [n_r, 1],
     batch indices).  Each batch is decoded once (this rank's batches only)
-    and run through every member.  bn: "batch", or "frozen" (freeze_engines)."""
+    and run through every member.  bn: "batch", or "frozen" (freeze_engines).
+    tta: "none", or a mode of tta_views -- a member's prediction is then its
+    mean over those views of the batch (predict_views)."""
     import torch
     grouped = hasattr(engines, "members")      # jr.ensemble.EnsembleEngine
     g = engines.g if grouped else engines[0].g
@@ -175,12 +210,17 @@ def predict_all(engines, data_dir, batch_size, rank=0, world=1, bn="batch"):
         image_dim=[g.height, g.width], decode_dtype="uint8",
         shard=(rank, world))
     preds = [[] for _ in range(engines.members if grouped else len(engines))]
+    views = None if tta == "none" else tta_views(tta, g.height, g.width)
     got_y, ids = [], []
     it = iter(dataset)
     try:
         for k, (x, y) in enumerate(it):
             ids.append(k * world + rank)
             got_y.append(y)
+            if views is not None:
+                for m, p in enumerate(predict_views(engines, x, y, views, bn)):
+                    preds[m].append(p)
+                continue
             # every member's forward is enqueued before the first result is
             # read back (one host sync per batch, not per member), while the
             # decoder threads already work on the next batches
@@ -280,6 +320,8 @@ Using operating treshold: {},
 
     thresholds = lib.metrics.generate_thresholds(NUM_THRESHOLDS, KEPSILON) + [operating_threshold]
     meta = checkpoint.read_meta(load_model_paths[0])
+    # (before any engine is built: d4 refuses images that are not square)
+    n_views = len(tta_views(args.tta, meta["height"], meta["width"])) if args.tta != "none" else 1
     conv_math, bn_stats, bn_info = args.conv_math, None, None
     if args.bn == "moving":
         if args.bn_calibrate_dir is None:       # before any engine is built
@@ -299,8 +341,10 @@ Using operating treshold: {},
             print(f"BN statistics: moving (momentum {bn_info['momentum']}, {bn_info['updates']} updates)")
         elif rank == 0:
             print(f"BN statistics: moving (calibrated on {k} batches of {args.bn_calibrate_dir})")
+    if args.tta != "none" and rank == 0:
+        print(f"Test-time augmentation: {args.tta} ({n_views} views)")
     preds, labels, order = predict_all(engines, data_dir, batch_size, rank, world,
-                                       bn="frozen" if args.bn == "moving" else "batch")
+                                       bn="frozen" if args.bn == "moving" else "batch", tta=args.tta)
 
     if dist:   # gather every rank's batches to rank 0, restore dataset order
         gathered = [None] * world

@@ -105,6 +105,11 @@ class AugmentParam(Structure):
                 ("brightness_delta", c_float), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
+class WarpParam(Structure):
+    """include/jr.h jr_warp_param: one image's affine resampling (jr.augment builds the tables)."""
+    _fields_ = [("m", c_float * 6), ("reserved", ctypes.c_uint32 * 2)]
+
+
 class PoolDesc(Structure):
     _fields_ = [(n, c_int32) for n in (
         "n", "h", "w", "c", "ho", "wo", "x_c_off", "x_c_stride", "y_c_off", "y_c_stride")]
@@ -224,6 +229,8 @@ _SIGS = {
     "jr_augment_workspace_size": (c_size_t, [c_int32, c_int32, c_int32]),
     "jr_image_u8_augment_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int32, c_int32, c_int32, c_int32, c_int32,
                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "jr_image_u8_warp_augment_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "jr_brier_accumulate": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "jr_crc32c": (ctypes.c_uint32, [c_void_p, c_size_t, ctypes.c_uint32]),
     "jr_masked_crc32c": (ctypes.c_uint32, [c_void_p, c_size_t]),

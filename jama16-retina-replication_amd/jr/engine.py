@@ -149,6 +149,7 @@ class Replica:
         for n in self.g.nodes:
             slices.setdefault(n.y.buf, set()).add(n.y.c_off)
         self.slices = {b: sorted(o) for b, o in slices.items()}
+        self._aug_ws = None             # the augmented upload's workspace and tables, at first use
 
     def _t(self, n: int, dtype=torch.float32) -> torch.Tensor:
         return torch.zeros(int(n), dtype=dtype, device=self.device)
@@ -234,12 +235,42 @@ class Replica:
             d.w_absmax = self._wmax(u)
         return d
 
-    def _upload(self, images, labels, B: int) -> None:
-        """A batch (NHWC float32, or uint8 to be scaled by 1/255) into the
-        first member's input buffer and the labels, on self.stream."""
+    def _upload(self, images, labels, B: int, augment=None, warp=None) -> None:
+        """A batch (NHWC float32, or uint8 to be scaled by 1/255; a host array
+        or a device tensor) into the first member's input buffer and the
+        labels, on self.stream.  augment / warp: jr.augment tables (one
+        jr_augment_param / jr_warp_param per image) for a uint8 batch --
+        augment alone goes through jr_image_u8_augment_nhwc, a warp through
+        jr_image_u8_warp_augment_nhwc (with the identity colour table when
+        augment is None)."""
         ib = self.g.bufs[self.g.input_buf]
         x, pixels, dst = torch.as_tensor(images), B * ib.h * ib.w, self.acts[self.g.input_buf]
-        if x.dtype == torch.uint8:
+        if augment is not None or warp is not None:
+            if x.dtype != torch.uint8:
+                raise ValueError("augment / warp need a uint8 batch (float batches are not augmented)")
+            from . import augment as _augment
+            tab = _augment.identity(B) if augment is None else _augment.as_table(augment, B)
+            wtab = None if warp is None else _augment.as_warp_table(warp, B)
+            if self._aug_ws is None:   # once: sized for the planned batch
+                nbytes = int(self.lib.jr_augment_workspace_size(self.batch, ib.h, ib.w))
+                self._aug_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                self._aug_tab = torch.empty(self.batch * tab.dtype.itemsize, dtype=torch.uint8, device=self.device)
+                self._warp_tab = torch.empty(self.batch * _augment.WARP_DTYPE.itemsize, dtype=torch.uint8,
+                                             device=self.device)
+            self._aug_tab[:tab.nbytes].copy_(torch.from_numpy(tab.view(np.uint8)), non_blocking=True)
+            xd = x.to(self.device, non_blocking=True).reshape(-1)
+            if wtab is None:
+                _ffi.check("jr_image_u8_augment_nhwc", self.lib.jr_image_u8_augment_nhwc(
+                    xd.data_ptr(), dst.data_ptr(), self.dt, B, ib.h, ib.w, ib.c, self.in_stride,
+                    self._aug_tab.data_ptr(), self._aug_ws.data_ptr(), self._aug_ws.numel(), self._s))
+            else:
+                self._warp_tab[:wtab.nbytes].copy_(torch.from_numpy(wtab.view(np.uint8)), non_blocking=True)
+                _ffi.check("jr_image_u8_warp_augment_nhwc", self.lib.jr_image_u8_warp_augment_nhwc(
+                    xd.data_ptr(), dst.data_ptr(), self.dt, B, ib.h, ib.w, ib.c, self.in_stride,
+                    self._aug_tab.data_ptr(), self._warp_tab.data_ptr(), self._aug_ws.data_ptr(),
+                    self._aug_ws.numel(), self._s))
+            self._keep_u8 = xd
+        elif x.dtype == torch.uint8:
             xd = x.to(self.device, non_blocking=True).reshape(-1)
             _ffi.check("jr_image_u8_to_nhwc", self.lib.jr_image_u8_to_nhwc(
                 xd.data_ptr(), dst.data_ptr(), self.dt, pixels, ib.c, self.in_stride, self._s))
@@ -489,7 +520,6 @@ class Engine(Replica):
         self._flush_points: List[int] = []
         self._graphs: Dict[int, int] = {}
         self.bucket_hooks: List[Tuple[int, Callable]] = []
-        self._aug_ws = None
         self._alloc()
         self.load_params(init_params(self.g, seed))
         self._choose_tiles("autotune" if autotune else tiles)
@@ -1238,34 +1268,16 @@ class Engine(Replica):
         self.lanes.fence(stream)
 
     # ------------------------------------------------------------------- data
-    def set_batch(self, images, labels=None, n: Optional[int] = None, augment=None) -> int:
+    def set_batch(self, images, labels=None, n: Optional[int] = None, augment=None, warp=None) -> int:
         """Copy a batch (NHWC float32, or uint8 to be scaled by 1/255) into the
-        input buffer.  Returns the batch size.  augment: a jr.augment table
-        (one jr_augment_param per image) -- the uint8 batch then goes through
-        jr_image_u8_augment_nhwc (training only; None: no augmentation)."""
+        input buffer.  Returns the batch size.  augment, warp: jr.augment
+        tables (one jr_augment_param / jr_warp_param per image) -- the uint8
+        batch then goes through jr_image_u8_augment_nhwc or, with a warp,
+        jr_image_u8_warp_augment_nhwc (None, None: no augmentation)."""
         B = int(images.shape[0]) if n is None else n
         self._check_images(images, B)
-        ib = self.g.bufs[self.g.input_buf]
         with torch.cuda.stream(self.stream):
-            if augment is None:
-                self._upload(images, labels, B)
-            else:
-                x = torch.as_tensor(images)
-                if x.dtype != torch.uint8:
-                    raise ValueError("augment needs a uint8 batch (float batches are not augmented)")
-                from . import augment as _augment
-                tab = _augment.as_table(augment, B)
-                if self._aug_ws is None:   # once: sized for the planned batch
-                    nbytes = int(self.lib.jr_augment_workspace_size(self.batch, ib.h, ib.w))
-                    self._aug_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                    self._aug_tab = torch.empty(self.batch * tab.dtype.itemsize, dtype=torch.uint8, device=self.device)
-                self._aug_tab[:tab.nbytes].copy_(torch.from_numpy(tab.view(np.uint8)), non_blocking=True)
-                xd = x.to(self.device, non_blocking=True).reshape(-1)
-                _ffi.check("jr_image_u8_augment_nhwc", self.lib.jr_image_u8_augment_nhwc(
-                    xd.data_ptr(), self.acts[self.g.input_buf].data_ptr(), self.dt, B, ib.h, ib.w, ib.c,
-                    self.in_stride, self._aug_tab.data_ptr(), self._aug_ws.data_ptr(), self._aug_ws.numel(), self._s))
-                self._keep_u8 = xd
-                self._set_labels(labels, B)
+            self._upload(images, labels, B, augment, warp)
         return B
 
     # ------------------------------------------------------------------- runs

@@ -232,12 +232,14 @@ class EnsembleEngine(Replica):
                   [("feat",)], [("head",)])
 
     # ------------------------------------------------------------------- runs
-    def set_batch(self, images, labels=None) -> int:
-        """One batch for every member (NHWC uint8 or float32, host or device)."""
+    def set_batch(self, images, labels=None, augment=None, warp=None) -> int:
+        """One batch for every member (NHWC uint8 or float32, host or device).
+        augment, warp: jr.augment tables for a uint8 batch (jr.Engine.set_batch)
+        -- one view of test-time augmentation."""
         B = int(images.shape[0])
         self._check_images(images, B)
         with torch.cuda.stream(self.stream):
-            self._upload(images, labels, B)
+            self._upload(images, labels, B, augment, warp)
             # every member reads the same images: copy member 0's
             ib, dst = self.g.bufs[self.g.input_buf], self.acts[self.g.input_buf]
             n, k = self.act_ms[self.g.input_buf], B * ib.h * ib.w * self.in_stride

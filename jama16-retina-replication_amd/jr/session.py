@@ -92,10 +92,10 @@ class Session:
         self.engine.forward(B)
         return self.engine.predictions(B)
 
-    def train_batch(self, images, labels, augment=None) -> tuple:
+    def train_batch(self, images, labels, augment=None, warp=None) -> tuple:
         """train.py:231-232: one step; returns (global_step, xent, probs).
-        augment: a jr.augment table for this (uint8) batch, or None."""
-        B = self.engine.set_batch(images, labels, augment=augment)
+        augment, warp: jr.augment tables for this (uint8) batch, or None."""
+        B = self.engine.set_batch(images, labels, augment=augment, warp=warp)
         step = self.global_step
         self.engine.train_step(B, allreduce=getattr(self, "allreduce", None))
         self.global_step += 1

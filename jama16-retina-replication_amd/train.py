@@ -48,8 +48,22 @@ KEPSILON = 1e-7
 SHUFFLE_BUFFER_SIZE = 2048
 
 
+GEOMETRY_FLAGS = ("augment_rotate", "augment_zoom", "augment_shift")
+
+
+class _Parser(argparse.ArgumentParser):
+    """The geometric augmentation flags are refinements of --augment: one of them without it is an error."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        given = [f for f in GEOMETRY_FLAGS if getattr(ns, f) is not None]
+        if given and not ns.augment:
+            self.error("--{} needs --augment".format(given[0]))
+        return ns
+
+
 def build_parser():
-    p = argparse.ArgumentParser(
+    p = _Parser(
         description="Trains and saves neural network for detection of diabetic retinopathy.")
     p.add_argument("-t", "--train_dir", default=DEFAULT_TRAIN_DIR,
                    help="path to folder that contains training tfrecords")
@@ -103,6 +117,14 @@ def build_parser():
     p.add_argument("--augment_brightness", type=float, default=None,
                    help="brightness shift range +-B of the [0, 1] pixel range (default 0.125)")
     p.add_argument("--no_augment_flip", action="store_true", help="no random left-right / up-down flips")
+    # geometric augmentation (with --augment; each off by default): a per-image rotation, zoom and shift,
+    # resampled bilinearly on the GPU, pixels from outside the source black
+    p.add_argument("--augment_rotate", type=float, default=None, metavar="DEG",
+                   help="rotate every training image by a random angle in +-DEG degrees")
+    p.add_argument("--augment_zoom", type=_range_arg, default=None, metavar="LO,HI",
+                   help="magnify every training image by a random factor in LO,HI")
+    p.add_argument("--augment_shift", type=float, default=None, metavar="FRAC",
+                   help="shift every training image by random fractions in +-FRAC of its width and height")
     # moving averages of the BN statistics (not updated by the reference's graph: off by default)
     p.add_argument("--bn_moving", type=float, nargs="?", const=0.99, default=None, metavar="MOMENTUM",
                    help="keep Keras-style moving averages of the BN batch statistics (momentum 0.99 when given "
@@ -132,6 +154,16 @@ def augment_spec(args):
         if v is not None:
             over[key] = v
     return AugmentSpec(**over)
+
+
+def warp_spec(args):
+    """The jr.augment.WarpSpec of the --augment_rotate / _zoom / _shift flags
+    (None: none of them is given); an omitted one takes its identity value."""
+    if not args.augment or all(getattr(args, f) is None for f in GEOMETRY_FLAGS):
+        return None
+    from jr.augment import WarpSpec
+    return WarpSpec(rotate=args.augment_rotate or 0.0, zoom=args.augment_zoom or (1.0, 1.0),
+                    shift=args.augment_shift or 0.0)
 
 
 def status_line(epoch, num_epochs, batch_num, xent, i_step=None):
@@ -248,6 +280,12 @@ Use SGD: {bool(args.vanilla_sgd)}
     aug_spec = augment_spec(args)
     aug_rng = np.random.Generator(np.random.PCG64([args.augment_seed, rank])) if aug_spec else None
     aug_meta = {"augment": {"spec": aug_spec.to_meta(), "seed": args.augment_seed}} if aug_spec else {}
+    # the geometry draws from a generator of its own: the colour draws of a seed
+    # are the same with and without it
+    geo_spec = warp_spec(args)
+    geo_rng = np.random.Generator(np.random.PCG64([args.augment_seed, rank, 1])) if geo_spec else None
+    if geo_spec:
+        aug_meta["augment_warp"] = {"spec": geo_spec.to_meta(), "seed": args.augment_seed}
     if dist:
         from jr.dist import BucketAllReduce
         sess.allreduce = BucketAllReduce(engine, world)
@@ -303,8 +341,9 @@ Use SGD: {bool(args.vanilla_sgd)}
                     break
                 if aug_spec is not None:
                     from jr import augment
+                    warp = augment.draw_warp(geo_spec, geo_rng, len(images), *size) if geo_spec else None
                     i_global, xent, probs = sess.train_batch(images, labels,
-                                                             augment.draw(aug_spec, aug_rng, len(images)))
+                                                             augment.draw(aug_spec, aug_rng, len(images)), warp)
                 else:
                     i_global, xent, probs = sess.train_batch(images, labels)
                 sess.update(labels, probs, "brier")
