@@ -342,6 +342,19 @@ int jr_bn_relu_bwd_multi(int dtype, int nseg, const jr_bn_seg* segs, const void*
 int jr_bn_relu_bwd_multi_absmax(int dtype, int nseg, const jr_bn_seg* segs, const void* x, int32_t x_c_off,
                                 int32_t x_c_stride, int64_t m, int32_t c, const float* mean, const float* invstd,
                                 void* dx, void* ws, size_t ws_bytes, float* dx_absmax, void* stream);
+/* The backward under FROZEN statistics (a forward that normalised with fixed
+ * mean / invstd: BN is then affine in x and nothing is differentiated through
+ * the statistics).  Segments, slices and the dx geometry are those of
+ * jr_bn_relu_bwd_multi; a segment's dbeta is ignored and may be NULL.  No
+ * workspace, one launch.  Per element, with pre the pre-activation exactly as
+ * jr_bn_relu_apply forms it from x, mean, invstd, beta (one shared device
+ * function: the gate is the forward's bit for bit):
+ *   g  = pre > 0 ? f32(dy) : 0      (a select: NaN / inf dy under a closed gate give 0)
+ *   dx = T(g * invstd)              (one fp32 multiply; JR_BF16: rounded to nearest-even)
+ * dtype: JR_F32 or JR_BF16, anything else JR_ERR_INVALID as jr_bn_relu_apply. */
+int jr_bn_relu_bwd_frozen(int dtype, int nseg, const jr_bn_seg* segs, const void* x, int32_t x_c_off,
+                          int32_t x_c_stride, int64_t m, int32_t c, const float* mean, const float* invstd, void* dx,
+                          void* stream);
 /* Up to 8 independent conv2d_bn backwards (the branch-final layers of one
  * Inception block, whose upstream gradients become final together) in ONE
  * set of three launches; layer l is exactly the jr_bn_relu_bwd_multi call
@@ -420,6 +433,12 @@ int jr_head_fwd(int mode, const float* feat, const float* w, const float* b, con
                 void* stream);
 int jr_head_bwd(int mode, const float* feat, const float* w, const float* probs, const float* labels,
                 int32_t n, int32_t c, int32_t units, float* dfeat, float* dw, float* db, void* stream);
+/* The gradient of ONE logit per sample with respect to its features (no loss,
+ * no probabilities, no 1/n): dfeat[i][k] = w[k][t_i], t_i = target ? target[i]
+ * : 0.  A t_i outside [0, units) writes a row of zeros; no address is formed
+ * from it.  w: the dense kernel [c][units]. */
+int jr_head_logit_bwd(const float* w, const int32_t* target, int32_t n, int32_t c, int32_t units, float* dfeat,
+                      void* stream);
 
 /* ---- optimizers (train.py:147-153: GradientDescentOptimizer /
  *      MomentumOptimizer(use_nesterov=True) -> TF ApplyMomentum) ------- */
@@ -612,6 +631,42 @@ int jr_image_u8_warp_augment_nhwc(const uint8_t* src, void* dst, int dtype, int3
 /* acc[0] += sum (p - y)^2, acc[1] += n   (tf.metrics.mean_squared_error,
  * train.py:175-177) */
 int jr_brier_accumulate(const float* probs, const float* labels, int32_t n, double* acc, void* stream);
+
+/* ---- attribution: per-image input gradients under frozen BN ------------
+ * (jr/attribution.py; not in the reference).  Every multiply and add named
+ * below is an fp32 operation rounded on its own (no fused multiply-add), so
+ * a float32 restatement reproduces the results bit for bit. */
+/* The data gradient of a convolution whose c_in <= 4 (the image layer, which
+ * jr_conv2d_bwd_data refuses).  dy: the raw-output gradient in the
+ * descriptor's y slice, fp32 (JR_F32) or bf16 (JR_BF16) -- the storage dtypes
+ * only, anything else JR_ERR_INVALID; y_c_off and y_c_stride multiples of 4
+ * fp32 / 8 bf16 channels.  w: the fp32 HWIO master filter, whatever dtype.
+ * dx: fp32 [n][h][w][dx_c_stride], dx_c_stride >= c_in; channels [c_in,
+ * dx_c_stride) are written as 0 and EVERY pixel is written (0 where no output
+ * covers it).  The descriptor's x slice fields are not read.
+ * Pixel (iy, ix), channel ci: the valid taps are the (r, s) with iy + pad_h -
+ * r >= 0, divisible by stride_h, quotient oy < ho (and the same in x); per
+ * tap p(r,s) = 0.0f, then for co = 0 .. c_out-1 ascending p = p + f32(dy[n,
+ * oy,ox,co]) * w[r,s,ci,co]; dx = (((0.0f + p(first)) + p(next)) + ...) over
+ * the valid taps in (r, s) ascending order.  No address is formed from an
+ * invalid (oy, ox).
+ * JR_ERR_UNSUPPORTED: c_in > 4, kh or kw > 7, a stride other than 1 or 2,
+ * c_out % 16 != 0, or a filter that with the dy patch of 8x8 pixels exceeds
+ * 48 KiB of LDS (c_out in the hundreds). */
+int jr_conv2d_bwd_image(const jr_conv_desc* d, int dtype, const void* dy, const float* w, float* dx,
+                        int32_t dx_c_stride, void* stream);
+/* dst[i] = T(f32(src[i]) * alpha), i < n (T: JR_F32 or JR_BF16; in place allowed) */
+int jr_attr_scale_input(int dtype, const void* src, void* dst, int64_t n, float alpha, void* stream);
+/* acc[i] = (first ? 0.0f : acc[i]) + dx[i] * weight */
+int jr_attr_accumulate(const float* dx, float* acc, int64_t n, float weight, int first, void* stream);
+/* One value per pixel from its c = 3 (else JR_ERR_UNSUPPORTED) channels of acc
+ * (fp32, acc_c_stride apart):
+ *   JR_ATTR_ABSMAX:     map = max_c |acc_c|                      (x may be NULL)
+ *   JR_ATTR_DOT_INPUT:  map = ((acc_0 x_0 + acc_1 x_1) + acc_2 x_2), x of dtype
+ *                       JR_F32 / JR_BF16 widened to fp32, x_c_stride apart */
+typedef enum jr_attr_mode { JR_ATTR_ABSMAX = 0, JR_ATTR_DOT_INPUT = 1 } jr_attr_mode;
+int jr_attr_map(int mode, const float* acc, int32_t acc_c_stride, const void* x, int dtype, int32_t x_c_stride,
+                int64_t pixels, int32_t c, float* map, void* stream);
 
 /* ---- host (CPU) helpers: TFRecord container and Example records ----- */
 uint32_t jr_crc32c(const uint8_t* data, size_t n, uint32_t crc);

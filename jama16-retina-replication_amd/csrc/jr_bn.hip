@@ -532,6 +532,60 @@ __global__ void __launch_bounds__(256) k_bn_relu_bwd_apply(BnSegs sg, const T* _
   if (sg.absmax) block_absmax_to(amax, sg.absmax);   // (uniform: a kernel argument)
 }
 
+// The backward under FROZEN statistics (jr_bn_relu_bwd_frozen): mean and
+// invstd are constants, so BN is affine and its backward one elementwise
+// pass, dx = T(g * invstd) with g = dy where the forward's pre-activation
+// (bn_pre: k_bn_relu_apply's expression, so the mask is the forward's bit for
+// bit) is positive, else 0 -- a select, whatever dy holds.  Thread layout and
+// loads as k_bn_relu_bwd_apply.
+template <typename T>
+__global__ void __launch_bounds__(256) k_bn_relu_bwd_frozen(BnSegs sg, const T* __restrict__ x, int xs, int64_t m,
+                                                            int c, const float* __restrict__ mean,
+                                                            const float* __restrict__ invstd, T* dx) {
+  constexpr int VW = Vec<T>::N;
+  const int tpr = c / VW;
+  const int rpp = 256 / tpr;
+  const int t = threadIdx.x;
+  const int q = t % tpr, rr = t / tpr;
+  if (rr >= rpp) return;
+  const int sgi = seg_of(sg, q * VW), lc = q * VW - sg.c0[sgi];
+  const T* dy = static_cast<const T*>(sg.dy[sgi]) + sg.dy_off[sgi] + lc;
+  const int dy_stride = sg.dy_stride[sgi];
+  float mu[VW], is[VW], be[VW];
+#pragma unroll
+  for (int j = 0; j < VW; ++j) {
+    const int k = q * VW + j;
+    mu[j] = mean[k]; is[j] = invstd[k]; be[j] = sg.beta[sgi][lc + j];
+  }
+  const int64_t r0 = (int64_t)blockIdx.x * rpp * kAppUnroll + rr;
+  uint4 xr[kAppUnroll], gr[kAppUnroll];
+#pragma unroll
+  for (int u = 0; u < kAppUnroll; ++u) {
+    const int64_t r = min(r0 + (int64_t)u * rpp, m - 1);
+    xr[u] = *reinterpret_cast<const uint4*>(x + r * xs + q * VW);
+    gr[u] = *reinterpret_cast<const uint4*>(dy + r * dy_stride);
+  }
+#pragma unroll
+  for (int u = 0; u < kAppUnroll; ++u) {
+    pin(xr[u]);
+    pin(gr[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < kAppUnroll; ++u) {
+    const int64_t r = r0 + (int64_t)u * rpp;
+    if (r >= m) break;
+    float xv[VW], gv[VW], o[VW];
+    Vec<T>::unpack(xr[u], xv);
+    Vec<T>::unpack(gr[u], gv);
+#pragma unroll
+    for (int j = 0; j < VW; ++j) {
+      const float g = bn_pre(xv[j], mu[j], is[j], be[j]) > 0.f ? gv[j] : 0.f;
+      o[j] = __fmul_rn(g, is[j]);
+    }
+    Vec<T>::st(dx + r * xs + q * VW, o);
+  }
+}
+
 // Canonical combine of ONE channel's backward-reduce partials when there are
 // at most kFoldMaxP of them (fp64 (sum dy', sum dy' xhat) per chunk): an
 // aligned group of 8 lanes, lane j summing chunks j, j+8, ... in order, then
@@ -896,6 +950,22 @@ JR_API int jr_bn_relu_bwd_multi_absmax(int dtype, int nseg, const jr_bn_seg* seg
   if (rc) return rc;
   sg.absmax = dx_absmax;
   return bn_bwd_launch(dtype, sg, x, x_c_stride, m, c, mean, invstd, dx, ws, ws_bytes, as_stream(stream));
+}
+
+JR_API int jr_bn_relu_bwd_frozen(int dtype, int nseg, const jr_bn_seg* segs, const void* x, int32_t x_c_off,
+                                 int32_t x_c_stride, int64_t m, int32_t c, const float* mean, const float* invstd,
+                                 void* dx, void* stream) {
+  BnSegs sg;
+  const int rc = bwd_setup(dtype, nseg, segs, x, x_c_off, x_c_stride, m, c, mean, invstd, dx, sg, false);
+  if (rc) return rc;
+  const dim3 grid(bn_plan(dtype, m, c).apply_grid);
+  hipStream_t s = as_stream(stream);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_bn_relu_bwd_frozen<T>, grid, dim3(256), 0, s, sg, (const T*)x, x_c_stride, m, c, mean, invstd,
+                       (T*)dx);
+  });
+  return check_launch("bn_relu_bwd_frozen");
 }
 
 JR_API int jr_bn_relu_bwd_batch(int dtype, int32_t n, const jr_bn_bwd_layer* layers, void* ws, size_t ws_bytes,

@@ -150,14 +150,15 @@ int apply_segs(int dtype, int nseg, const jr_bn_apply_seg* segs, int c, ApplySeg
   return JR_OK;
 }
 
-int bwd_segs(int dtype, int nseg, const jr_bn_seg* segs, int c, BnSegs& sg) {
+int bwd_segs(int dtype, int nseg, const jr_bn_seg* segs, int c, BnSegs& sg, bool need_dbeta) {
   static const SegMsgs msg = {
       "bn_relu_bwd: null pointer in a segment",
       "bn_relu_bwd: segment channels must be a positive multiple of 4 (fp32) / 8 (bf16)", "bn_relu_bwd: bad dy slice",
       "bn_relu_bwd: segment channels must sum to c"};
   SegView v[kMaxSegs];
   for (int i = 0; i < nseg; ++i)
-    v[i] = {segs[i].dy && segs[i].beta && segs[i].dbeta, segs[i].dy_c_off, segs[i].dy_c_stride, segs[i].c};
+    v[i] = {segs[i].dy && segs[i].beta && (segs[i].dbeta || !need_dbeta), segs[i].dy_c_off, segs[i].dy_c_stride,
+            segs[i].c};
   sg = BnSegs{};
   sg.n = nseg;
   const int rc = check_segs(dtype, nseg, v, c, msg, sg.c0);
@@ -173,13 +174,14 @@ int bwd_segs(int dtype, int nseg, const jr_bn_seg* segs, int c, BnSegs& sg) {
 }
 
 int bwd_setup(int dtype, int nseg, const jr_bn_seg* segs, const void*& x, int32_t x_c_off, int32_t x_c_stride,
-              int64_t m, int32_t c, const float* mean, const float* invstd, void*& dx, BnSegs& sg) {
+              int64_t m, int32_t c, const float* mean, const float* invstd, void*& dx, BnSegs& sg,
+              bool need_dbeta) {
   int rc = check_common(dtype, m, c);
   if (rc) return rc;
   if (!segs || nseg < 1 || nseg > kMaxSegs) return fail(JR_ERR_INVALID, "bn_relu_bwd: 1..4 segments");
   if (!x || !mean || !invstd || !dx) return fail(JR_ERR_INVALID, "bn_relu_bwd: null pointer");
   if (!check_slice(dtype, x_c_off, x_c_stride, c)) return fail(JR_ERR_INVALID, "bn_relu_bwd: bad x / dx slice");
-  rc = bwd_segs(dtype, nseg, segs, c, sg);
+  rc = bwd_segs(dtype, nseg, segs, c, sg, need_dbeta);
   if (rc) return rc;
   x = static_cast<const char*>(x) + (size_t)x_c_off * elt_size(dtype);
   dx = static_cast<char*>(dx) + (size_t)x_c_off * elt_size(dtype);

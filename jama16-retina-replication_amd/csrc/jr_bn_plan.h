@@ -110,11 +110,13 @@ bool fold_bwd();
 // (pointers, channel counts, slices, channels summing to c) and fills the
 // kernel's table.  nseg is 1..kMaxSegs (the callers check it first).
 int apply_segs(int dtype, int nseg, const jr_bn_apply_seg* segs, int c, ApplySegs& sg);
-int bwd_segs(int dtype, int nseg, const jr_bn_seg* segs, int c, BnSegs& sg);
+int bwd_segs(int dtype, int nseg, const jr_bn_seg* segs, int c, BnSegs& sg, bool need_dbeta = true);
 // Validates the segments and slices of a backward launch set; on success
-// fills sg and moves x / dx to the slice's first channel.
+// fills sg and moves x / dx to the slice's first channel.  need_dbeta = false
+// (jr_bn_relu_bwd_frozen, which writes none): a segment's dbeta may be NULL.
 int bwd_setup(int dtype, int nseg, const jr_bn_seg* segs, const void*& x, int32_t x_c_off, int32_t x_c_stride,
-              int64_t m, int32_t c, const float* mean, const float* invstd, void*& dx, BnSegs& sg);
+              int64_t m, int32_t c, const float* mean, const float* invstd, void*& dx, BnSegs& sg,
+              bool need_dbeta = true);
 
 // A batched backward: validates every layer (each as bwd_setup, at most
 // kFoldMaxP chunks) and the workspace, lays the layers' partials out in ws

@@ -135,9 +135,29 @@ __global__ void k_head_dw(int mode, const float* __restrict__ feat, const float*
   }
 }
 
+// dfeat[b][k] = W[k][t_b]: the gradient of logit t_b of sample b (no loss, no
+// 1/n); a target outside [0, units) gives a row of zeros and forms no address
+__global__ void k_head_logit_bwd(const float* __restrict__ w, const int32_t* __restrict__ target, int n, int c,
+                                 int units, float* dfeat) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)n * c) return;
+  const int b = (int)(e / c), k = (int)(e - (int64_t)b * c);
+  const int t = target ? target[b] : 0;
+  dfeat[e] = (t >= 0 && t < units) ? w[(int64_t)k * units + t] : 0.f;
+}
+
 }  // namespace jr
 
 using namespace jr;
+
+JR_API int jr_head_logit_bwd(const float* w, const int32_t* target, int32_t n, int32_t c, int32_t units, float* dfeat,
+                             void* stream) {
+  if (!w || !dfeat) return fail(JR_ERR_INVALID, "head_logit_bwd: null pointer");
+  if (n <= 0 || c <= 0 || units <= 0 || units > kMaxUnits) return fail(JR_ERR_INVALID, "head_logit_bwd: bad sizes");
+  hipLaunchKernelGGL(k_head_logit_bwd, dim3((int)ceil_div((int64_t)n * c, 256)), dim3(256), 0, as_stream(stream), w,
+                     target, n, c, units, dfeat);
+  return check_launch("head_logit_bwd");
+}
 
 JR_API int jr_head_fwd(int mode, const float* feat, const float* w, const float* b, const float* labels,
                        int32_t n, int32_t c, int32_t units, float* logits, float* probs, float* loss,

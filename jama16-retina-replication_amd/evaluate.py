@@ -14,6 +14,12 @@ member is resident on the GPU at once (one engine each: parameters plus
 batch-32 buffers, a few GB per member against 288 GB of HBM), and each test
 batch is decoded once and run through all members -- the same batches, so
 the same batch-statistics BN (App. C Q1) and the same predictions.
+
+Not in the reference: --bn moving (frozen BN), --tta, and --attribution
+{gradient,integrated} --attribution_dir DIR, which under --bn moving also
+writes per-image saliency maps of the logit (jr.attribution): DIR/maps_<k>.npy
+per test batch k (float32 [n, h, w], the mean over members) and DIR/index.csv
+(batch,row,label,prediction); stdout and the CSV stay byte-equal.
 """
 import argparse
 import csv
@@ -44,8 +50,26 @@ NUM_THRESHOLDS = 200
 KEPSILON = 1e-7
 
 
+class _Parser(argparse.ArgumentParser):
+    """The flag combinations that are refused, at parse time (no GPU involved)."""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if a.attribution is not None:
+            if a.bn != "moving":
+                self.error("--attribution requires --bn moving: only under frozen BN statistics is the gradient of "
+                           "an image's logit a property of that image (with batch statistics it leaks into the batch)")
+            if a.tta != "none":
+                self.error("--attribution refuses --tta other than none: a map belongs to one view of the image")
+            if a.attribution_dir is None:
+                self.error("--attribution requires --attribution_dir DIR")
+            if a.attribution_steps < 1:
+                self.error("--attribution_steps must be at least 1")
+        return a
+
+
 def build_parser():
-    p = argparse.ArgumentParser(
+    p = _Parser(
         description="Evaluate performance of trained graph on test data set. "
                     "Specify --data_dir if you use the -o param.")
     p.add_argument("-m", "--messidor", action="store_true", help="evaluate performance on Messidor-Original")
@@ -84,6 +108,15 @@ def build_parser():
                    help="average every member's prediction over views of each test batch, resampled on the GPU: "
                         "flips (4 views: the two mirrors and both) or d4 (8 views: the quarter turns, plain and "
                         "mirrored; square images); default none (one view, the reference's)")
+    # per-image saliency maps (not in the reference)
+    p.add_argument("--attribution", default=None, choices=["gradient", "integrated"],
+                   help="with --bn moving: write per-image saliency maps of the logit (jr.attribution) -- gradient "
+                        "(max over channels of |d logit / d pixel|) or integrated (integrated gradients from the "
+                        "black image); one engine per member, the map is the mean over members")
+    p.add_argument("--attribution_dir", default=None, metavar="DIR",
+                   help="where --attribution writes maps_<batch>.npy (float32 [n, h, w]) and index.csv")
+    p.add_argument("--attribution_steps", type=int, default=16, metavar="M",
+                   help="integration steps of --attribution integrated (midpoint rule; default 16)")
     return p
 
 
@@ -107,12 +140,13 @@ def expand_model_paths(load_model_path: str):
     return [load_model_path]
 
 
-def make_engines(paths, meta, batch_size, device=0, conv_math="x6h", dtype="f32", grouped=False):
+def make_engines(paths, meta, batch_size, device=0, conv_math="x6h", dtype="f32", grouped=False, input_grad=False):
     """The ensemble's inference engines, parameters loaded; conv tiles from
     the committed MI355X table of the eval workload (tiles="pinned"; the
     heuristic where none matches): every member and every run sums in the
     same order.  grouped: ONE jr.ensemble.EnsembleEngine holding every member
-    (one launch per layer for all members); else one jr.Engine per member."""
+    (one launch per layer for all members); else one jr.Engine per member
+    (input_grad: each with the buffers of Engine.input_gradient)."""
     from jr import checkpoint
     from jr.engine import Engine
     if grouped and conv_math != "x8p":
@@ -123,7 +157,8 @@ def make_engines(paths, meta, batch_size, device=0, conv_math="x6h", dtype="f32"
     engines = []
     for path in paths:
         eng = Engine(batch_size, meta["height"], meta["width"], meta.get("units", 1), device=device,
-                     train=False, dtype=dtype, conv_math=conv_math if dtype == "f32" else "bf16")
+                     train=False, dtype=dtype, conv_math=conv_math if dtype == "f32" else "bf16",
+                     input_grad=input_grad)
         flat, _ = checkpoint.load(path, eng.g)
         eng.load_params(flat)
         engines.append(eng)
@@ -195,12 +230,41 @@ def predict_views(engines, x, y, views, bn="batch"):
     return [np.mean(np.array([v[m] for v in seen]), axis=0) for m in range(len(seen[0]))]
 
 
-def predict_all(engines, data_dir, batch_size, rank=0, world=1, bn="batch", tta="none"):
+def member_mean(maps):
+    """The fp32 mean of the members' maps, summed in member order."""
+    s = np.asarray(maps[0], np.float32)
+    for m in maps[1:]:
+        s = s + np.asarray(m, np.float32)
+    return s / np.float32(len(maps))
+
+
+def write_maps(engines, n, k, attribution):
+    """maps_<k>.npy of test batch k (its global index): the member mean of
+    jr.attribution.attribute on the batch every engine holds."""
+    from jr.attribution import attribute
+    maps = [attribute(e, attribution["method"], attribution["steps"], B=n).cpu().numpy() for e in engines]
+    os.makedirs(attribution["dir"], exist_ok=True)
+    np.save(os.path.join(attribution["dir"], f"maps_{k:06d}.npy"), member_mean(maps))
+
+
+def write_index(path, labels, predictions, batch_size):
+    """index.csv: one line per test image in dataset order -- its batch (the
+    k of maps_<k>.npy), its row there, its label and the ensemble prediction."""
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["batch", "row", "label", "prediction"])
+        for i in range(len(labels)):
+            w.writerow([i // batch_size, i % batch_size, int(labels[i, 0]), "{:.9g}".format(float(predictions[i, 0]))])
+
+
+def predict_all(engines, data_dir, batch_size, rank=0, world=1, bn="batch", tta="none", attribution=None):
     """Per-member predictions over this rank's batches: ([M][n_r, 1], [n_r, 1],
     batch indices).  Each batch is decoded once (this rank's batches only)
     and run through every member.  bn: "batch", or "frozen" (freeze_engines).
     tta: "none", or a mode of tta_views -- a member's prediction is then its
-    mean over those views of the batch (predict_views)."""
+    mean over those views of the batch (predict_views).  attribution: None, or
+    {"method", "steps", "dir"} -- after a batch's predictions are read, its
+    saliency maps are written (write_maps; per-member engines, frozen BN)."""
     import torch
     grouped = hasattr(engines, "members")      # jr.ensemble.EnsembleEngine
     g = engines.g if grouped else engines[0].g
@@ -239,6 +303,8 @@ def predict_all(engines, data_dir, batch_size, rank=0, world=1, bn="batch", tta=
                 e.forward(n, bn=bn)
             for m, e in enumerate(engines):
                 preds[m].append(e.predictions(n))
+            if attribution is not None:
+                write_maps(engines, n, ids[-1], attribution)
     finally:
         lib.dataset.close_iterator(it)
     empty = np.zeros((0, 1), np.float32)
@@ -333,8 +399,15 @@ Using operating treshold: {},
             if rank == 0:
                 print("--bn moving: conv_math x8 is used instead of x6h (x6h scales activations by a bound that "
                       "holds only for values standardised by their own batch's statistics)")
+    attribution = None
+    if args.attribution is not None:
+        attribution = {"method": args.attribution, "steps": args.attribution_steps, "dir": str(args.attribution_dir)}
+        if rank == 0:       # (stderr: stdout stays byte-equal to the run without --attribution)
+            print(f"--attribution {args.attribution}: one engine per member (as --per_member), each with input-gradient "
+                  f"buffers; maps to {attribution['dir']}", file=sys.stderr)
     engines = make_engines(load_model_paths, meta, batch_size, device=local, conv_math=conv_math,
-                           dtype=args.dtype, grouped=not args.per_member)
+                           dtype=args.dtype, grouped=not (args.per_member or attribution),
+                           input_grad=attribution is not None)
     if args.bn == "moving":
         k = freeze_engines(engines, bn_stats, args.bn_calibrate_dir, args.bn_calibrate_batches, batch_size)
         if rank == 0 and bn_info is not None:
@@ -344,7 +417,8 @@ Using operating treshold: {},
     if args.tta != "none" and rank == 0:
         print(f"Test-time augmentation: {args.tta} ({n_views} views)")
     preds, labels, order = predict_all(engines, data_dir, batch_size, rank, world,
-                                       bn="frozen" if args.bn == "moving" else "batch", tta=args.tta)
+                                       bn="frozen" if args.bn == "moving" else "batch", tta=args.tta,
+                                       attribution=attribution)
 
     if dist:   # gather every rank's batches to rank 0, restore dataset order
         gathered = [None] * world
@@ -367,6 +441,8 @@ Using operating treshold: {},
     all_predictions = np.array(preds)
     avg_pred = np.mean(all_predictions, axis=0)          # evaluate.py:214-217
     all_y = labels
+    if attribution is not None:
+        write_index(os.path.join(attribution["dir"], "index.csv"), all_y, avg_pred, batch_size)
 
     names = {"tp": lib.metrics.true_positives_at_thresholds, "fp": lib.metrics.false_positives_at_thresholds,
              "fn": lib.metrics.false_negatives_at_thresholds, "tn": lib.metrics.true_negatives_at_thresholds}

@@ -24,6 +24,7 @@ JR_F32_X8P = 3     # conv entry points only: the X8 arithmetic on pre-split h/m/
 JR_F32_X6H = 4     # conv entry points only: fp32 tensors, scaled fp16 three-way split, six f16 MFMAs (jr.h)
 JR_CONV_FWD, JR_CONV_BWD_DATA, JR_CONV_BWD_FILTER = 0, 1, 2
 JR_HEAD_SIGMOID, JR_HEAD_SOFTMAX = 0, 1
+JR_ATTR_ABSMAX, JR_ATTR_DOT_INPUT = 0, 1
 
 
 class JRError(RuntimeError):
@@ -187,6 +188,8 @@ _SIGS = {
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "jr_bn_relu_bwd_multi_absmax": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "jr_bn_relu_bwd_frozen": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "jr_absmax_prep": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "jr_bn_moving_update": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                                     c_float, c_float, c_void_p]),
@@ -215,6 +218,12 @@ _SIGS = {
                             c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jr_head_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                             c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jr_head_logit_bwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "jr_conv2d_bwd_image": (c_int, [POINTER(ConvDesc), c_int, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "jr_attr_scale_input": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_float, c_void_p]),
+    "jr_attr_accumulate": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p]),
+    "jr_attr_map": (c_int, [c_int, c_void_p, c_int32, c_void_p, c_int, c_int32, c_int64, c_int32, c_void_p,
+                            c_void_p]),
     "jr_nesterov_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
                                    c_float, c_void_p]),
     "jr_momentum_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,

@@ -21,6 +21,11 @@ that step, MI355X-native:
   moving averages of every BN layer's batch statistics (jr_bn_moving_update);
   freeze_bn() + forward(bn="frozen") then normalise with fixed statistics, so
   an image's output depends on that image alone.
+* Optional (input_grad=True): a third call list, the data-gradient chain of
+  one logit per image down to the image after a frozen forward
+  (input_gradient: jr_head_logit_bwd, jr_bn_relu_bwd_frozen, the data
+  gradients, jr_conv2d_bwd_image) -- what jr.attribution builds saliency maps
+  from.  No filter gradients, no optimizer, no training buffers.
 * Data parallel: gradients are all-reduced (torch.distributed backend 'nccl' =
   RCCL over xGMI) in buckets issued during the backward pass, in reverse layer
   order, so communication overlaps the remaining backward kernels.
@@ -438,12 +443,18 @@ class Engine(Replica):
                  head: str = "sigmoid", seed: int = 0, graph: Optional[Graph] = None,
                  autotune: bool = False, tiles: str = "pinned", fuse_siblings: bool = True, lanes: int = 2,
                  conv_math: Optional[str] = None, defer_wgrad: Optional[bool] = None, fuse_pool: Optional[bool] = None,
-                 fold_stats: Optional[bool] = None, bn_moving: Optional[float] = None):
+                 fold_stats: Optional[bool] = None, bn_moving: Optional[float] = None, input_grad: bool = False):
         # bn_moving: None, or the momentum of the moving averages of the BN
         # statistics every training step then updates (Keras: 0.99)
         if bn_moving is not None and not 0.0 <= float(bn_moving) <= 1.0:
             raise ValueError("bn_moving: None or a momentum in [0, 1]")
         self.bn_momentum = None if bn_moving is None else float(bn_moving)
+        # input_grad: the buffers of the data-gradient chain down to the image
+        # (input_gradient, jr.attribution), with or without train
+        self.input_grad = bool(input_grad)
+        if self.input_grad and conv_math == "x8p":
+            raise ValueError("input_grad=True is not available with conv_math='x8p': the input-gradient call list "
+                             "does not write its operand planes; use x8, f32 or bf16")
         # JR_LANE_PRIORITY="p0,p1,...": HIP stream priority per lane (lower =
         # higher priority). Default: lane 0 (the trunk) high for fp32 steps,
         # measured 0.1 ms/step faster over 6 interleaved rounds on two boxes
@@ -454,6 +465,8 @@ class Engine(Replica):
                          ("x8", "x8p", "x6h", "f32"), head, fuse_siblings, fuse_pool, lanes,
                          [int(v) for v in prio.split(",") if v.strip()])
         self.batch, self.train_mode = batch, train
+        self._data_grads = train or self.input_grad     # gradient buffers and data-gradient plans exist
+        self._frozen_fwd = None         # batch size of the frozen forward since the last set_batch, if any
         if optimizer not in ("nesterov", "momentum", "sgd", "adam"):
             raise ValueError(f"unknown optimizer {optimizer}")
         self.optimizer = optimizer
@@ -591,6 +604,7 @@ class Engine(Replica):
             self.grads = self._t(self.nparam)
             self.accum = self._t(self.nparam)
             self.adam_v = self._t(self.nparam) if self.optimizer == "adam" else None
+        if self._data_grads:
             self.dacts = [self._t(B * b.h * b.w * b.c, at) if b.id != g.input_buf else None
                           for b in g.bufs]
             # per-lane scratch for the raw-output gradient of the launch in flight
@@ -601,17 +615,25 @@ class Engine(Replica):
             # next stem layer's BN backward must not overwrite what that
             # filter gradient still reads)
             self.draw_stem2 = (self._t(max(B * u.ho * u.wo * u.cout for u in self.cunits), at)
-                               if self.nlanes > 1 and not self.x8p else None)
+                               if self.train_mode and self.nlanes > 1 and not self.x8p else None)
             self.draw = self.draw_lane[0]
             self.dfeat = self._t(B * feat_c)
             # the batched block-output BN backwards' raw gradients live in two
             # alternating sets of per-layer buffers
             self.bn_batch = (bn_batch_groups(g, self.plan, B, self._vw, self.fused_bufs)
-                             if self.bn_batch_on else [])
+                             if self.bn_batch_on and self.train_mode else [])
             slots = max((len(grp) for grp in self.bn_batch), default=0)
             self.drawb = [[self._t(max(B * grp[k].ho * grp[k].wo * grp[k].cout
                                        for grp in self.bn_batch if k < len(grp)), at) for k in range(slots)]
                           for _ in range(2 if slots else 0)]
+        if self.input_grad:
+            ib = g.bufs[g.input_buf]
+            # the image gradient (fp32, 4 channels per pixel: c = 3 and a zero), the
+            # unscaled input kept for scaled passes, the drivers' accumulator, the targets
+            self.dinput = self._t(B * ib.h * ib.w * 4)
+            self.x0 = self._t(B * ib.h * ib.w * self.in_stride, at)
+            self.attr_acc = self._t(B * ib.h * ib.w * 4)
+            self.ig_target = self._t(B, torch.int32)
         if self.dt == _ffi.JR_BF16 or self.x8p:
             self._alloc_bf16_filters(planes=3 if self.x8p else 1)
         if self.x8p:
@@ -620,7 +642,7 @@ class Engine(Replica):
         for u in self.cunits:
             d = self._conv_desc(u, B)
             ops = (_ffi.JR_CONV_FWD, _ffi.JR_CONV_BWD_DATA, _ffi.JR_CONV_BWD_FILTER)
-            for op in (ops if self.train_mode else ops[:1]):
+            for op in (ops if self.train_mode else ops[:2] if self.input_grad else ops[:1]):
                 ws = max(ws, self.lib.jr_conv2d_workspace_size(ctypes.byref(d), op, self.cdt))
             ws = max(ws, self.lib.jr_bn_workspace_size(B * u.ho * u.wo, u.cout))   # one backward per launch (or less)
         for grp in self.bn_batch:                        # one batched BN backward per block
@@ -695,16 +717,15 @@ class Engine(Replica):
                 progress(u.name)
             d = self._conv_desc(u, B)
             x = (self.aplanes[u.x] if self.x8p else self.acts[u.x]).data_ptr()
-            draw = (self.drawp_lane[0] if self.x8p else self.draw).data_ptr() if self.train_mode else 0
+            draw = (self.drawp_lane[0] if self.x8p else self.draw).data_ptr() if self._data_grads else 0
             raw = self.raw_unit[u.first.idx].data_ptr()
             _ffi.check("autotune fwd", L.jr_conv2d_autotune(ctypes.byref(d), _ffi.JR_CONV_FWD, self.cdt, x,
                                                              self._wf(u), raw, ws, wsb, s))
-            if not self.train_mode:
-                continue
-            _ffi.check("autotune wgrad", L.jr_conv2d_autotune(
-                ctypes.byref(d), _ffi.JR_CONV_BWD_FILTER, self.cdt, x, draw,
-                self.grads.data_ptr() + 4 * u.koff, ws, wsb, s))
-            if u.x != self.g.input_buf:
+            if self.train_mode:
+                _ffi.check("autotune wgrad", L.jr_conv2d_autotune(
+                    ctypes.byref(d), _ffi.JR_CONV_BWD_FILTER, self.cdt, x, draw,
+                    self.grads.data_ptr() + 4 * u.koff, ws, wsb, s))
+            if self._data_grads and u.x != self.g.input_buf:
                 _ffi.check("autotune dgrad", L.jr_conv2d_autotune(
                     ctypes.byref(d), _ffi.JR_CONV_BWD_DATA, self.cdt, draw, self._wd(u),
                     self.dacts[u.x].data_ptr(), ws, wsb, s))
@@ -777,11 +798,10 @@ class Engine(Replica):
             f, wg, dg = cfgs[u.name]
             d = self._conv_desc(u, self.batch)
             _ffi.check("set_config", self.lib.jr_conv2d_set_config(ctypes.byref(d), _ffi.JR_CONV_FWD, self.cdt, 0, f))
-            if not self.train_mode:
-                continue
-            _ffi.check("set_config", self.lib.jr_conv2d_set_config(ctypes.byref(d), _ffi.JR_CONV_BWD_FILTER,
-                                                                   self.cdt, 0, wg))
-            if u.x != self.g.input_buf:
+            if self.train_mode:
+                _ffi.check("set_config", self.lib.jr_conv2d_set_config(ctypes.byref(d), _ffi.JR_CONV_BWD_FILTER,
+                                                                       self.cdt, 0, wg))
+            if self._data_grads and u.x != self.g.input_buf:
                 for p, c in enumerate(dg):
                     _ffi.check("set_config", self.lib.jr_conv2d_set_config(ctypes.byref(d), _ffi.JR_CONV_BWD_DATA,
                                                                            self.cdt, p, c))
@@ -799,8 +819,8 @@ class Engine(Replica):
             ops = [(_ffi.JR_CONV_FWD, 0)]
             if self.train_mode:
                 ops.append((_ffi.JR_CONV_BWD_FILTER, 0))
-                if u.x != self.g.input_buf:
-                    ops += [(_ffi.JR_CONV_BWD_DATA, p) for p in range(u.stride * u.stride)]
+            if self._data_grads and u.x != self.g.input_buf:
+                ops += [(_ffi.JR_CONV_BWD_DATA, p) for p in range(u.stride * u.stride)]
             for op, p in ops:
                 _ffi.check("set_config", self.lib.jr_conv2d_set_config(ctypes.byref(d), op, self.cdt, p, -1))
 
@@ -1222,8 +1242,8 @@ class Engine(Replica):
               (ctypes.byref(d), self.cdt, self._AX(u.x), draw, self.grads.data_ptr() + 4 * u.koff, ws, b.wsb, b.S[wl]),
               "conv_wgrad", wl, reads, [("g", uid), wskey])
 
-    def _bwd_pool(self, b: Build, i: int, n: PoolNode) -> None:
-        if i in self.pool_bwd:
+    def _bwd_pool(self, b: Build, i: int, n: PoolNode, plain: bool = False) -> None:
+        if i in self.pool_bwd and not plain:
             return              # with its producer's BN backward (jr_bn_relu_bwd_maxpool)
         L, dt, B, ln = self.lib, self.dt, b.B, b.lane_of[i]
         acc = 1 if n.x in b.written else 0
@@ -1239,6 +1259,104 @@ class Engine(Replica):
                   "avgpool_bwd", ln, [("d", n.y.buf, n.y.c_off)], self._d_all(n.x),
                   nbytes=B * n.c * (n.ho * n.wo + n.h * n.w * (1 + acc)) * self.esz)
         b.written.add(n.x)
+
+    # ---- input gradient (frozen BN)
+    def _build_input_grad(self, B: int, nl: Optional[int] = None) -> list:
+        """The data-gradient chain of ONE logit per image down to the image,
+        after a frozen forward of the same batch: head (jr_head_logit_bwd) and
+        GAP, then in reverse node order the pool backwards and, per conv
+        launch, the frozen BN backward (jr_bn_relu_bwd_frozen, reading the
+        frozen statistics) and the data gradient -- jr_conv2d_bwd_image into
+        self.dinput for the image layer.  Fused stem pools: the plain max-pool
+        backward from the stored argmax, then the frozen BN backward.  No
+        filter gradient, no hook, no optimizer.  Its own key and schedule."""
+        self._ensure_tiles()
+        nl = self.nlanes if nl is None else max(1, min(int(nl), self.nlanes))
+        key = (B, nl, "input_grad")
+        if key in self._calls:
+            return self._calls[key][1]
+        if B > self.batch or B <= 0:
+            raise ValueError(f"batch {B} outside 1..{self.batch}")
+        g, unit_of = self.g, self.plan.unit_of
+        b = Build(B, self.lanes, nl, self.ws_lane, self.ws_bytes, node_lanes(g, self.plan, nl))
+        b.stats_shift = self.frozen.data_ptr() - self.stats.data_ptr()
+        ob, s0 = g.bufs[g.output_buf], b.S[0]
+        b.add(b.bwd, self.lib.jr_head_logit_bwd,
+              (self._p("dense/kernel"), self.ig_target.data_ptr(), B, ob.c, self.units, self.dfeat.data_ptr(), s0),
+              "head_logit_bwd", 0, [("p",), ("target",)], [("dfeat",)])
+        b.add(b.bwd, self.lib.jr_gap_bwd,
+              (self.dt, self.dfeat.data_ptr(), B, ob.h * ob.w, ob.c, self._D(g.output_buf), s0),
+              "gap_bwd", 0, [("dfeat",)], self._d_all(g.output_buf))
+        for i in range(len(g.nodes) - 1, -1, -1):
+            n = g.nodes[i]
+            if n.kind != "conv":
+                self._bwd_pool(b, i, n, plain=True)
+            elif unit_of[n.idx].first is n:
+                self._ig_conv(b, i, unit_of[n.idx])
+        schedule(b.seq)
+        self._calls[key] = (None, b.bwd, None, b.keep, None)
+        return b.bwd
+
+    def _ig_conv(self, b: Build, i: int, u: ConvUnit) -> None:
+        ln, uid, M = b.lane_of[i], u.first.idx, b.B * u.ho * u.wo
+        acc = 1 if u.x in b.written else 0
+        d = self._conv_desc(u, b.B)
+        b.keep.append(d)
+        draw, dkey = self.draw_lane[ln].data_ptr(), ("draw", ln)
+        for grp in self._bn_groups(u):
+            co0 = grp[0][1]
+            cg = sum(m.cout for m, _ in grp)
+            segs = (_ffi.BnSeg * len(grp))(*[
+                _ffi.BnSeg(self._D(m.y.buf), m.y.c_off, self.g.bufs[m.y.buf].c, m.cout, self._beta(m), None)
+                for m, _ in grp])
+            b.keep.append(segs)
+            b.add(b.bwd, self.lib.jr_bn_relu_bwd_frozen,
+                  (self.dt, len(grp), ctypes.byref(segs), self.raw_unit[uid].data_ptr(), co0, u.cout, M, cg,
+                   self.mean_unit[uid].data_ptr() + 4 * co0 + b.stats_shift,
+                   self.invstd_unit[uid].data_ptr() + 4 * co0 + b.stats_shift, draw, b.S[ln]),
+                  "bn_relu_bwd_frozen", ln, [("d", m.y.buf, m.y.c_off) for m, _ in grp] + [("r", uid), ("p",)], [dkey],
+                  nbytes=3 * M * cg * self.esz)
+        if u.x != self.g.input_buf:
+            self._bwd_dgrad(b, ln, u, d, draw, dkey, acc)
+            return
+        ib = self.g.bufs[u.x]
+        b.add(b.bwd, self.lib.jr_conv2d_bwd_image,
+              (ctypes.byref(d), self.dt, draw, self.params.data_ptr() + 4 * u.koff, self.dinput.data_ptr(), 4, b.S[ln]),
+              "conv_bwd_image", ln, [dkey, ("p",)], [("dinput",)],
+              nbytes=M * u.cout * self.esz + 16 * b.B * ib.h * ib.w)
+
+    def input_gradient(self, B: Optional[int] = None, target=None) -> None:
+        """Enqueue d logit_t(i) / d image_i for every image i of the batch into
+        self.dinput (fp32 [B, h, w, 4], channel 3 zero).  target: None (logit 0)
+        or one class index per image.  Needs Engine(..., input_grad=True) and a
+        forward(B, bn="frozen") of the current batch: under frozen BN the
+        gradient of an image's logit is a property of that image alone."""
+        if not self.input_grad:
+            raise ValueError("input_gradient needs an engine built with input_grad=True")
+        self._check_frozen("frozen")
+        B = B or self.batch
+        if self._frozen_fwd != B:
+            raise ValueError(f"input_gradient({B}) needs a forward({B}, bn='frozen') of the current batch first "
+                             "(none since the last set_batch / batch-statistics forward)")
+        calls = self._build_input_grad(B)
+        with torch.cuda.stream(self.stream):
+            if target is None:
+                self.ig_target[:B].zero_()
+            else:
+                t = torch.as_tensor(target, dtype=torch.int32).reshape(-1)
+                if t.numel() != B:
+                    raise ValueError("target must have one class index per image")
+                self.ig_target[:B].copy_(t, non_blocking=True)
+        self.lanes.fork()
+        self.lanes.run(calls)
+        self.lanes.join()
+
+    def input_gradient_numpy(self, B: Optional[int] = None) -> np.ndarray:
+        """[B, h, w, 3]: the result of the last input_gradient."""
+        B = B or self.batch
+        ib = self.g.bufs[self.g.input_buf]
+        self.synchronize()
+        return self.dinput[:B * ib.h * ib.w * 4].view(B, ib.h, ib.w, 4)[..., :ib.c].cpu().numpy()
 
     # ---- optimizer
     def _opt_update(self, b: Build) -> None:
@@ -1276,6 +1394,7 @@ class Engine(Replica):
         jr_image_u8_warp_augment_nhwc (None, None: no augmentation)."""
         B = int(images.shape[0]) if n is None else n
         self._check_images(images, B)
+        self._frozen_fwd = None
         with torch.cuda.stream(self.stream):
             self._upload(images, labels, B, augment, warp)
         return B
@@ -1284,7 +1403,9 @@ class Engine(Replica):
     def forward(self, B: Optional[int] = None, bn: str = "batch") -> None:
         """bn="frozen": normalise with the statistics of freeze_bn() instead
         of this batch's (every image's output then depends on that image alone)."""
-        fwd = self._build_calls(B or self.batch, frozen=self._check_frozen(bn))[0]
+        frozen = self._check_frozen(bn)
+        fwd = self._build_calls(B or self.batch, frozen=frozen)[0]
+        self._frozen_fwd = (B or self.batch) if frozen else None
         self.lanes.fork()
         self.lanes.run(fwd)
         self.lanes.join()
