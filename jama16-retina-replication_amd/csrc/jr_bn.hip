@@ -21,7 +21,7 @@
 // chunk geometry, grids, workspace layout, argument validation, the tunable
 // constants and the kernel-argument structs -- is host-only code in
 // jr_bn_plan.h / jr_bn_plan.cpp.
-#include "jr_common.h"
+#include "jr_bn_rows.h"
 
 namespace jr {
 
@@ -35,54 +35,8 @@ constexpr bool kF32Select = JR_BN_F32_SELECT;  // (diagnostic) fp32 reduce loads
 // rows in flight per thread in the reductions (16 B per row and operand)
 template <int MODE> constexpr int red_rows() { return MODE == 0 ? 16 : JR_BN_BWD_ROWS; }
 
-// Pins a loaded vector in registers at this point: hipcc otherwise sinks a
-// load into the conditional block of its only use (one wait per row).
-__device__ __forceinline__ void pin(uint4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
-
-// (bn_xhat / bn_pre: jr_common.h, shared with the fused BN + max-pool)
-
-// One 16-byte vector of channels: 4 fp32 or 8 bf16, widened to fp32.
-template <typename T> struct Vec;
-template <> struct Vec<float> {
-  static constexpr int N = 4;
-  __device__ static void unpack(uint4 u, float* v) {
-    v[0] = __uint_as_float(u.x); v[1] = __uint_as_float(u.y);
-    v[2] = __uint_as_float(u.z); v[3] = __uint_as_float(u.w);
-  }
-  __device__ static void ld(const float* p, float* v) { unpack(*reinterpret_cast<const uint4*>(p), v); }
-  __device__ static void st(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
-template <> struct Vec<uint16_t> {
-  static constexpr int N = 8;
-  __device__ static void ld(const uint16_t* p, float* v) { unpack(*reinterpret_cast<const uint4*>(p), v); }
-  __device__ static void unpack(uint4 u, float* v) {
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(w[i] << 16);
-      v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  __device__ static void st(uint16_t* p, const float* v) {
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (uint32_t)f2bf(v[2 * i]) | ((uint32_t)f2bf(v[2 * i + 1]) << 16);
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-};
-
-// (BnSegs: jr_bn_plan.h.  Thread layout shared by every BN kernel: a row of c
-// channels is tpr = c / VW threads (one vector group q each); a 256-thread
-// block covers rpp = 256 / tpr rows per pass (row phase rr).  No index
-// division in the loops.)
-__device__ __forceinline__ int seg_of(const BnSegs& sg, int ch) {
-  int s = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxSegs; ++i) s += (i < sg.n && ch >= sg.c0[i]) ? 1 : 0;
-  return s;
-}
+// (pin, Vec, the thread layout, seg_of, the per-element expressions and the
+// elementwise row pass: jr_bn_rows.h)
 
 // Per-chunk column sums.  MODE 0: (sum x, sum x^2).  MODE 1 (bwd):
 // (sum dy', sum dy'*xhat).  Per-thread fp64 sums over a fixed row set,
@@ -183,8 +137,7 @@ __device__ __forceinline__ void bn_reduce_body(const T* __restrict__ x, int xs, 
 #pragma unroll
           for (int j = 0; j < VW; ++j) {
             const float xh = bn_xhat(xv[j], mu[j], is[j]);
-            const float pre = __fadd_rn(xh, be[j]);
-            const float g = pre > 0.f ? gv[j] : 0.f;
+            const float g = relu_grad(xh, be[j], gv[j]);
             if constexpr (kBatch32) {
               f0[j] += g;
               f1[j] = fmaf(g, xh, f1[j]);
@@ -282,7 +235,8 @@ __global__ void __launch_bounds__(256) k_bn_finalize(const double* __restrict__ 
 }
 
 // Elementwise passes: block b covers rows [b*rpp*U, (b+1)*rpp*U), thread
-// (q, rr) rows rr, rr+rpp, ...; per-channel constants loaded once.
+// (q, rr) rows rr, rr+rpp, ...; per-channel constants loaded once; the rows
+// themselves: row_pass (jr_bn_rows.h).
 // Grouped (ensemble members, blockIdx.y = member): x, y, the statistics and
 // beta move by their member strides (bytes; all 0 for an ordinary launch).
 template <typename T>
@@ -301,38 +255,12 @@ __global__ void __launch_bounds__(256) k_bn_relu_apply(const T* __restrict__ x, 
     beta = reinterpret_cast<const float*>(reinterpret_cast<const char*>(beta) + mb * be_mb);
   }
   constexpr int VW = Vec<T>::N;
-  const int tpr = c / VW;
-  const int rpp = 256 / tpr;
-  const int t = threadIdx.x;
-  const int q = t % tpr, rr = t / tpr;
-  if (rr >= rpp) return;
-  float mu[VW], is[VW], be[VW];
-#pragma unroll
-  for (int j = 0; j < VW; ++j) {
-    mu[j] = mean[q * VW + j]; is[j] = invstd[q * VW + j]; be[j] = beta[q * VW + j];
-  }
-  const int64_t r0 = (int64_t)blockIdx.x * rpp * kAppUnroll + rr;
-  // every row's load is unconditional (rows past m re-read row m - 1) and
-  // unpacked only after all were issued: a load under `if (r < m)` whose
-  // bf16 unpack sat in the same branch made hipcc wait for each row in turn
-  uint4 xr[kAppUnroll];
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) {
-    const int64_t r = min(r0 + (int64_t)u * rpp, m - 1);
-    xr[u] = *reinterpret_cast<const uint4*>(x + r * xs + q * VW);
-  }
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) pin(xr[u]);
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) {
-    const int64_t r = r0 + (int64_t)u * rpp;
-    if (r >= m) break;
-    float xv[VW], o[VW];
-    Vec<T>::unpack(xr[u], xv);
-#pragma unroll
-    for (int j = 0; j < VW; ++j) o[j] = fmaxf(bn_pre(xv[j], mu[j], is[j], be[j]), 0.f);
-    Vec<T>::st(y + r * y_stride + y_off + q * VW, o);
-  }
+  const RowLane l = row_lane<T>(c);
+  if (l.rr >= l.rpp) return;
+  const int ch = l.q * VW;
+  const BnConst<VW> k = bn_const<VW>(mean + ch, invstd + ch, beta + ch);
+  row_pass<T, false>(x + ch, xs, nullptr, 0, y + y_off + ch, y_stride, l.block_row(blockIdx.x), l.rpp, m,
+                     [=](int j, float xv, float) { return bn_relu(xv, k.mu[j], k.is[j], k.be[j]); });
 }
 
 // The apply of a fused sibling launch's members in ONE launch
@@ -343,41 +271,14 @@ __global__ void __launch_bounds__(256) k_bn_relu_apply_multi(const T* __restrict
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ invstd, ApplySegs sg) {
   constexpr int VW = Vec<T>::N;
-  const int tpr = c / VW;
-  const int rpp = 256 / tpr;
-  const int t = threadIdx.x;
-  const int q = t % tpr, rr = t / tpr;
-  if (rr >= rpp) return;
-  int si = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxSegs; ++i) si += (i < sg.n && q * VW >= sg.c0[i]) ? 1 : 0;
-  const int lc = q * VW - sg.c0[si];
-  T* y = static_cast<T*>(sg.y[si]) + sg.y_off[si] + lc;
-  const int ys = sg.y_stride[si];
-  float mu[VW], is[VW], be[VW];
-#pragma unroll
-  for (int j = 0; j < VW; ++j) {
-    mu[j] = mean[q * VW + j]; is[j] = invstd[q * VW + j]; be[j] = sg.beta[si][lc + j];
-  }
-  const int64_t r0 = (int64_t)blockIdx.x * rpp * kAppUnroll + rr;
-  uint4 xr[kAppUnroll];
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) {
-    const int64_t r = min(r0 + (int64_t)u * rpp, m - 1);
-    xr[u] = *reinterpret_cast<const uint4*>(x + r * xs + q * VW);
-  }
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) pin(xr[u]);
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) {
-    const int64_t r = r0 + (int64_t)u * rpp;
-    if (r >= m) break;
-    float xv[VW], o[VW];
-    Vec<T>::unpack(xr[u], xv);
-#pragma unroll
-    for (int j = 0; j < VW; ++j) o[j] = fmaxf(bn_pre(xv[j], mu[j], is[j], be[j]), 0.f);
-    Vec<T>::st(y + r * ys, o);
-  }
+  const RowLane l = row_lane<T>(c);
+  if (l.rr >= l.rpp) return;
+  const int ch = l.q * VW;
+  const int si = seg_of(sg, ch), lc = ch - sg.c0[si];
+  const BnConst<VW> k = bn_const<VW>(mean + ch, invstd + ch, sg.beta[si] + lc);
+  row_pass<T, false>(x + ch, xs, nullptr, 0, static_cast<T*>(sg.y[si]) + sg.y_off[si] + lc, sg.y_stride[si],
+                     l.block_row(blockIdx.x), l.rpp, m,
+                     [=](int j, float xv, float) { return bn_relu(xv, k.mu[j], k.is[j], k.be[j]); });
 }
 
 // k_bn_relu_apply with the statistics finalize folded in: block (bx, by)
@@ -415,96 +316,52 @@ __global__ void __launch_bounds__(256) k_bn_relu_apply_stats(const T* __restrict
     }
   }
   __syncthreads();
-  const int tpr = cg / VW;
-  const int rpp = 256 / tpr;
-  const int q = t % tpr, rr = t / tpr;
-  if (rr >= rpp) return;
-  float mu[VW], is[VW], be[VW];
-#pragma unroll
-  for (int k = 0; k < VW; ++k) {
-    mu[k] = s_mu[q * VW + k]; is[k] = s_is[q * VW + k]; be[k] = beta[c0 + q * VW + k];
-  }
+  const RowLane l = row_lane<T>(cg);
+  if (l.rr >= l.rpp) return;
+  const int co = c0 + l.q * VW;
+  const BnConst<VW> k = bn_const<VW>(s_mu + l.q * VW, s_is + l.q * VW, beta + co);
   const int64_t r0 = (int64_t)blockIdx.x * rpb, r1 = min(m, r0 + rpb);
-  const int co = c0 + q * VW;
-  for (int64_t rb = r0 + rr; rb < r1; rb += (int64_t)rpp * kAppUnroll) {
-    // unconditional loads (rows past the block re-read its last row), unpacked
-    // after all were issued (as in k_bn_relu_apply)
-    uint4 xr[kAppUnroll];
-#pragma unroll
-    for (int u = 0; u < kAppUnroll; ++u) {
-      const int64_t r = min(rb + (int64_t)u * rpp, r1 - 1);
-      xr[u] = *reinterpret_cast<const uint4*>(x + r * xs + co);
-    }
-#pragma unroll
-    for (int u = 0; u < kAppUnroll; ++u) pin(xr[u]);
-#pragma unroll
-    for (int u = 0; u < kAppUnroll; ++u) {
-      const int64_t r = rb + (int64_t)u * rpp;
-      if (r >= r1) break;
-      float xv[VW], o[VW];
-      Vec<T>::unpack(xr[u], xv);
-#pragma unroll
-      for (int k = 0; k < VW; ++k) o[k] = fmaxf(bn_pre(xv[k], mu[k], is[k], be[k]), 0.f);
-      Vec<T>::st(y + r * y_stride + y_off + co, o);
-    }
-  }
+  for (int64_t rb = r0 + l.rr; rb < r1; rb += (int64_t)l.rpp * kAppUnroll)
+    row_pass<T, false>(x + co, xs, nullptr, 0, y + y_off + co, y_stride, rb, l.rpp, r1,
+                       [=](int j, float xv, float) { return bn_relu(xv, k.mu[j], k.is[j], k.be[j]); });
 }
 
-// returns the largest |dx| this thread stored (0 if none)
+// The backward's rows of one thread: dx = bn_bwd_batch over rows rb, ... below
+// `end` of the channels at ch, k1 / k2 at the thread's first channel; one
+// pass (a block kernel) or, FOLD, stepped by rpp * kAppUnroll up to `end`.
+// Returns the largest |dx| this thread stored (0 if none).
+template <typename T, bool FOLD>
+__device__ __forceinline__ float bn_bwd_rows(const BnSegs& sg, const T* __restrict__ x, int xs, int ch,
+                                             const float* __restrict__ mean, const float* __restrict__ invstd,
+                                             const float* k1, const float* k2, T* dx, int64_t rb, int rpp,
+                                             int64_t end) {
+  constexpr int VW = Vec<T>::N;
+  const SegGrad<T> sd = seg_grad<T>(sg, ch);
+  const BnConst<VW> k = bn_const<VW>(mean + ch, invstd + ch, sd.beta);
+  float c1[VW], c2[VW];
+#pragma unroll
+  for (int j = 0; j < VW; ++j) {
+    c1[j] = k1[j]; c2[j] = k2[j];
+  }
+  const auto f = [=](int j, float xv, float dy) {
+    const float xh = bn_xhat(xv, k.mu[j], k.is[j]);
+    return bn_bwd_batch(xh, relu_grad(xh, k.be[j], dy), k.is[j], c1[j], c2[j]);
+  };
+  if constexpr (!FOLD) return row_pass<T, true>(x + ch, xs, sd.dy, sd.stride, dx + ch, xs, rb, rpp, end, f);
+  for (; rb < end; rb += (int64_t)rpp * kAppUnroll)
+    row_pass<T, true>(x + ch, xs, sd.dy, sd.stride, dx + ch, xs, rb, rpp, end, f);
+  return 0.f;
+}
+
 template <typename T>
 __device__ __forceinline__ float bn_bwd_apply_body(const BnSegs& sg, const T* __restrict__ x, int xs, int64_t m, int c,
                                                    const float* __restrict__ mean, const float* __restrict__ invstd,
                                                    const float* __restrict__ k1, const float* __restrict__ k2, T* dx,
                                                    int bx) {
-  constexpr int VW = Vec<T>::N;
-  const int tpr = c / VW;
-  const int rpp = 256 / tpr;
-  const int t = threadIdx.x;
-  const int q = t % tpr, rr = t / tpr;
-  if (rr >= rpp) return 0.f;
-  const int sgi = seg_of(sg, q * VW), lc = q * VW - sg.c0[sgi];
-  const T* dy = static_cast<const T*>(sg.dy[sgi]) + sg.dy_off[sgi] + lc;
-  const int dy_stride = sg.dy_stride[sgi];
-  float mu[VW], is[VW], be[VW], c1[VW], c2[VW];
-#pragma unroll
-  for (int j = 0; j < VW; ++j) {
-    const int k = q * VW + j;
-    mu[j] = mean[k]; is[j] = invstd[k]; be[j] = sg.beta[sgi][lc + j]; c1[j] = k1[k]; c2[j] = k2[k];
-  }
-  const int64_t r0 = (int64_t)bx * rpp * kAppUnroll + rr;
-  // unconditional loads (rows past m re-read row m - 1), unpacked after all
-  // were issued (as in k_bn_relu_apply)
-  uint4 xr[kAppUnroll], gr[kAppUnroll];
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) {
-    const int64_t r = min(r0 + (int64_t)u * rpp, m - 1);
-    xr[u] = *reinterpret_cast<const uint4*>(x + r * xs + q * VW);
-    gr[u] = *reinterpret_cast<const uint4*>(dy + r * dy_stride);
-  }
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) {
-    pin(xr[u]);
-    pin(gr[u]);
-  }
-  float amax = 0.f;
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) {
-    const int64_t r = r0 + (int64_t)u * rpp;
-    if (r >= m) break;
-    float xv[VW], gv[VW], o[VW];
-    Vec<T>::unpack(xr[u], xv);
-    Vec<T>::unpack(gr[u], gv);
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      const float xh = bn_xhat(xv[j], mu[j], is[j]);
-      const float pre = __fadd_rn(xh, be[j]);
-      const float g = pre > 0.f ? gv[j] : 0.f;
-      o[j] = is[j] * (g - c1[j] - xh * c2[j]);
-      amax = fmaxf(amax, fabsf(o[j]));
-    }
-    Vec<T>::st(dx + r * xs + q * VW, o);
-  }
-  return amax;
+  const RowLane l = row_lane<T>(c);
+  if (l.rr >= l.rpp) return 0.f;
+  const int ch = l.q * Vec<T>::N;
+  return bn_bwd_rows<T, false>(sg, x, xs, ch, mean, invstd, k1 + ch, k2 + ch, dx, l.block_row(bx), l.rpp, m);
 }
 
 // The block's max of v into word blockIdx.x % 64 of out (atomicMax on the
@@ -534,56 +391,22 @@ __global__ void __launch_bounds__(256) k_bn_relu_bwd_apply(BnSegs sg, const T* _
 
 // The backward under FROZEN statistics (jr_bn_relu_bwd_frozen): mean and
 // invstd are constants, so BN is affine and its backward one elementwise
-// pass, dx = T(g * invstd) with g = dy where the forward's pre-activation
-// (bn_pre: k_bn_relu_apply's expression, so the mask is the forward's bit for
-// bit) is positive, else 0 -- a select, whatever dy holds.  Thread layout and
-// loads as k_bn_relu_bwd_apply.
+// pass, dx = T(g * invstd) with g = relu_grad(dy).  Thread layout and loads as
+// k_bn_relu_bwd_apply.
 template <typename T>
 __global__ void __launch_bounds__(256) k_bn_relu_bwd_frozen(BnSegs sg, const T* __restrict__ x, int xs, int64_t m,
                                                             int c, const float* __restrict__ mean,
                                                             const float* __restrict__ invstd, T* dx) {
   constexpr int VW = Vec<T>::N;
-  const int tpr = c / VW;
-  const int rpp = 256 / tpr;
-  const int t = threadIdx.x;
-  const int q = t % tpr, rr = t / tpr;
-  if (rr >= rpp) return;
-  const int sgi = seg_of(sg, q * VW), lc = q * VW - sg.c0[sgi];
-  const T* dy = static_cast<const T*>(sg.dy[sgi]) + sg.dy_off[sgi] + lc;
-  const int dy_stride = sg.dy_stride[sgi];
-  float mu[VW], is[VW], be[VW];
-#pragma unroll
-  for (int j = 0; j < VW; ++j) {
-    const int k = q * VW + j;
-    mu[j] = mean[k]; is[j] = invstd[k]; be[j] = sg.beta[sgi][lc + j];
-  }
-  const int64_t r0 = (int64_t)blockIdx.x * rpp * kAppUnroll + rr;
-  uint4 xr[kAppUnroll], gr[kAppUnroll];
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) {
-    const int64_t r = min(r0 + (int64_t)u * rpp, m - 1);
-    xr[u] = *reinterpret_cast<const uint4*>(x + r * xs + q * VW);
-    gr[u] = *reinterpret_cast<const uint4*>(dy + r * dy_stride);
-  }
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) {
-    pin(xr[u]);
-    pin(gr[u]);
-  }
-#pragma unroll
-  for (int u = 0; u < kAppUnroll; ++u) {
-    const int64_t r = r0 + (int64_t)u * rpp;
-    if (r >= m) break;
-    float xv[VW], gv[VW], o[VW];
-    Vec<T>::unpack(xr[u], xv);
-    Vec<T>::unpack(gr[u], gv);
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      const float g = bn_pre(xv[j], mu[j], is[j], be[j]) > 0.f ? gv[j] : 0.f;
-      o[j] = __fmul_rn(g, is[j]);
-    }
-    Vec<T>::st(dx + r * xs + q * VW, o);
-  }
+  const RowLane l = row_lane<T>(c);
+  if (l.rr >= l.rpp) return;
+  const int ch = l.q * VW;
+  const SegGrad<T> sd = seg_grad<T>(sg, ch);
+  const BnConst<VW> k = bn_const<VW>(mean + ch, invstd + ch, sd.beta);
+  row_pass<T, true>(x + ch, xs, sd.dy, sd.stride, dx + ch, xs, l.block_row(blockIdx.x), l.rpp, m,
+                    [=](int j, float xv, float dy) {
+                      return bn_bwd_frozen(relu_grad(bn_xhat(xv, k.mu[j], k.is[j]), k.be[j], dy), k.is[j]);
+                    });
 }
 
 // Canonical combine of ONE channel's backward-reduce partials when there are
@@ -649,7 +472,6 @@ __global__ void __launch_bounds__(256) k_bn_relu_bwd_apply_fold(BnSegs sg, const
                                                                 const float* __restrict__ invstd,
                                                                 const double* __restrict__ part, int nchunks, T* dx,
                                                                 int rpb) {
-  constexpr int VW = Vec<T>::N;
   __shared__ float s_k1[kFoldCh], s_k2[kFoldCh];
   const int t = threadIdx.x;
   const int c0 = blockIdx.y * kFoldCh;
@@ -672,51 +494,11 @@ __global__ void __launch_bounds__(256) k_bn_relu_bwd_apply_fold(BnSegs sg, const
     }
   }
   __syncthreads();
-  const int tpr = cg / VW;
-  const int rpp = 256 / tpr;
-  const int q = t % tpr, rr = t / tpr;
-  if (rr >= rpp) return;
-  const int ch = c0 + q * VW;
-  const int sgi = seg_of(sg, ch), lc = ch - sg.c0[sgi];
-  const T* dy = static_cast<const T*>(sg.dy[sgi]) + sg.dy_off[sgi] + lc;
-  const int dy_stride = sg.dy_stride[sgi];
-  float mu[VW], is[VW], be[VW], c1[VW], c2[VW];
-#pragma unroll
-  for (int k = 0; k < VW; ++k) {
-    mu[k] = mean[ch + k]; is[k] = invstd[ch + k]; be[k] = sg.beta[sgi][lc + k];
-    c1[k] = s_k1[q * VW + k]; c2[k] = s_k2[q * VW + k];
-  }
-  const int64_t r0 = (int64_t)blockIdx.x * rpb, r1 = min(m, r0 + rpb);
-  for (int64_t rb = r0 + rr; rb < r1; rb += (int64_t)rpp * kAppUnroll) {
-    uint4 xr[kAppUnroll], gr[kAppUnroll];
-#pragma unroll
-    for (int u = 0; u < kAppUnroll; ++u) {
-      const int64_t r = min(rb + (int64_t)u * rpp, r1 - 1);
-      xr[u] = *reinterpret_cast<const uint4*>(x + r * xs + ch);
-      gr[u] = *reinterpret_cast<const uint4*>(dy + r * dy_stride);
-    }
-#pragma unroll
-    for (int u = 0; u < kAppUnroll; ++u) {
-      pin(xr[u]);
-      pin(gr[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < kAppUnroll; ++u) {
-      const int64_t r = rb + (int64_t)u * rpp;
-      if (r >= r1) break;
-      float xv[VW], gv[VW], o[VW];
-      Vec<T>::unpack(xr[u], xv);
-      Vec<T>::unpack(gr[u], gv);
-#pragma unroll
-      for (int k = 0; k < VW; ++k) {
-        const float xh = bn_xhat(xv[k], mu[k], is[k]);
-        const float pre = __fadd_rn(xh, be[k]);
-        const float g = pre > 0.f ? gv[k] : 0.f;
-        o[k] = is[k] * (g - c1[k] - xh * c2[k]);
-      }
-      Vec<T>::st(dx + r * xs + ch, o);
-    }
-  }
+  const RowLane l = row_lane<T>(cg);
+  if (l.rr >= l.rpp) return;
+  const int64_t r0 = (int64_t)blockIdx.x * rpb;
+  const int v0 = l.q * Vec<T>::N;
+  bn_bwd_rows<T, true>(sg, x, xs, c0 + v0, mean, invstd, s_k1 + v0, s_k2 + v0, dx, r0 + l.rr, l.rpp, min(m, r0 + rpb));
 }
 
 // Several independent layers' backwards in ONE set of three launches
@@ -1009,96 +791,30 @@ __global__ void __launch_bounds__(256) k_maxpool_bwd_bn(jr_pool_desc d, const ui
                                                         const float* __restrict__ beta, double* part) {
   __shared__ double red[256][8];
   const int c4 = d.c >> 2;
-  const int hc = (d.h + 1) >> 1, wc = (d.w + 1) >> 1;
-  const int total = d.n * hc * wc * c4;
+  const int total = d.n * ((d.h + 1) >> 1) * ((d.w + 1) >> 1) * c4;
   const int stride = gridDim.x * blockDim.x;
   const int q = (blockIdx.x * blockDim.x + threadIdx.x) % c4;   // fixed per thread: blockDim.x % c4 == 0
-  float mu[4], is[4], be[4];
-#pragma unroll
-  for (int l = 0; l < 4; ++l) {
-    mu[l] = mean[q * 4 + l];
-    is[l] = invstd[q * 4 + l];
-    be[l] = beta[q * 4 + l];
-  }
+  const BnConst<4> k = bn_const<4>(mean + q * 4, invstd + q * 4, beta + q * 4);
   double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-    const int cell = e / c4;
-    const int cb = cell % wc;
-    const int t = cell / wc;
-    const int ca = t % hc;
-    const int b = t / hc;
-    uint32_t am[2][2];
-    float4 g[2][2];
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride)
+    maxpool_bwd_cell(d, argmax, pdy, e / c4, q, [&](int b, int ih, int iw, float4 o) {
+      const int64_t pix = ((int64_t)b * d.h + ih) * d.w + iw;
+      P4<T>::st(dy + pix * d.x_c_stride + d.x_c_off + q * 4, o);
+      float acc[4] = {o.x, o.y, o.z, o.w};
+      if constexpr (sizeof(T) == 2) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int oh = ca - 1 + i, ow = cb - 1 + j;
-        am[i][j] = 0xffffffffu;
-        g[i][j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (oh >= 0 && oh < d.ho && ow >= 0 && ow < d.wo) {
-          const int64_t op = ((int64_t)b * d.ho + oh) * d.wo + ow;
-          am[i][j] = *reinterpret_cast<const uint32_t*>(argmax + op * d.c + q * 4);
-          float v[4];
-          if constexpr (sizeof(T) == 4) {
-            const float4 f = *reinterpret_cast<const float4*>(pdy + op * d.y_c_stride + d.y_c_off + q * 4);
-            v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-          } else {
-            const uint2 u = *reinterpret_cast<const uint2*>(pdy + op * d.y_c_stride + d.y_c_off + q * 4);
-            v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
-            v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
-          }
-          g[i][j] = make_float4(v[0], v[1], v[2], v[3]);
-        }
+        for (int l = 0; l < 4; ++l) acc[l] = bf2f(f2bf(acc[l]));   // the value k_bn_reduce would read
       }
-    }
+      const float4 xq = P4<T>::ld(x + pix * xs + q * 4);
+      const float xv[4] = {xq.x, xq.y, xq.z, xq.w};
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-#pragma unroll
-      for (int v = 0; v < 2; ++v) {
-        const int ih = 2 * ca + u, iw = 2 * cb + v;
-        if (ih >= d.h || iw >= d.w) continue;
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const int r = u + 2 - 2 * i, c = v + 2 - 2 * j;
-            if (r > 2 || c > 2) continue;
-            const float ga[4] = {g[i][j].x, g[i][j].y, g[i][j].z, g[i][j].w};
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-              if ((int)((am[i][j] >> (8 * l)) & 0xff) == r * 3 + c) acc[l] += ga[l];
-          }
-        }
-        const int64_t pix = ((int64_t)b * d.h + ih) * d.w + iw;
-        float xv[4];
-        T* p = dy + pix * d.x_c_stride + d.x_c_off + q * 4;
-        if constexpr (sizeof(T) == 4) {
-          *reinterpret_cast<float4*>(p) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-          const float4 f = *reinterpret_cast<const float4*>(x + pix * xs + q * 4);
-          xv[0] = f.x; xv[1] = f.y; xv[2] = f.z; xv[3] = f.w;
-        } else {
-          uint2 w;
-          w.x = (uint32_t)f2bf(acc[0]) | ((uint32_t)f2bf(acc[1]) << 16);
-          w.y = (uint32_t)f2bf(acc[2]) | ((uint32_t)f2bf(acc[3]) << 16);
-          *reinterpret_cast<uint2*>(p) = w;
-#pragma unroll
-          for (int l = 0; l < 4; ++l) acc[l] = bf2f(f2bf(acc[l]));   // the value k_bn_reduce would read
-          const uint2 xr = *reinterpret_cast<const uint2*>(x + pix * xs + q * 4);
-          xv[0] = __uint_as_float(xr.x << 16); xv[1] = __uint_as_float(xr.x & 0xffff0000u);
-          xv[2] = __uint_as_float(xr.y << 16); xv[3] = __uint_as_float(xr.y & 0xffff0000u);
-        }
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-          const float xh = bn_xhat(xv[l], mu[l], is[l]);
-          const float g2 = __fadd_rn(xh, be[l]) > 0.f ? acc[l] : 0.f;
-          s0[l] += (double)g2;
-          s1[l] += (double)g2 * (double)xh;
-        }
+      for (int l = 0; l < 4; ++l) {
+        const float xh = bn_xhat(xv[l], k.mu[l], k.is[l]);
+        const float g2 = relu_grad(xh, k.be[l], acc[l]);
+        s0[l] += (double)g2;
+        s1[l] += (double)g2 * (double)xh;
       }
-    }
-  }
+    });
   const int t = threadIdx.x;
 #pragma unroll
   for (int l = 0; l < 4; ++l) {
@@ -1149,6 +865,12 @@ JR_API int jr_bn_relu_bwd_maxpool_absmax(int dtype, const jr_pool_desc* d, const
       !check_slice(dtype, 0, x_c_stride, c))
     return fail(JR_ERR_INVALID, "bn_relu_bwd_maxpool: bad slice");
   if (!ws || ws_bytes < pool_bwd_ws(c)) return fail(JR_ERR_WORKSPACE, "bn_relu_bwd_maxpool: workspace too small");
+  // the finalize and the apply see the dy this call writes as one segment
+  const jr_bn_seg seg{dy, d->x_c_off, d->x_c_stride, c, beta, dbeta};
+  BnSegs sg;
+  rc = bwd_segs(dtype, 1, &seg, c, sg);
+  if (rc) return rc;
+  sg.absmax = dx_absmax;
   hipStream_t s = as_stream(stream);
   const PoolBwdGeom g = pool_bwd_geom(d);
   const jr_bn_launch_plan p = bn_plan(dtype, m, c);
@@ -1162,16 +884,6 @@ JR_API int jr_bn_relu_bwd_maxpool_absmax(int dtype, const jr_pool_desc* d, const
   });
   rc = check_launch("maxpool_bwd + bn reduce");
   if (rc) return rc;
-  BnSegs sg{};
-  sg.n = 1;
-  sg.dy[0] = at_channel(dtype, dy, d->x_c_off);
-  sg.dy_off[0] = 0;
-  sg.dy_stride[0] = d->x_c_stride;
-  sg.beta[0] = beta;
-  sg.dbeta[0] = dbeta;
-  sg.c0[0] = 0;
-  sg.c0[1] = c;
-  sg.absmax = dx_absmax;
   hipLaunchKernelGGL((k_bn_finalize<1>), dim3(p.stats_finalize_grid), dim3(256), 0, s, part, g.grid, c, m, 0.f, k1,
                      k2, sg);
   rc = check_launch("bn_bwd finalize");

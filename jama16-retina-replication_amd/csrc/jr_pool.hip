@@ -10,71 +10,25 @@
 //    9-10; a7): TF divides by the number of in-bounds taps (exclude padding).
 //  - GlobalAveragePooling2D (pooling='avg', train.py:130; a9).
 // All kernels move fp32x4 (or bf16x4) vectors along the channel axis.
-#include "jr_common.h"
+#include "jr_bn_rows.h"
 
 namespace jr {
-
-template <typename T> struct P4;
-template <> struct P4<float> {
-  __device__ static float4 ld(const float* p) { return *reinterpret_cast<const float4*>(p); }
-  __device__ static void st(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-};
-template <> struct P4<uint16_t> {
-  __device__ static float4 ld(const uint16_t* p) {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u),
-                       __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-  }
-  __device__ static void st(uint16_t* p, float4 v) {
-    uint2 u;
-    u.x = (uint32_t)f2bf(v.x) | ((uint32_t)f2bf(v.y) << 16);
-    u.y = (uint32_t)f2bf(v.z) | ((uint32_t)f2bf(v.w) << 16);
-    *reinterpret_cast<uint2*>(p) = u;
-  }
-};
 
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) {
   return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
 }
 
+// (P4, maxpool_scan, maxpool_bwd_cell: jr_bn_rows.h)
 template <typename T>
 __global__ void __launch_bounds__(256) k_maxpool_fwd(jr_pool_desc d, const T* __restrict__ x, T* y,
                                                      uint8_t* argmax) {
-  const int c4 = d.c >> 2;
-  const int total = d.n * d.ho * d.wo * c4;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const int q = e % c4;
-    const int pix = e / c4;
-    const int ow = pix % d.wo;
-    const int t = pix / d.wo;
-    const int oh = t % d.ho;
-    const int b = t / d.ho;
-    float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    int arg[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int ih = oh * 2 + r, iw = ow * 2 + c;
-        const float4 v = P4<T>::ld(x + ((int64_t)(b * d.h + ih) * d.w + iw) * d.x_c_stride + d.x_c_off + q * 4);
-        const float va[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (va[j] > best[j] || (r == 0 && c == 0)) { best[j] = va[j]; arg[j] = r * 3 + c; }
-      }
-    }
-    P4<T>::st(y + (int64_t)pix * d.y_c_stride + d.y_c_off + q * 4, make_float4(best[0], best[1], best[2], best[3]));
-    if (argmax) {
-      const uint32_t packed = (uint32_t)arg[0] | ((uint32_t)arg[1] << 8) | ((uint32_t)arg[2] << 16) |
-                              ((uint32_t)arg[3] << 24);
-      *reinterpret_cast<uint32_t*>(argmax + (int64_t)pix * d.c + q * 4) = packed;
-    }
-  }
+  maxpool_scan(d, x, y, argmax, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x,
+               [](int, int) { return [](int, float v) { return v; }; });
 }
 
 // BN + ReLU + max-pool in one pass (the stem's conv2d_3 / conv2d_5 outputs,
 // whose only reader is the max-pool): every window tap is the raw conv output
-// put through bn_pre and ReLU -- and rounded to the path dtype, exactly as
+// put through bn_relu -- and rounded to the path dtype, exactly as
 // k_bn_relu_apply stores it -- before the comparison, so y and argmax are
 // bitwise the two-kernel result, without writing and re-reading the
 // full-resolution activation (354 / 248 MB per fp32 step).  Grouped
@@ -86,109 +40,31 @@ __global__ void __launch_bounds__(256) k_bn_relu_maxpool_fwd(jr_pool_desc d, con
                                                              const float* __restrict__ invstd,
                                                              const float* __restrict__ beta, T* y, uint8_t* argmax,
                                                              int ipm, long long st_mb, long long be_mb) {
-  const int c4 = d.c >> 2;
-  const int total = d.n * d.ho * d.wo * c4;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const int q = e % c4;
-    const int pix = e / c4;
-    const int ow = pix % d.wo;
-    const int t = pix / d.wo;
-    const int oh = t % d.ho;
-    const int b = t / d.ho;
+  maxpool_scan(d, x, y, argmax, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, [=](int b, int q) {
+    // (the member's statistics and beta, then the tap: the value k_bn_relu_apply stores)
     const long long mem = b / ipm;
-    float mu[4], is[4], be[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      mu[j] = mean[mem * st_mb + q * 4 + j];
-      is[j] = invstd[mem * st_mb + q * 4 + j];
-      be[j] = beta[mem * be_mb + q * 4 + j];
-    }
-    float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    int arg[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int ih = oh * 2 + r, iw = ow * 2 + c;
-        const float4 v = P4<T>::ld(x + ((int64_t)(b * d.h + ih) * d.w + iw) * d.x_c_stride + d.x_c_off + q * 4);
-        const float va[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float a = fmaxf(bn_pre(va[j], mu[j], is[j], be[j]), 0.f);
-          if constexpr (sizeof(T) == 2) a = bf2f(f2bf(a));
-          if (a > best[j] || (r == 0 && c == 0)) { best[j] = a; arg[j] = r * 3 + c; }
-        }
-      }
-    }
-    P4<T>::st(y + (int64_t)pix * d.y_c_stride + d.y_c_off + q * 4, make_float4(best[0], best[1], best[2], best[3]));
-    if (argmax) {
-      const uint32_t packed = (uint32_t)arg[0] | ((uint32_t)arg[1] << 8) | ((uint32_t)arg[2] << 16) |
-                              ((uint32_t)arg[3] << 24);
-      *reinterpret_cast<uint32_t*>(argmax + (int64_t)pix * d.c + q * 4) = packed;
-    }
-  }
+    const BnConst<4> k = bn_const<4>(mean + mem * st_mb + q * 4, invstd + mem * st_mb + q * 4,
+                                     beta + mem * be_mb + q * 4);
+    return [=](int j, float v) {
+      const float a = bn_relu(v, k.mu[j], k.is[j], k.be[j]);
+      return sizeof(T) == 2 ? bf2f(f2bf(a)) : a;
+    };
+  });
 }
 
-// Backward as a gather over 2x2 input cells: input rows 2a, 2a+1 and columns
-// 2b, 2b+1 are covered only by the windows oh in {a-1, a}, ow in {b-1, b}, so
-// one thread loads those (at most) four windows' dy and argmax once and writes
-// the four input pixels of its cell -- one dy/argmax load per output pixel
-// instead of the 2.25 of a thread per input pixel.  Each input pixel still sums
-// its windows in (oh, ow) ascending order.
+// (the gather: maxpool_bwd_cell)
 template <typename T>
 __global__ void __launch_bounds__(256) k_maxpool_bwd(jr_pool_desc d, const uint8_t* __restrict__ argmax,
                                                      const T* __restrict__ dy, T* __restrict__ dx, int accumulate) {
   const int c4 = d.c >> 2;
-  const int hc = (d.h + 1) >> 1, wc = (d.w + 1) >> 1;
-  const int total = d.n * hc * wc * c4;
+  const int total = d.n * ((d.h + 1) >> 1) * ((d.w + 1) >> 1) * c4;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
     const int q = e % c4;
-    const int cell = e / c4;
-    const int cb = cell % wc;
-    const int t = cell / wc;
-    const int ca = t % hc;
-    const int b = t / hc;
-    uint32_t am[2][2];
-    float4 g[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int oh = ca - 1 + i, ow = cb - 1 + j;
-        am[i][j] = 0xffffffffu;                  // position 255: matches no tap
-        g[i][j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (oh >= 0 && oh < d.ho && ow >= 0 && ow < d.wo) {
-          const int64_t op = ((int64_t)b * d.ho + oh) * d.wo + ow;
-          am[i][j] = *reinterpret_cast<const uint32_t*>(argmax + op * d.c + q * 4);
-          g[i][j] = P4<T>::ld(dy + op * d.y_c_stride + d.y_c_off + q * 4);
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-#pragma unroll
-      for (int v = 0; v < 2; ++v) {
-        const int ih = 2 * ca + u, iw = 2 * cb + v;
-        if (ih >= d.h || iw >= d.w) continue;
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const int r = u + 2 - 2 * i, c = v + 2 - 2 * j;   // tap of (ih, iw) in window (ca-1+i, cb-1+j)
-            if (r > 2 || c > 2) continue;                      // compile-time after unrolling
-            const float ga[4] = {g[i][j].x, g[i][j].y, g[i][j].z, g[i][j].w};
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-              if ((int)((am[i][j] >> (8 * l)) & 0xff) == r * 3 + c) acc[l] += ga[l];
-          }
-        }
-        T* p = dx + ((int64_t)(b * d.h + ih) * d.w + iw) * d.x_c_stride + d.x_c_off + q * 4;
-        float4 o = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        if (accumulate) o = f4add(o, P4<T>::ld(p));
-        P4<T>::st(p, o);
-      }
-    }
+    maxpool_bwd_cell(d, argmax, dy, e / c4, q, [=](int b, int ih, int iw, float4 o) {
+      T* p = dx + ((int64_t)(b * d.h + ih) * d.w + iw) * d.x_c_stride + d.x_c_off + q * 4;
+      if (accumulate) o = f4add(o, P4<T>::ld(p));
+      P4<T>::st(p, o);
+    });
   }
 }
 
