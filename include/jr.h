@@ -52,7 +52,10 @@
  *    (dropped: ml + lm < 2^-32 |a b| and l*l, the JR_F32_X8 class), and the
  *    result is scaled back exactly.  Same tiles, config ids, split-K and
  *    stream-K plans as JR_F32_X8; 3/4 of its MFMAs.  A magnitude above the
- *    stated bound saturates (wrong results): bounds must hold.
+ *    stated bound saturates (wrong results): bounds must hold.  Where a
+ *    host bound has no proof (activations under frozen BN statistics), the
+ *    *_guard entry points check it on the device as the values are stored
+ *    and report through jr_device_check instead of saturating in silence.
  */
 #ifndef JR_H_
 #define JR_H_
@@ -128,6 +131,9 @@ const char* jr_version(void);
  * library's device error word, or a hand-off word of a stream with no work
  * in flight is non-zero (a stale count below the piece count, which makes a
  * tile complete early; the words of every idle stream are scanned here).
+ * The same error word counts the magnitude guards: a jr_absmax_prep segment
+ * above its limit, or a block of a *_guard entry point that stored an
+ * activation above its limit.
  * The outputs of the launches since the last check are then invalid.
  * Stream-K blocks never wait for one another, so no timeout exists.  On
  * JR_ERR_DEVICE the call synchronises the device, re-zeroes every stream-K
@@ -314,6 +320,40 @@ int jr_bn_relu_apply_grouped(int dtype, int32_t members, const void* x, int32_t 
                              int64_t x_member_stride, int64_t m, int32_t c, const float* mean, const float* invstd,
                              int64_t stats_member_stride, const float* beta, int64_t beta_member_stride, void* y,
                              int32_t y_c_off, int32_t y_c_stride, int64_t y_member_stride, void* stream);
+/* The guarded forms: the entry point of the same name with `limit` before
+ * `stream` (also jr_bn_relu_maxpool3x3s2_fwd_guard / _grouped_guard below).
+ * They exist for forwards under FROZEN statistics that feed JR_F32_X6H convs:
+ * there the activation bound of the batch-statistics forward (Samuelson's
+ * inequality) does not hold, so the kernels that store the activations check
+ * it instead.
+ *  - Every stored output (and argmax) is bit for bit the unguarded entry
+ *    point's: the same kernels, thread layout and per-element device function.
+ *  - limit must be finite and > 0: anything else is JR_ERR_INVALID, checked
+ *    first, before any HIP call; the rest of the validation is the unguarded
+ *    call's.
+ *  - Each block whose largest stored |y| is not <= limit counts one failure
+ *    into the library's device error word (JR_ERR_HIP if there is none: call
+ *    jr_init before capturing); jr_device_check then returns JR_ERR_DEVICE
+ *    once and clears the word.  +inf trips the guard; a NaN need not (the
+ *    maximum is taken with fmaxf, which drops it).  A negative pre-activation
+ *    of any size stores 0 and never trips it.
+ *  - Grouped forms: one error word for all members.  No host synchronisation,
+ *    no atomics but the error count; capturable.
+ * With a power-of-two bound m on the descriptor of the conv that reads y,
+ * limit = 2 m keeps the JR_F32_X6H split exact (see jr_conv_desc); fp16
+ * saturates only near 4 m.  The scales are then constants: a frozen forward
+ * guarded this way is bitwise independent of the other images of the batch. */
+int jr_bn_relu_apply_guard(int dtype, const void* x, int32_t x_c_off, int32_t x_c_stride, int64_t m, int32_t c,
+                           const float* mean, const float* invstd, const float* beta, void* y, int32_t y_c_off,
+                           int32_t y_c_stride, float limit, void* stream);
+int jr_bn_relu_apply_multi_guard(int dtype, int nseg, const jr_bn_apply_seg* segs, const void* x, int32_t x_c_off,
+                                 int32_t x_c_stride, int64_t m, int32_t c, const float* mean, const float* invstd,
+                                 float limit, void* stream);
+int jr_bn_relu_apply_grouped_guard(int dtype, int32_t members, const void* x, int32_t x_c_off, int32_t x_c_stride,
+                                   int64_t x_member_stride, int64_t m, int32_t c, const float* mean,
+                                   const float* invstd, int64_t stats_member_stride, const float* beta,
+                                   int64_t beta_member_stride, void* y, int32_t y_c_off, int32_t y_c_stride,
+                                   int64_t y_member_stride, float limit, void* stream);
 /* Backward of apply+stats: dy is the gradient w.r.t. y (a channel slice),
  * dx receives the gradient w.r.t. the raw conv output in the same channel
  * slice geometry as x, dbeta [c] receives sum of the ReLU-masked dy. */
@@ -355,6 +395,18 @@ int jr_bn_relu_bwd_multi_absmax(int dtype, int nseg, const jr_bn_seg* segs, cons
 int jr_bn_relu_bwd_frozen(int dtype, int nseg, const jr_bn_seg* segs, const void* x, int32_t x_c_off,
                           int32_t x_c_stride, int64_t m, int32_t c, const float* mean, const float* invstd, void* dx,
                           void* stream);
+/* jr_bn_relu_bwd_frozen (dx bitwise unchanged) that also raises dx_absmax,
+ * exactly as jr_bn_relu_bwd_multi_absmax does: 64 device floats, zeroed by the
+ * caller (jr_absmax_reset) before the first launch that feeds them, whose
+ * maximum is then max |dx| of every launch that fed them -- the dy_absmax of
+ * the JR_F32_X6H data-gradient GEMM that reads dx.  That scale is measured
+ * per batch (a gradient has no a-priori bound), so an x6h input gradient
+ * under frozen statistics is independent of the other images of the batch
+ * only to within the x6h error class, not bitwise as the guarded frozen
+ * forward is.  dx_absmax NULL: jr_bn_relu_bwd_frozen. */
+int jr_bn_relu_bwd_frozen_absmax(int dtype, int nseg, const jr_bn_seg* segs, const void* x, int32_t x_c_off,
+                                 int32_t x_c_stride, int64_t m, int32_t c, const float* mean, const float* invstd,
+                                 void* dx, float* dx_absmax, void* stream);
 /* Up to 8 independent conv2d_bn backwards (the branch-final layers of one
  * Inception block, whose upstream gradients become final together) in ONE
  * set of three launches; layer l is exactly the jr_bn_relu_bwd_multi call
@@ -416,6 +468,18 @@ int jr_bn_relu_maxpool3x3s2_fwd_grouped(const jr_pool_desc* d, int dtype, int32_
                                         const void* raw, const float* mean, const float* invstd,
                                         int64_t stats_member_stride, const float* beta, int64_t beta_member_stride,
                                         void* y, uint8_t* argmax, void* stream);
+/* Their guarded forms (the contract: jr_bn_relu_apply_guard).  The guard is
+ * over the POOLED values these calls store, which are what the next conv
+ * reads: a raw value in a row or column that no 3x3/2 window covers, or one
+ * that is not its window's maximum, never trips it. */
+int jr_bn_relu_maxpool3x3s2_fwd_guard(const jr_pool_desc* d, int dtype, const void* raw, const float* mean,
+                                      const float* invstd, const float* beta, void* y, uint8_t* argmax, float limit,
+                                      void* stream);
+int jr_bn_relu_maxpool3x3s2_fwd_grouped_guard(const jr_pool_desc* d, int dtype, int32_t images_per_member,
+                                              const void* raw, const float* mean, const float* invstd,
+                                              int64_t stats_member_stride, const float* beta,
+                                              int64_t beta_member_stride, void* y, uint8_t* argmax, float limit,
+                                              void* stream);
 int jr_avgpool3x3s1_fwd(const jr_pool_desc* d, int dtype, const void* x, void* y, void* stream);
 int jr_avgpool3x3s1_bwd(const jr_pool_desc* d, int dtype, const void* dy, void* dx, int accumulate,
                         void* stream);
@@ -504,6 +568,11 @@ typedef struct jr_absmax_seg {
 } jr_absmax_seg;
 int jr_absmax_prep(const float* src, const jr_absmax_seg* segs, int32_t nseg, float* out, int64_t zero_floats,
                    void* stream);
+/* jr_absmax_prep's zeroing alone: rows[0 .. n_floats) = 0 in stream order (one
+ * memset node: capturable), for absmax words that a launch list raises anew
+ * on every run (jr_bn_relu_bwd_frozen_absmax).  JR_ERR_INVALID for a NULL
+ * pointer or a negative count; n_floats == 0 does nothing. */
+int jr_absmax_reset(float* rows, int64_t n_floats, void* stream);
 
 /* ---- moving averages of the BN statistics, frozen inference ----------
  * The engines keep every conv launch's batch statistics in one flat fp32

@@ -184,7 +184,8 @@ JR_API int jr_device_check(void) {
   (void)hipDeviceSynchronize();
   return fail(JR_ERR_DEVICE, "device check: " + std::to_string(h) +
                                  " failure(s) counted by kernels (a stream-K hand-off count past its tile's piece "
-                                 "count, or a JR_F32_X6H magnitude bound exceeded: jr_absmax_prep) and " +
+                                 "count, or a JR_F32_X6H magnitude bound exceeded: jr_absmax_prep, or an activation "
+                                 "above the limit of a *_guard entry point) and " +
                                  std::to_string(stale) +
                                  " stream-K hand-off word(s) of idle streams not left zero; the outputs of the "
                                  "launches since the last jr_device_check are invalid (hand-off words reset)");

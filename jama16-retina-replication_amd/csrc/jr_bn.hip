@@ -239,13 +239,21 @@ __global__ void __launch_bounds__(256) k_bn_finalize(const double* __restrict__ 
 // themselves: row_pass (jr_bn_rows.h).
 // Grouped (ensemble members, blockIdx.y = member): x, y, the statistics and
 // beta move by their member strides (bytes; all 0 for an ordinary launch).
-template <typename T>
+// GUARD (the *_guard entry points): the same pass, then block_guard over the
+// largest magnitude the block stored -- guarded_relu is the stored value, so
+// y is bit for bit the unguarded kernel's; idle threads stay for the block
+// reduction with 0.
+template <typename T> __device__ __forceinline__ float guarded_relu(float a) {
+  return sizeof(T) == 2 ? bf2f(f2bf(a)) : a;   // (bf16: what Vec::st stores; rounding it again is the identity)
+}
+
+template <typename T, bool GUARD>
 __global__ void __launch_bounds__(256) k_bn_relu_apply(const T* __restrict__ x, int xs, int64_t m, int c,
                                                        const float* __restrict__ mean,
                                                        const float* __restrict__ invstd,
                                                        const float* __restrict__ beta, T* y, int y_off,
                                                        int y_stride, int64_t x_mb, int64_t y_mb, int64_t st_mb,
-                                                       int64_t be_mb) {
+                                                       int64_t be_mb, float limit, unsigned* err) {
   if (gridDim.y > 1) {
     const int64_t mb = blockIdx.y;
     x = reinterpret_cast<const T*>(reinterpret_cast<const char*>(x) + mb * x_mb);
@@ -256,29 +264,46 @@ __global__ void __launch_bounds__(256) k_bn_relu_apply(const T* __restrict__ x, 
   }
   constexpr int VW = Vec<T>::N;
   const RowLane l = row_lane<T>(c);
-  if (l.rr >= l.rpp) return;
-  const int ch = l.q * VW;
-  const BnConst<VW> k = bn_const<VW>(mean + ch, invstd + ch, beta + ch);
-  row_pass<T, false>(x + ch, xs, nullptr, 0, y + y_off + ch, y_stride, l.block_row(blockIdx.x), l.rpp, m,
-                     [=](int j, float xv, float) { return bn_relu(xv, k.mu[j], k.is[j], k.be[j]); });
+  const bool idle = l.rr >= l.rpp;
+  if (!GUARD && idle) return;
+  float amax = 0.f;
+  if (!idle) {
+    const int ch = l.q * VW;
+    const BnConst<VW> k = bn_const<VW>(mean + ch, invstd + ch, beta + ch);
+    amax = row_pass<T, false>(x + ch, xs, nullptr, 0, y + y_off + ch, y_stride, l.block_row(blockIdx.x), l.rpp, m,
+                              [=](int j, float xv, float) {
+                                const float a = bn_relu(xv, k.mu[j], k.is[j], k.be[j]);
+                                return GUARD ? guarded_relu<T>(a) : a;
+                              });
+  }
+  if (GUARD) block_guard(amax, limit, err);
 }
 
 // The apply of a fused sibling launch's members in ONE launch
 // (jr_bn_relu_apply_multi): the raw output's c channels, segment i its own
-// output slice and beta; per element exactly k_bn_relu_apply's arithmetic.
-template <typename T>
+// output slice and beta; per element exactly k_bn_relu_apply's arithmetic
+// (and its GUARD).
+template <typename T, bool GUARD>
 __global__ void __launch_bounds__(256) k_bn_relu_apply_multi(const T* __restrict__ x, int xs, int64_t m, int c,
                                                              const float* __restrict__ mean,
-                                                             const float* __restrict__ invstd, ApplySegs sg) {
+                                                             const float* __restrict__ invstd, ApplySegs sg,
+                                                             float limit, unsigned* err) {
   constexpr int VW = Vec<T>::N;
   const RowLane l = row_lane<T>(c);
-  if (l.rr >= l.rpp) return;
-  const int ch = l.q * VW;
-  const int si = seg_of(sg, ch), lc = ch - sg.c0[si];
-  const BnConst<VW> k = bn_const<VW>(mean + ch, invstd + ch, sg.beta[si] + lc);
-  row_pass<T, false>(x + ch, xs, nullptr, 0, static_cast<T*>(sg.y[si]) + sg.y_off[si] + lc, sg.y_stride[si],
-                     l.block_row(blockIdx.x), l.rpp, m,
-                     [=](int j, float xv, float) { return bn_relu(xv, k.mu[j], k.is[j], k.be[j]); });
+  const bool idle = l.rr >= l.rpp;
+  if (!GUARD && idle) return;
+  float amax = 0.f;
+  if (!idle) {
+    const int ch = l.q * VW;
+    const int si = seg_of(sg, ch), lc = ch - sg.c0[si];
+    const BnConst<VW> k = bn_const<VW>(mean + ch, invstd + ch, sg.beta[si] + lc);
+    amax = row_pass<T, false>(x + ch, xs, nullptr, 0, static_cast<T*>(sg.y[si]) + sg.y_off[si] + lc, sg.y_stride[si],
+                              l.block_row(blockIdx.x), l.rpp, m, [=](int j, float xv, float) {
+                                const float a = bn_relu(xv, k.mu[j], k.is[j], k.be[j]);
+                                return GUARD ? guarded_relu<T>(a) : a;
+                              });
+  }
+  if (GUARD) block_guard(amax, limit, err);
 }
 
 // k_bn_relu_apply with the statistics finalize folded in: block (bx, by)
@@ -367,16 +392,8 @@ __device__ __forceinline__ float bn_bwd_apply_body(const BnSegs& sg, const T* __
 // The block's max of v into word blockIdx.x % 64 of out (atomicMax on the
 // float bits: every value is >= 0).  Every thread of the block calls it.
 __device__ __forceinline__ void block_absmax_to(float v, float* out) {
-  __shared__ float s_max[4];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float b = s_max[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) b = fmaxf(b, s_max[w]);
-    atomicMax(reinterpret_cast<unsigned*>(out) + (blockIdx.x & 63), __float_as_uint(b));
-  }
+  const float b = block_max(v);   // (jr_bn_rows.h)
+  if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned*>(out) + (blockIdx.x & 63), __float_as_uint(b));
 }
 
 template <typename T>
@@ -392,21 +409,24 @@ __global__ void __launch_bounds__(256) k_bn_relu_bwd_apply(BnSegs sg, const T* _
 // The backward under FROZEN statistics (jr_bn_relu_bwd_frozen): mean and
 // invstd are constants, so BN is affine and its backward one elementwise
 // pass, dx = T(g * invstd) with g = relu_grad(dy).  Thread layout and loads as
-// k_bn_relu_bwd_apply.
+// k_bn_relu_bwd_apply, and its sg.absmax (jr_bn_relu_bwd_frozen_absmax).
 template <typename T>
 __global__ void __launch_bounds__(256) k_bn_relu_bwd_frozen(BnSegs sg, const T* __restrict__ x, int xs, int64_t m,
                                                             int c, const float* __restrict__ mean,
                                                             const float* __restrict__ invstd, T* dx) {
   constexpr int VW = Vec<T>::N;
   const RowLane l = row_lane<T>(c);
-  if (l.rr >= l.rpp) return;
-  const int ch = l.q * VW;
-  const SegGrad<T> sd = seg_grad<T>(sg, ch);
-  const BnConst<VW> k = bn_const<VW>(mean + ch, invstd + ch, sd.beta);
-  row_pass<T, true>(x + ch, xs, sd.dy, sd.stride, dx + ch, xs, l.block_row(blockIdx.x), l.rpp, m,
-                    [=](int j, float xv, float dy) {
-                      return bn_bwd_frozen(relu_grad(bn_xhat(xv, k.mu[j], k.is[j]), k.be[j], dy), k.is[j]);
-                    });
+  float amax = 0.f;
+  if (l.rr < l.rpp) {
+    const int ch = l.q * VW;
+    const SegGrad<T> sd = seg_grad<T>(sg, ch);
+    const BnConst<VW> k = bn_const<VW>(mean + ch, invstd + ch, sd.beta);
+    amax = row_pass<T, true>(x + ch, xs, sd.dy, sd.stride, dx + ch, xs, l.block_row(blockIdx.x), l.rpp, m,
+                             [=](int j, float xv, float dy) {
+                               return bn_bwd_frozen(relu_grad(bn_xhat(xv, k.mu[j], k.is[j]), k.be[j], dy), k.is[j]);
+                             });
+  }
+  if (sg.absmax) block_absmax_to(amax, sg.absmax);   // (uniform: a kernel argument)
 }
 
 // Canonical combine of ONE channel's backward-reduce partials when there are
@@ -566,33 +586,56 @@ JR_API int jr_bn_stats(int dtype, const void* x, int64_t m, int32_t c, float eps
   return check_launch("bn_stats finalize");
 }
 
+// (Guard, guard_limit, guard_word: jr_common.h)
 static int bn_apply_launch(int dtype, int members, const void* x, int32_t x_c_stride, int64_t x_mb, int64_t m,
                            int32_t c, const float* mean, const float* invstd, int64_t st_mb, const float* beta,
-                           int64_t be_mb, void* y, int32_t y_c_off, int32_t y_c_stride, int64_t y_mb, hipStream_t s) {
+                           int64_t be_mb, void* y, int32_t y_c_off, int32_t y_c_stride, int64_t y_mb, float limit,
+                           hipStream_t s) {
+  Guard g;
+  const int rc = guard_word("bn_relu_apply", limit, s, g);
+  if (rc) return rc;
   const dim3 grid(bn_plan(dtype, m, c).apply_grid, members);
   by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(k_bn_relu_apply<T>, grid, dim3(256), 0, s, (const T*)x, x_c_stride, m, c, mean, invstd, beta,
-                       (T*)y, y_c_off, y_c_stride, x_mb, y_mb, st_mb, be_mb);
+    if (!g.err)
+      hipLaunchKernelGGL((k_bn_relu_apply<T, false>), grid, dim3(256), 0, s, (const T*)x, x_c_stride, m, c, mean,
+                         invstd, beta, (T*)y, y_c_off, y_c_stride, x_mb, y_mb, st_mb, be_mb, 0.f, nullptr);
+    else
+      hipLaunchKernelGGL((k_bn_relu_apply<T, true>), grid, dim3(256), 0, s, (const T*)x, x_c_stride, m, c, mean,
+                         invstd, beta, (T*)y, y_c_off, y_c_stride, x_mb, y_mb, st_mb, be_mb, g.limit, g.err);
   });
   return check_launch("bn_relu_apply");
 }
 
-JR_API int jr_bn_relu_apply(int dtype, const void* x, int32_t x_c_off, int32_t x_c_stride, int64_t m, int32_t c,
-                            const float* mean, const float* invstd, const float* beta, void* y, int32_t y_c_off,
-                            int32_t y_c_stride, void* stream) {
+// (limit = 0: jr_bn_relu_apply; > 0: jr_bn_relu_apply_guard)
+static int bn_relu_apply(int dtype, const void* x, int32_t x_c_off, int32_t x_c_stride, int64_t m, int32_t c,
+                         const float* mean, const float* invstd, const float* beta, void* y, int32_t y_c_off,
+                         int32_t y_c_stride, float limit, void* stream) {
   int rc = check_common(dtype, m, c);
   if (rc) return rc;
   if (!x || !mean || !invstd || !beta || !y) return fail(JR_ERR_INVALID, "bn_relu_apply: null pointer");
   if (!check_slice(dtype, x_c_off, x_c_stride, c)) return fail(JR_ERR_INVALID, "bn_relu_apply: bad input slice");
   if (!check_slice(dtype, y_c_off, y_c_stride, c)) return fail(JR_ERR_INVALID, "bn_relu_apply: bad output slice");
   return bn_apply_launch(dtype, 1, at_channel(dtype, x, x_c_off), x_c_stride, 0, m, c, mean, invstd, 0, beta, 0, y,
-                         y_c_off, y_c_stride, 0, as_stream(stream));
+                         y_c_off, y_c_stride, 0, limit, as_stream(stream));
 }
 
-JR_API int jr_bn_relu_apply_multi(int dtype, int nseg, const jr_bn_apply_seg* segs, const void* x, int32_t x_c_off,
-                                  int32_t x_c_stride, int64_t m, int32_t c, const float* mean, const float* invstd,
-                                  void* stream) {
+JR_API int jr_bn_relu_apply(int dtype, const void* x, int32_t x_c_off, int32_t x_c_stride, int64_t m, int32_t c,
+                            const float* mean, const float* invstd, const float* beta, void* y, int32_t y_c_off,
+                            int32_t y_c_stride, void* stream) {
+  return bn_relu_apply(dtype, x, x_c_off, x_c_stride, m, c, mean, invstd, beta, y, y_c_off, y_c_stride, 0.f, stream);
+}
+
+JR_API int jr_bn_relu_apply_guard(int dtype, const void* x, int32_t x_c_off, int32_t x_c_stride, int64_t m, int32_t c,
+                                  const float* mean, const float* invstd, const float* beta, void* y,
+                                  int32_t y_c_off, int32_t y_c_stride, float limit, void* stream) {
+  if (!guard_limit(limit)) return fail(JR_ERR_INVALID, "bn_relu_apply_guard: limit must be finite and > 0");
+  return bn_relu_apply(dtype, x, x_c_off, x_c_stride, m, c, mean, invstd, beta, y, y_c_off, y_c_stride, limit, stream);
+}
+
+static int bn_relu_apply_multi(int dtype, int nseg, const jr_bn_apply_seg* segs, const void* x, int32_t x_c_off,
+                               int32_t x_c_stride, int64_t m, int32_t c, const float* mean, const float* invstd,
+                               float limit, void* stream) {
   int rc = check_common(dtype, m, c);
   if (rc) return rc;
   if (!segs || nseg < 1 || nseg > kMaxSegs) return fail(JR_ERR_INVALID, "bn_relu_apply_multi: 1..4 segments");
@@ -604,12 +647,32 @@ JR_API int jr_bn_relu_apply_multi(int dtype, int nseg, const jr_bn_apply_seg* se
   x = at_channel(dtype, x, x_c_off);
   const dim3 grid(bn_plan(dtype, m, c).apply_grid);
   hipStream_t s = as_stream(stream);
+  Guard g;
+  rc = guard_word("bn_relu_apply_multi", limit, s, g);
+  if (rc) return rc;
   by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(k_bn_relu_apply_multi<T>, grid, dim3(256), 0, s, (const T*)x, x_c_stride, m, c, mean, invstd,
-                       sg);
+    if (!g.err)
+      hipLaunchKernelGGL((k_bn_relu_apply_multi<T, false>), grid, dim3(256), 0, s, (const T*)x, x_c_stride, m, c, mean,
+                         invstd, sg, 0.f, nullptr);
+    else
+      hipLaunchKernelGGL((k_bn_relu_apply_multi<T, true>), grid, dim3(256), 0, s, (const T*)x, x_c_stride, m, c, mean,
+                         invstd, sg, g.limit, g.err);
   });
   return check_launch("bn_relu_apply_multi");
+}
+
+JR_API int jr_bn_relu_apply_multi(int dtype, int nseg, const jr_bn_apply_seg* segs, const void* x, int32_t x_c_off,
+                                  int32_t x_c_stride, int64_t m, int32_t c, const float* mean, const float* invstd,
+                                  void* stream) {
+  return bn_relu_apply_multi(dtype, nseg, segs, x, x_c_off, x_c_stride, m, c, mean, invstd, 0.f, stream);
+}
+
+JR_API int jr_bn_relu_apply_multi_guard(int dtype, int nseg, const jr_bn_apply_seg* segs, const void* x,
+                                        int32_t x_c_off, int32_t x_c_stride, int64_t m, int32_t c, const float* mean,
+                                        const float* invstd, float limit, void* stream) {
+  if (!guard_limit(limit)) return fail(JR_ERR_INVALID, "bn_relu_apply_multi_guard: limit must be finite and > 0");
+  return bn_relu_apply_multi(dtype, nseg, segs, x, x_c_off, x_c_stride, m, c, mean, invstd, limit, stream);
 }
 
 JR_API int jr_bn_relu_apply_stats(int dtype, const void* x, int32_t x_c_off, int32_t x_c_stride, int64_t m, int32_t c,
@@ -637,11 +700,11 @@ JR_API int jr_bn_relu_apply_stats(int dtype, const void* x, int32_t x_c_off, int
   return check_launch("bn_relu_apply_stats");
 }
 
-JR_API int jr_bn_relu_apply_grouped(int dtype, int32_t members, const void* x, int32_t x_c_off, int32_t x_c_stride,
-                                    int64_t x_member_stride, int64_t m, int32_t c, const float* mean,
-                                    const float* invstd, int64_t stats_member_stride, const float* beta,
-                                    int64_t beta_member_stride, void* y, int32_t y_c_off, int32_t y_c_stride,
-                                    int64_t y_member_stride, void* stream) {
+static int bn_relu_apply_grouped(int dtype, int32_t members, const void* x, int32_t x_c_off, int32_t x_c_stride,
+                                 int64_t x_member_stride, int64_t m, int32_t c, const float* mean,
+                                 const float* invstd, int64_t stats_member_stride, const float* beta,
+                                 int64_t beta_member_stride, void* y, int32_t y_c_off, int32_t y_c_stride,
+                                 int64_t y_member_stride, float limit, void* stream) {
   int rc = check_common(dtype, m, c);
   if (rc) return rc;
   if (members < 1 || members > 65535) return fail(JR_ERR_INVALID, "bn_relu_apply_grouped: members must be 1..65535");
@@ -655,7 +718,28 @@ JR_API int jr_bn_relu_apply_grouped(int dtype, int32_t members, const void* x, i
     return fail(JR_ERR_INVALID, "bn_relu_apply_grouped: member strides must be 16-byte multiples");
   return bn_apply_launch(dtype, members, at_channel(dtype, x, x_c_off), x_c_stride, x_member_stride * esz, m, c, mean,
                          invstd, stats_member_stride * 4, beta, beta_member_stride * 4, y, y_c_off, y_c_stride,
-                         y_member_stride * esz, as_stream(stream));
+                         y_member_stride * esz, limit, as_stream(stream));
+}
+
+JR_API int jr_bn_relu_apply_grouped(int dtype, int32_t members, const void* x, int32_t x_c_off, int32_t x_c_stride,
+                                    int64_t x_member_stride, int64_t m, int32_t c, const float* mean,
+                                    const float* invstd, int64_t stats_member_stride, const float* beta,
+                                    int64_t beta_member_stride, void* y, int32_t y_c_off, int32_t y_c_stride,
+                                    int64_t y_member_stride, void* stream) {
+  return bn_relu_apply_grouped(dtype, members, x, x_c_off, x_c_stride, x_member_stride, m, c, mean, invstd,
+                               stats_member_stride, beta, beta_member_stride, y, y_c_off, y_c_stride, y_member_stride,
+                               0.f, stream);
+}
+
+JR_API int jr_bn_relu_apply_grouped_guard(int dtype, int32_t members, const void* x, int32_t x_c_off,
+                                          int32_t x_c_stride, int64_t x_member_stride, int64_t m, int32_t c,
+                                          const float* mean, const float* invstd, int64_t stats_member_stride,
+                                          const float* beta, int64_t beta_member_stride, void* y, int32_t y_c_off,
+                                          int32_t y_c_stride, int64_t y_member_stride, float limit, void* stream) {
+  if (!guard_limit(limit)) return fail(JR_ERR_INVALID, "bn_relu_apply_grouped_guard: limit must be finite and > 0");
+  return bn_relu_apply_grouped(dtype, members, x, x_c_off, x_c_stride, x_member_stride, m, c, mean, invstd,
+                               stats_member_stride, beta, beta_member_stride, y, y_c_off, y_c_stride, y_member_stride,
+                               limit, stream);
 }
 
 // The apply pass of the backward (k1, k2 from a finalize).
@@ -737,9 +821,17 @@ JR_API int jr_bn_relu_bwd_multi_absmax(int dtype, int nseg, const jr_bn_seg* seg
 JR_API int jr_bn_relu_bwd_frozen(int dtype, int nseg, const jr_bn_seg* segs, const void* x, int32_t x_c_off,
                                  int32_t x_c_stride, int64_t m, int32_t c, const float* mean, const float* invstd,
                                  void* dx, void* stream) {
+  return jr_bn_relu_bwd_frozen_absmax(dtype, nseg, segs, x, x_c_off, x_c_stride, m, c, mean, invstd, dx, nullptr,
+                                      stream);
+}
+
+JR_API int jr_bn_relu_bwd_frozen_absmax(int dtype, int nseg, const jr_bn_seg* segs, const void* x, int32_t x_c_off,
+                                        int32_t x_c_stride, int64_t m, int32_t c, const float* mean,
+                                        const float* invstd, void* dx, float* dx_absmax, void* stream) {
   BnSegs sg;
   const int rc = bwd_setup(dtype, nseg, segs, x, x_c_off, x_c_stride, m, c, mean, invstd, dx, sg, false);
   if (rc) return rc;
+  sg.absmax = dx_absmax;
   const dim3 grid(bn_plan(dtype, m, c).apply_grid);
   hipStream_t s = as_stream(stream);
   by_dtype(dtype, [&](auto t) {

@@ -2,7 +2,8 @@
 // max-pools (jr_pool.hip) share, each written once: the 16-byte channel vector
 // and thread layout of the BN passes, the per-element BN + ReLU expressions
 // (forward, ReLU-masked gradient, the two backwards), the elementwise row pass,
-// the 3x3 stride-2 window scan and the 2x2-cell backward gather.  The bits of
+// the block maximum and bound guard, the 3x3 stride-2 window scan and the
+// 2x2-cell backward gather.  The bits of
 // everything built from them are pinned by tests/golden/bn_bits.json.
 #pragma once
 #include "jr_common.h"
@@ -177,18 +178,45 @@ __device__ __forceinline__ float row_pass(const T* __restrict__ x, int xs, const
   return amax;
 }
 
+// ---- block maximum and the bound guard -------------------------------------
+// The block's max of v (every value >= 0; fmaxf drops a NaN), valid in thread
+// 0.  Every thread of the block calls it, once per kernel.
+__device__ __forceinline__ float block_max(float v) {
+  __shared__ float s_max[4];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float b = 0.f;
+  if (threadIdx.x == 0) {
+    b = s_max[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) b = fmaxf(b, s_max[w]);
+  }
+  return b;
+}
+// The guard of the *_guard entry points (jr.h): v is the largest magnitude the
+// thread stored; a block whose largest is not <= limit counts one failure into
+// the device error word (the predicate of k_absmax_segs: +inf trips it, a NaN
+// the fmaxf dropped does not).  Every thread of the block calls it.
+__device__ __forceinline__ void block_guard(float v, float limit, unsigned* err) {
+  const float b = block_max(v);
+  if (threadIdx.x == 0 && !(b <= limit)) atomicAdd(err, 1u);
+}
+
 // ---- max-pool 3x3 stride 2 'valid' ------------------------------------------
 // Forward: a grid-stride loop (elements first, first + step, ...: the kernel
 // reads its own block and grid size) over (output pixel, channel quad); each
 // window is scanned in (r, c) order and the first maximum wins (argmax 0..8).
 // taps(b, q) returns the per-tap transform a = tap(j, v) of image b's channel
 // quad q: the identity for the plain pool, BN + ReLU + rounding to the path
-// dtype for the fused one.
+// dtype for the fused one.  Returns the largest |y| this thread stored (0 if
+// none; unused: eliminated).
 template <typename T, typename Taps>
-__device__ __forceinline__ void maxpool_scan(const jr_pool_desc& d, const T* __restrict__ x, T* y, uint8_t* argmax,
+__device__ __forceinline__ float maxpool_scan(const jr_pool_desc& d, const T* __restrict__ x, T* y, uint8_t* argmax,
                                              int first, int step, Taps taps) {
   const int c4 = d.c >> 2;
   const int total = d.n * d.ho * d.wo * c4;
+  float amax = 0.f;
   for (int e = first; e < total; e += step) {
     const int q = e % c4;
     const int pix = e / c4;
@@ -214,12 +242,15 @@ __device__ __forceinline__ void maxpool_scan(const jr_pool_desc& d, const T* __r
       }
     }
     P4<T>::st(y + (int64_t)pix * d.y_c_stride + d.y_c_off + q * 4, make_float4(best[0], best[1], best[2], best[3]));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(best[j]));
     if (argmax) {
       const uint32_t packed = (uint32_t)arg[0] | ((uint32_t)arg[1] << 8) | ((uint32_t)arg[2] << 16) |
                               ((uint32_t)arg[3] << 24);
       *reinterpret_cast<uint32_t*>(argmax + (int64_t)pix * d.c + q * 4) = packed;
     }
   }
+  return amax;
 }
 
 // Backward as a gather over 2x2 input cells: input rows 2a, 2a+1 and columns

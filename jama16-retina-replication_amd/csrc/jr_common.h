@@ -29,6 +29,24 @@ unsigned* stream_scratch(hipStream_t s, int kind, size_t words);
 // clears it.  Allocated by jr_init (or on first use outside a capture).
 unsigned* device_error_word(hipStream_t s);
 
+// The *_guard entry points (jr.h): each checks its limit (finite, > 0) before
+// anything else, then shares the unguarded call's validation and launcher,
+// which takes limit = 0 for "no guard" and fetches the error word last, as
+// jr_absmax_prep does.
+inline bool guard_limit(float limit) { return limit > 0.f && limit < __builtin_inff(); }
+struct Guard {
+  float limit = 0.f;
+  unsigned* err = nullptr;   // non-NULL: launch the GUARD kernel
+};
+inline int guard_word(const char* what, float limit, hipStream_t s, Guard& g) {
+  g = Guard{};
+  if (!(limit > 0.f)) return JR_OK;
+  g.limit = limit;
+  g.err = device_error_word(s);
+  if (!g.err) return fail(JR_ERR_HIP, std::string(what) + ": no device error word (call jr_init before capturing)");
+  return JR_OK;
+}
+
 // Bijective XCD-aware remap of a flat workgroup id (cdna_hip_programming.md
 // §5 "XCD swizzle must be bijective"): blocks b, b+8, b+16 ... are dealt to one
 // XCD by the dispatcher, so consecutive remapped ids land on one XCD's L2.

@@ -409,6 +409,16 @@ JR_API int jr_absmax_prep(const float* src, const jr_absmax_seg* segs, int32_t n
   return check_launch("absmax_prep");
 }
 
+// jr_absmax_prep's memset alone: absmax words that a launch list raises anew
+// on every run (the frozen backward's data-gradient rows) start from zero.
+JR_API int jr_absmax_reset(float* rows, int64_t n_floats, void* stream) {
+  if (!rows || n_floats < 0) return fail(JR_ERR_INVALID, "absmax_reset: bad arguments");
+  if (n_floats == 0) return JR_OK;
+  if (hipMemsetAsync(rows, 0, (size_t)n_floats * sizeof(float), as_stream(stream)) != hipSuccess)
+    return fail(JR_ERR_HIP, "absmax_reset: memset failed");
+  return JR_OK;
+}
+
 JR_API int jr_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
   if (!src || !dst || n < 0) return fail(JR_ERR_INVALID, "cast: bad arguments");
   if (n == 0) return JR_OK;

@@ -33,14 +33,19 @@ __global__ void __launch_bounds__(256) k_maxpool_fwd(jr_pool_desc d, const T* __
 // bitwise the two-kernel result, without writing and re-reading the
 // full-resolution activation (354 / 248 MB per fp32 step).  Grouped
 // (ensemble members): image b belongs to member b / ipm, whose statistics
-// and beta sit st_mb / be_mb floats further (0 for one member).
-template <typename T>
+// and beta sit st_mb / be_mb floats further (0 for one member).  GUARD (the
+// *_guard entry points): block_guard over the pooled values the block stored
+// -- what the next conv reads; a tap that no window covers, or that loses its
+// window, is never stored.
+template <typename T, bool GUARD>
 __global__ void __launch_bounds__(256) k_bn_relu_maxpool_fwd(jr_pool_desc d, const T* __restrict__ x,
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ invstd,
                                                              const float* __restrict__ beta, T* y, uint8_t* argmax,
-                                                             int ipm, long long st_mb, long long be_mb) {
-  maxpool_scan(d, x, y, argmax, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, [=](int b, int q) {
+                                                             int ipm, long long st_mb, long long be_mb, float limit,
+                                                             unsigned* err) {
+  const int first = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+  const float amax = maxpool_scan(d, x, y, argmax, first, step, [=](int b, int q) {
     // (the member's statistics and beta, then the tap: the value k_bn_relu_apply stores)
     const long long mem = b / ipm;
     const BnConst<4> k = bn_const<4>(mean + mem * st_mb + q * 4, invstd + mem * st_mb + q * 4,
@@ -50,6 +55,7 @@ __global__ void __launch_bounds__(256) k_bn_relu_maxpool_fwd(jr_pool_desc d, con
       return sizeof(T) == 2 ? bf2f(f2bf(a)) : a;
     };
   });
+  if (GUARD) block_guard(amax, limit, err);
 }
 
 // (the gather: maxpool_bwd_cell)
@@ -233,31 +239,65 @@ JR_API int jr_maxpool3x3s2_fwd(const jr_pool_desc* d, int dtype, const void* x, 
   return check_launch("maxpool_fwd");
 }
 
-JR_API int jr_bn_relu_maxpool3x3s2_fwd_grouped(const jr_pool_desc* d, int dtype, int32_t images_per_member,
-                                               const void* raw, const float* mean, const float* invstd,
-                                               int64_t stats_member_stride, const float* beta,
-                                               int64_t beta_member_stride, void* y, uint8_t* argmax, void* stream) {
+// (limit = 0: the unguarded entry points; > 0: their *_guard forms)
+static int bn_relu_maxpool_fwd(const jr_pool_desc* d, int dtype, int32_t images_per_member, const void* raw,
+                               const float* mean, const float* invstd, int64_t stats_member_stride, const float* beta,
+                               int64_t beta_member_stride, void* y, uint8_t* argmax, float limit, void* stream) {
   int rc = check_pool(d, dtype, true);
   if (rc) return rc;
   if (!raw || !mean || !invstd || !beta || !y) return fail(JR_ERR_INVALID, "bn_relu_maxpool_fwd: null pointer");
   if (images_per_member < 1 || d->n % images_per_member != 0 || stats_member_stride < 0 || beta_member_stride < 0)
     return fail(JR_ERR_INVALID, "bn_relu_maxpool_fwd: images_per_member must divide n; strides >= 0");
   const int g = grid_for((int64_t)d->n * d->ho * d->wo * (d->c / 4));
+  hipStream_t s = as_stream(stream);
+  Guard gd;
+  rc = guard_word("bn_relu_maxpool_fwd", limit, s, gd);
+  if (rc) return rc;
   by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(k_bn_relu_maxpool_fwd<T>, dim3(g), dim3(256), 0, as_stream(stream), *d, (const T*)raw, mean,
-                       invstd, beta, (T*)y, argmax, images_per_member, (long long)stats_member_stride,
-                       (long long)beta_member_stride);
+    if (!gd.err)
+      hipLaunchKernelGGL((k_bn_relu_maxpool_fwd<T, false>), dim3(g), dim3(256), 0, s, *d, (const T*)raw, mean, invstd,
+                         beta, (T*)y, argmax, images_per_member, (long long)stats_member_stride,
+                         (long long)beta_member_stride, 0.f, nullptr);
+    else
+      hipLaunchKernelGGL((k_bn_relu_maxpool_fwd<T, true>), dim3(g), dim3(256), 0, s, *d, (const T*)raw, mean, invstd,
+                         beta, (T*)y, argmax, images_per_member, (long long)stats_member_stride,
+                         (long long)beta_member_stride, gd.limit, gd.err);
   });
   return check_launch("bn_relu_maxpool_fwd");
+}
+
+JR_API int jr_bn_relu_maxpool3x3s2_fwd_grouped(const jr_pool_desc* d, int dtype, int32_t images_per_member,
+                                               const void* raw, const float* mean, const float* invstd,
+                                               int64_t stats_member_stride, const float* beta,
+                                               int64_t beta_member_stride, void* y, uint8_t* argmax, void* stream) {
+  return bn_relu_maxpool_fwd(d, dtype, images_per_member, raw, mean, invstd, stats_member_stride, beta,
+                             beta_member_stride, y, argmax, 0.f, stream);
+}
+
+JR_API int jr_bn_relu_maxpool3x3s2_fwd_grouped_guard(const jr_pool_desc* d, int dtype, int32_t images_per_member,
+                                                     const void* raw, const float* mean, const float* invstd,
+                                                     int64_t stats_member_stride, const float* beta,
+                                                     int64_t beta_member_stride, void* y, uint8_t* argmax, float limit,
+                                                     void* stream) {
+  if (!guard_limit(limit)) return fail(JR_ERR_INVALID, "bn_relu_maxpool_fwd_guard: limit must be finite and > 0");
+  return bn_relu_maxpool_fwd(d, dtype, images_per_member, raw, mean, invstd, stats_member_stride, beta,
+                             beta_member_stride, y, argmax, limit, stream);
 }
 
 JR_API int jr_bn_relu_maxpool3x3s2_fwd(const jr_pool_desc* d, int dtype, const void* raw, const float* mean,
                                        const float* invstd, const float* beta, void* y, uint8_t* argmax,
                                        void* stream) {
   if (!d) return fail(JR_ERR_INVALID, "pool: null descriptor");
-  return jr_bn_relu_maxpool3x3s2_fwd_grouped(d, dtype, d->n > 0 ? d->n : 1, raw, mean, invstd, 0, beta, 0, y,
-                                             argmax, stream);
+  return bn_relu_maxpool_fwd(d, dtype, d->n > 0 ? d->n : 1, raw, mean, invstd, 0, beta, 0, y, argmax, 0.f, stream);
+}
+
+JR_API int jr_bn_relu_maxpool3x3s2_fwd_guard(const jr_pool_desc* d, int dtype, const void* raw, const float* mean,
+                                             const float* invstd, const float* beta, void* y, uint8_t* argmax,
+                                             float limit, void* stream) {
+  if (!guard_limit(limit)) return fail(JR_ERR_INVALID, "bn_relu_maxpool_fwd_guard: limit must be finite and > 0");
+  if (!d) return fail(JR_ERR_INVALID, "pool: null descriptor");
+  return bn_relu_maxpool_fwd(d, dtype, d->n > 0 ? d->n : 1, raw, mean, invstd, 0, beta, 0, y, argmax, limit, stream);
 }
 
 JR_API int jr_maxpool3x3s2_bwd(const jr_pool_desc* d, int dtype, const uint8_t* argmax, const void* dy,

@@ -15,7 +15,8 @@ batch-32 buffers, a few GB per member against 288 GB of HBM), and each test
 batch is decoded once and run through all members -- the same batches, so
 the same batch-statistics BN (App. C Q1) and the same predictions.
 
-Not in the reference: --bn moving (frozen BN), --tta, and --attribution
+Not in the reference: --bn moving (frozen BN; --x6h_frozen keeps the x6h
+arithmetic there, guarded on the GPU), --tta, and --attribution
 {gradient,integrated} --attribution_dir DIR, which under --bn moving also
 writes per-image saliency maps of the logit (jr.attribution): DIR/maps_<k>.npy
 per test batch k (float32 [n, h, w], the mean over members) and DIR/index.csv
@@ -65,6 +66,14 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--attribution requires --attribution_dir DIR")
             if a.attribution_steps < 1:
                 self.error("--attribution_steps must be at least 1")
+        if a.x6h_frozen:
+            if a.bn != "moving":
+                self.error("--x6h_frozen requires --bn moving: it is the guarded frozen-BN forward of x6h (with batch "
+                           "statistics x6h needs no guard)")
+            if a.dtype != "f32":
+                self.error("--x6h_frozen requires --dtype f32: x6h is an fp32 convolution arithmetic")
+            if a.conv_math != "x6h":
+                self.error("--x6h_frozen requires --conv_math x6h (the default)")
         return a
 
 
@@ -103,6 +112,17 @@ def build_parser():
                         "--bn_calibrate_batches batches of the tfrecords in DIR (for checkpoints trained without "
                         "--bn_moving; in memory, nothing is written)")
     p.add_argument("--bn_calibrate_batches", type=int, default=16, metavar="K")
+    p.add_argument("--x6h_frozen", action="store_true",
+                   help="with --bn moving, --dtype f32 and --conv_math x6h: keep x6h under the frozen statistics "
+                        "instead of falling back to x8.  The activation scale stays the engine's constant bound, and "
+                        "every BN + ReLU output is checked against it on the GPU as it is stored: predictions are "
+                        "bitwise independent of the other images of the batch, and an activation above the bound "
+                        "stops the run with an error (repeat it without this flag) instead of saturating fp16.  The "
+                        "x6h input gradient of --attribution scales each layer's gradient by its measured per-batch "
+                        "maximum, so maps are batch-independent to within the x6h error class, not bitwise.  Measured "
+                        "(profiles/frozen_x6h.txt, 299^2, batch 32): the grouped 10-member frozen forward is 4-7 %% "
+                        "faster than on x8; one engine per member (--per_member, --attribution) is about 2x slower "
+                        "on x6h than on x8, frozen or not")
     # test-time augmentation (not in the reference, which scores one view of every image)
     p.add_argument("--tta", default="none", choices=["none", "flips", "d4"],
                    help="average every member's prediction over views of each test batch, resampled on the GPU: "
@@ -140,25 +160,27 @@ def expand_model_paths(load_model_path: str):
     return [load_model_path]
 
 
-def make_engines(paths, meta, batch_size, device=0, conv_math="x6h", dtype="f32", grouped=False, input_grad=False):
+def make_engines(paths, meta, batch_size, device=0, conv_math="x6h", dtype="f32", grouped=False, input_grad=False,
+                 x6h_frozen=False):
     """The ensemble's inference engines, parameters loaded; conv tiles from
     the committed MI355X table of the eval workload (tiles="pinned"; the
     heuristic where none matches): every member and every run sums in the
     same order.  grouped: ONE jr.ensemble.EnsembleEngine holding every member
     (one launch per layer for all members); else one jr.Engine per member
-    (input_grad: each with the buffers of Engine.input_gradient)."""
+    (input_grad: each with the buffers of Engine.input_gradient).
+    x6h_frozen: the engines' guarded frozen forward on x6h (--x6h_frozen)."""
     from jr import checkpoint
     from jr.engine import Engine
     if grouped and conv_math != "x8p":
         from jr.ensemble import EnsembleEngine
         params = [checkpoint.load(path, None)[0] for path in paths]
         return EnsembleEngine(params, batch_size, meta["height"], meta["width"], meta.get("units", 1), device=device,
-                              dtype=dtype, conv_math=conv_math if dtype == "f32" else "bf16")
+                              dtype=dtype, conv_math=conv_math if dtype == "f32" else "bf16", x6h_frozen=x6h_frozen)
     engines = []
     for path in paths:
         eng = Engine(batch_size, meta["height"], meta["width"], meta.get("units", 1), device=device,
                      train=False, dtype=dtype, conv_math=conv_math if dtype == "f32" else "bf16",
-                     input_grad=input_grad)
+                     input_grad=input_grad, x6h_frozen=x6h_frozen)
         flat, _ = checkpoint.load(path, eng.g)
         eng.load_params(flat)
         engines.append(eng)
@@ -346,7 +368,7 @@ def main(argv=None):
         return 2
 
     import torch
-    from jr import checkpoint
+    from jr import _ffi, checkpoint
 
     load_model_paths = expand_model_paths(str(args.load_model_path))
     batch_size = int(args.batch_size)
@@ -394,7 +416,7 @@ Using operating treshold: {},
             from jr.inception import build_inception_v3
             bn_stats, bn_info = load_bn_stats(load_model_paths, build_inception_v3(
                 meta["height"], meta["width"], meta.get("units", 1)))
-        if args.dtype == "f32" and conv_math == "x6h":
+        if args.dtype == "f32" and conv_math == "x6h" and not args.x6h_frozen:
             conv_math = "x8"
             if rank == 0:
                 print("--bn moving: conv_math x8 is used instead of x6h (x6h scales activations by a bound that "
@@ -407,7 +429,7 @@ Using operating treshold: {},
                   f"buffers; maps to {attribution['dir']}", file=sys.stderr)
     engines = make_engines(load_model_paths, meta, batch_size, device=local, conv_math=conv_math,
                            dtype=args.dtype, grouped=not (args.per_member or attribution),
-                           input_grad=attribution is not None)
+                           input_grad=attribution is not None, x6h_frozen=args.x6h_frozen)
     if args.bn == "moving":
         k = freeze_engines(engines, bn_stats, args.bn_calibrate_dir, args.bn_calibrate_batches, batch_size)
         if rank == 0 and bn_info is not None:
@@ -416,9 +438,15 @@ Using operating treshold: {},
             print(f"BN statistics: moving (calibrated on {k} batches of {args.bn_calibrate_dir})")
     if args.tta != "none" and rank == 0:
         print(f"Test-time augmentation: {args.tta} ({n_views} views)")
-    preds, labels, order = predict_all(engines, data_dir, batch_size, rank, world,
-                                       bn="frozen" if args.bn == "moving" else "batch", tta=args.tta,
-                                       attribution=attribution)
+    try:
+        preds, labels, order = predict_all(engines, data_dir, batch_size, rank, world,
+                                           bn="frozen" if args.bn == "moving" else "batch", tta=args.tta,
+                                           attribution=attribution)
+    except _ffi.JRError as e:
+        if args.x6h_frozen and e.status == _ffi.JR_ERR_DEVICE:     # the guard; no retry on another path here
+            print("--x6h_frozen: an activation exceeded the x6h bound under the frozen BN statistics; the "
+                  "predictions are invalid -- repeat the run without --x6h_frozen (x8)", file=sys.stderr)
+        raise
 
     if dist:   # gather every rank's batches to rank 0, restore dataset order
         gathered = [None] * world

@@ -190,7 +190,23 @@ _SIGS = {
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "jr_bn_relu_bwd_frozen": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the guarded forms (jr.h): the unguarded signature with `float limit` before the stream
+    "jr_bn_relu_apply_guard": (c_int, [c_int, c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
+    "jr_bn_relu_apply_multi_guard": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32,
+                                             c_void_p, c_void_p, c_float, c_void_p]),
+    "jr_bn_relu_apply_grouped_guard": (c_int, [c_int, c_int32, c_void_p, c_int32, c_int32, c_int64, c_int64, c_int32,
+                                               c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32,
+                                               c_int32, c_int64, c_float, c_void_p]),
+    "jr_bn_relu_maxpool3x3s2_fwd_guard": (c_int, [POINTER(PoolDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_float, c_void_p]),
+    "jr_bn_relu_maxpool3x3s2_fwd_grouped_guard": (c_int, [POINTER(PoolDesc), c_int, c_int32, c_void_p, c_void_p,
+                                                          c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                                          c_float, c_void_p]),
+    "jr_bn_relu_bwd_frozen_absmax": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jr_absmax_prep": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    "jr_absmax_reset": (c_int, [c_void_p, c_int64, c_void_p]),
     "jr_bn_moving_update": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                                     c_float, c_float, c_void_p]),
     "jr_bn_moving_freeze": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
@@ -331,8 +347,9 @@ def device_check() -> None:
     """jr_device_check on the current device (after the caller synchronised
     its streams): raise JRError when a stream-K hand-off count word was not
     left zero (counted past its piece count by a launch, or found stale on an
-    idle stream); the library has then reset its hand-off words, so later
-    launches are correct again."""
+    idle stream), or a magnitude guard counted a failure (jr_absmax_prep's
+    limit, a *_guard entry point's); the library has then reset its hand-off
+    words and the count, so later launches are correct again."""
     check("jr_device_check", load().jr_device_check())
 
 

@@ -14,6 +14,14 @@ d logit_i / d x_i is a property of image i.
 Every step is a libjr call (jr.h: jr_attr_scale_input, jr_attr_accumulate,
 jr_attr_map) around Engine.forward(bn="frozen") and Engine.input_gradient;
 their fp32 arithmetic is stated there and restated in tests/attribution_ref.py.
+
+conv_math="x6h" engines need x6h_frozen=True (jr.Engine) and then work
+unchanged: integrated gradients scale the image by alpha <= 1, which stays
+inside the image bound x_bound = 1 of the first conv, and every forward is the
+guarded one.  The x6h data gradients scale each layer's dy by its measured
+per-batch maximum (a gradient has no a-priori bound), so an x6h map of an image
+depends on the rest of its batch within the x6h error class -- not bitwise
+independent, as the x8 / f32 maps and the x6h predictions are.
 """
 from __future__ import annotations
 

@@ -20,12 +20,19 @@ that step, MI355X-native:
 * Optional (bn_moving=momentum): one more launch per step keeps Keras-style
   moving averages of every BN layer's batch statistics (jr_bn_moving_update);
   freeze_bn() + forward(bn="frozen") then normalise with fixed statistics, so
-  an image's output depends on that image alone.
+  an image's output depends on that image alone.  conv_math="x6h" takes part
+  only with x6h_frozen=True: the frozen lists then store every activation
+  through the guarded entry points (Replica._frozen_guard: a constant scale,
+  predictions bitwise batch-independent, an activation above the bound raises
+  JRError(JR_ERR_DEVICE) at the next synchronize() / predictions()).
 * Optional (input_grad=True): a third call list, the data-gradient chain of
   one logit per image down to the image after a frozen forward
   (input_gradient: jr_head_logit_bwd, jr_bn_relu_bwd_frozen, the data
   gradients, jr_conv2d_bwd_image) -- what jr.attribution builds saliency maps
-  from.  No filter gradients, no optimizer, no training buffers.
+  from.  No filter gradients, no optimizer, no training buffers.  On x6h
+  (x6h_frozen=True) the frozen BN backward also measures max |dx| per launch
+  (jr_bn_relu_bwd_frozen_absmax, the dy scale of its data gradient): that
+  gradient is batch-independent within the x6h error class, not bitwise.
 * Data parallel: gradients are all-reduced (torch.distributed backend 'nccl' =
   RCCL over xGMI) in buckets issued during the backward pass, in reverse layer
   order, so communication overlaps the remaining backward kernels.
@@ -97,7 +104,7 @@ class Replica:
     members = 1
 
     def __init__(self, graph: Graph, device, dtype: str, conv_math: Optional[str], maths: Tuple[str, ...], head: str,
-                 fuse_siblings: bool, fuse_pool: Optional[bool], lanes: int, priorities=()):
+                 fuse_siblings: bool, fuse_pool: Optional[bool], lanes: int, priorities=(), x6h_frozen: bool = False):
         if dtype not in DTYPES:
             raise ValueError(f"dtype must be one of {sorted(DTYPES)}")
         if conv_math is None:            # fp32 default: x8 (fp32-accurate, on the bf16 matrix cores)
@@ -105,6 +112,9 @@ class Replica:
         if conv_math not in (maths if dtype == "f32" else ("bf16",)):
             raise ValueError(f"conv_math: one of {maths} for dtype f32 (x8 = JR_F32_X8, x8p = JR_F32_X8P on pre-split "
                              "operand planes, x6h = JR_F32_X6H scaled fp16 split, f32 = fp32 MFMA); 'bf16' for bf16")
+        if x6h_frozen and conv_math != "x6h":
+            raise ValueError("x6h_frozen=True is the guarded frozen forward of conv_math='x6h' "
+                             f"(this engine: conv_math={conv_math!r})")
         if not torch.cuda.is_available():
             raise RuntimeError(f"jr.{type(self).__name__} needs a ROCm GPU (libjr has no CPU path)")
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
@@ -123,6 +133,13 @@ class Replica:
         # activations from the bound |relu(xhat + beta)| <= sqrt(N - 1) +
         # max |beta| (Samuelson), beta guarded on the device (jr.h)
         self.x6h = conv_math == "x6h"
+        # x6h_frozen (opt-in): frozen-BN forwards (and the input gradient) run on
+        # x6h too.  Samuelson's bound does not hold for values normalised with
+        # fixed statistics, so the frozen call lists store every activation
+        # through the *_guard entry points instead (_frozen_guard), which keep
+        # the constant scale of act_bound and report an activation above it
+        # through jr_device_check (synchronize / predictions: JR_ERR_DEVICE)
+        self.x6h_frozen = bool(x6h_frozen)
         self.cdt = {"x8": _ffi.JR_F32_X8, "x8p": _ffi.JR_F32_X8P, "x6h": _ffi.JR_F32_X6H}.get(conv_math, self.dt)
         # activation dtype: fp32, or bf16 (parameters, gradients, momentum,
         # BN statistics and the head stay fp32 master copies either way)
@@ -224,6 +241,22 @@ class Replica:
                                 beta_row, self.act_bound) for m in range(M) for u in self.cunits for n in u.members]
         self.absmax_table = self._table(_ffi.AbsmaxSeg, segs)
         self.absmax_nseg = len(segs)
+
+    def _frozen_guard(self) -> Optional[float]:
+        """The limit of the guarded BN applies and fused stem pools of a frozen
+        call list (x6h_frozen), or None: the unguarded entry points.
+
+        limit = 2 * act_bound.  act_bound is a power of two m, so the convs'
+        activation scale is exactly 2^14 / m (jr.h): values up to 2 m still
+        split exactly and fp16 saturates only near 4 m -- the margin the beta
+        guard of _alloc_absmax keeps for the batch-statistics forward.  Every
+        conv input is covered: the image is <= 1 (x_bound = 1); every BN + ReLU
+        output is stored by a guarded call; and the max- and average-pools
+        (mixed3 / mixed8 included) read non-negative guarded values, whose
+        maximum or mean never exceeds them, so the pools need no guard of
+        their own.  The scale is a constant, not a measurement: a frozen x6h
+        prediction stays bitwise independent of the other images of the batch."""
+        return 2.0 * self.act_bound if self.x6h and self.x6h_frozen else None
 
     def _wmax(self, u: ConvUnit) -> int:
         return self.absmax.data_ptr() + 4 * 64 * self._arow[u.first.idx] * self.members
@@ -422,7 +455,7 @@ class Replica:
             return False
         if bn != "frozen":
             raise ValueError("forward: bn is 'batch' or 'frozen'")
-        if self.x6h:
+        if self.x6h and not self.x6h_frozen:
             raise ValueError("bn='frozen' is not available with conv_math='x6h': its activation scale rests on the "
                              "bound |relu(xhat + beta)| <= sqrt(N - 1) + max |beta| of values standardised by their "
                              "own batch, which frozen statistics void; use x8, x8p, f32 or bf16")
@@ -443,7 +476,8 @@ class Engine(Replica):
                  head: str = "sigmoid", seed: int = 0, graph: Optional[Graph] = None,
                  autotune: bool = False, tiles: str = "pinned", fuse_siblings: bool = True, lanes: int = 2,
                  conv_math: Optional[str] = None, defer_wgrad: Optional[bool] = None, fuse_pool: Optional[bool] = None,
-                 fold_stats: Optional[bool] = None, bn_moving: Optional[float] = None, input_grad: bool = False):
+                 fold_stats: Optional[bool] = None, bn_moving: Optional[float] = None, input_grad: bool = False,
+                 x6h_frozen: bool = False):
         # bn_moving: None, or the momentum of the moving averages of the BN
         # statistics every training step then updates (Keras: 0.99)
         if bn_moving is not None and not 0.0 <= float(bn_moving) <= 1.0:
@@ -463,7 +497,7 @@ class Engine(Replica):
         prio = os.environ.get("JR_LANE_PRIORITY", "-1,0" if dtype == "f32" else "")
         super().__init__(graph or build_inception_v3(height, width, units), device, dtype, conv_math,
                          ("x8", "x8p", "x6h", "f32"), head, fuse_siblings, fuse_pool, lanes,
-                         [int(v) for v in prio.split(",") if v.strip()])
+                         [int(v) for v in prio.split(",") if v.strip()], x6h_frozen=x6h_frozen)
         self.batch, self.train_mode = batch, train
         self._data_grads = train or self.input_grad     # gradient buffers and data-gradient plans exist
         self._frozen_fwd = None         # batch size of the frozen forward since the last set_batch, if any
@@ -900,6 +934,7 @@ class Engine(Replica):
         b = Build(B, self.lanes, nl, self.ws_lane, self.ws_bytes, node_lanes(g, self.plan, nl), self._flush_points)
         if frozen:
             b.stats_shift = self.frozen.data_ptr() - self.stats.data_ptr()
+            b.guard = self._frozen_guard()
         self._fwd_prep(b)
         for i, n in enumerate(g.nodes):
             if n.kind != "conv":
@@ -1013,19 +1048,22 @@ class Engine(Replica):
                 _ffi.BnApplySeg(self._A(m.y.buf), m.y.c_off, g.bufs[m.y.buf].c, m.cout, self._beta(m))
                 for m in u.members])
             b.keep.append(segs)
-            b.add(b.fwd, L.jr_bn_relu_apply_multi,
+            fn, lim = ((L.jr_bn_relu_apply_multi, ()) if b.guard is None
+                       else (L.jr_bn_relu_apply_multi_guard, (b.guard,)))
+            b.add(b.fwd, fn,
                   (dt, len(u.members), ctypes.byref(segs), raw, 0, u.cout, M, u.cout, mean + b.stats_shift,
-                   invstd + b.stats_shift, s),
+                   invstd + b.stats_shift) + lim + (s,),
                   "bn_relu", ln, [("r", uid), ("p",)], [("a", m.y.buf, m.y.c_off) for m in u.members],
                   nbytes=2 * M * u.cout * self.esz)
             return
         for m, co in zip(u.members, u.col_off):
             if m.y.buf in self.fused_bufs:
                 continue        # applied inside its max-pool
-            b.add(b.fwd, L.jr_bn_relu_apply,
+            fn, lim = (L.jr_bn_relu_apply, ()) if b.guard is None else (L.jr_bn_relu_apply_guard, (b.guard,))
+            b.add(b.fwd, fn,
                   (dt, raw, co, u.cout, M, m.cout, self.mean[m.idx].data_ptr() + b.stats_shift,
                    self.invstd[m.idx].data_ptr() + b.stats_shift, self._beta(m), self._A(m.y.buf), m.y.c_off,
-                   g.bufs[m.y.buf].c, s),
+                   g.bufs[m.y.buf].c) + lim + (s,),
                   "bn_relu", ln, [("r", uid), ("p",)], [("a", m.y.buf, m.y.c_off)], nbytes=2 * M * m.cout * self.esz)
 
     def _fwd_pool(self, b: Build, i: int, n: PoolNode) -> None:
@@ -1037,10 +1075,12 @@ class Engine(Replica):
             pn = self._pool_producer(n)
             d.x_c_off, d.x_c_stride = 0, pn.cout                       # its raw output
             puid = self.plan.unit_of[pn.idx].first.idx
-            b.add(b.fwd, L.jr_bn_relu_maxpool3x3s2_fwd,
+            fn, lim = ((L.jr_bn_relu_maxpool3x3s2_fwd, ()) if b.guard is None
+                       else (L.jr_bn_relu_maxpool3x3s2_fwd_guard, (b.guard,)))
+            b.add(b.fwd, fn,
                   (ctypes.byref(d), dt, self.raw_unit[puid].data_ptr(), self.mean[pn.idx].data_ptr() + b.stats_shift,
                    self.invstd[pn.idx].data_ptr() + b.stats_shift, self._beta(pn), self._A(n.y.buf),
-                   self.argmax[i].data_ptr(), s),
+                   self.argmax[i].data_ptr()) + lim + (s,),
                   "bn_relu_maxpool_fwd", ln, [("r", puid), ("p",)], out + [("am", i)],
                   nbytes=B * n.c * (n.h * n.w * self.esz + n.ho * n.wo * (self.esz + 1)))
         elif n.kind == "maxpool":
@@ -1269,7 +1309,10 @@ class Engine(Replica):
         frozen statistics) and the data gradient -- jr_conv2d_bwd_image into
         self.dinput for the image layer.  Fused stem pools: the plain max-pool
         backward from the stored argmax, then the frozen BN backward.  No
-        filter gradient, no hook, no optimizer.  Its own key and schedule."""
+        filter gradient, no hook, no optimizer.  Its own key and schedule.
+        x6h (x6h_frozen): the list starts with one jr_absmax_reset of the
+        data-gradient magnitude rows on lane 0, and every frozen BN backward
+        is jr_bn_relu_bwd_frozen_absmax into its launch's row."""
         self._ensure_tiles()
         nl = self.nlanes if nl is None else max(1, min(int(nl), self.nlanes))
         key = (B, nl, "input_grad")
@@ -1281,6 +1324,16 @@ class Engine(Replica):
         b = Build(B, self.lanes, nl, self.ws_lane, self.ws_bytes, node_lanes(g, self.plan, nl))
         b.stats_shift = self.frozen.data_ptr() - self.stats.data_ptr()
         ob, s0 = g.bufs[g.output_buf], b.S[0]
+        if self.x6h:
+            # x6h (x6h_frozen): every frozen BN backward raises its launch's
+            # data-gradient row (the dy_absmax of its dgrad), so the rows [U, 2U)
+            # start from zero on EVERY run -- two input_gradient calls after one
+            # forward give the same bits as one.  (Row 2U - 1 also held the
+            # betas' maxima of the forward's jr_absmax_prep: their guard was
+            # evaluated inside that launch, nothing reads them afterwards.)
+            U = len(self.cunits)
+            b.add(b.bwd, self.lib.jr_absmax_reset, (self.absmax.data_ptr() + 4 * 64 * U, 64 * U, s0),
+                  "absmax_reset", 0, [], [("dmax", u.first.idx) for u in self.cunits], nbytes=4 * 64 * U)
         b.add(b.bwd, self.lib.jr_head_logit_bwd,
               (self._p("dense/kernel"), self.ig_target.data_ptr(), B, ob.c, self.units, self.dfeat.data_ptr(), s0),
               "head_logit_bwd", 0, [("p",), ("target",)], [("dfeat",)])
@@ -1310,12 +1363,16 @@ class Engine(Replica):
                 _ffi.BnSeg(self._D(m.y.buf), m.y.c_off, self.g.bufs[m.y.buf].c, m.cout, self._beta(m), None)
                 for m, _ in grp])
             b.keep.append(segs)
-            b.add(b.bwd, self.lib.jr_bn_relu_bwd_frozen,
+            # x6h: also the raw-output gradient's magnitude, the dy_absmax of the
+            # dgrad below (which reads dkey, written here: ordered behind it)
+            fn, amax = ((self.lib.jr_bn_relu_bwd_frozen_absmax, (self._dmax(u),)) if self.x6h
+                        else (self.lib.jr_bn_relu_bwd_frozen, ()))
+            b.add(b.bwd, fn,
                   (self.dt, len(grp), ctypes.byref(segs), self.raw_unit[uid].data_ptr(), co0, u.cout, M, cg,
                    self.mean_unit[uid].data_ptr() + 4 * co0 + b.stats_shift,
-                   self.invstd_unit[uid].data_ptr() + 4 * co0 + b.stats_shift, draw, b.S[ln]),
-                  "bn_relu_bwd_frozen", ln, [("d", m.y.buf, m.y.c_off) for m, _ in grp] + [("r", uid), ("p",)], [dkey],
-                  nbytes=3 * M * cg * self.esz)
+                   self.invstd_unit[uid].data_ptr() + 4 * co0 + b.stats_shift, draw) + amax + (b.S[ln],),
+                  "bn_relu_bwd_frozen", ln, [("d", m.y.buf, m.y.c_off) for m, _ in grp] + [("r", uid), ("p",)],
+                  [dkey] + ([("dmax", uid)] if self.x6h else []), nbytes=3 * M * cg * self.esz)
         if u.x != self.g.input_buf:
             self._bwd_dgrad(b, ln, u, d, draw, dkey, acc)
             return
@@ -1330,7 +1387,9 @@ class Engine(Replica):
         self.dinput (fp32 [B, h, w, 4], channel 3 zero).  target: None (logit 0)
         or one class index per image.  Needs Engine(..., input_grad=True) and a
         forward(B, bn="frozen") of the current batch: under frozen BN the
-        gradient of an image's logit is a property of that image alone."""
+        gradient of an image's logit is a property of that image alone (bit
+        for bit on x8 / f32 / bf16; on x6h, whose dy scales are measured per
+        batch, to within the x6h error class)."""
         if not self.input_grad:
             raise ValueError("input_gradient needs an engine built with input_grad=True")
         self._check_frozen("frozen")

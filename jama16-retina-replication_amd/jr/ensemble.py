@@ -19,6 +19,14 @@ resident as ONE replica with a member dimension: every tensor is member-major
 Every member sees exactly its own batch-statistics BN (App. C Q1) and the
 per-member tile plan, so its predictions are BITWISE those of a jr.Engine of
 that member (tests/test_gpu_ensemble.py).  Inference only (train=False).
+
+forward(bn="frozen") normalises with fixed statistics (freeze_bn).  On
+conv_math="x6h" that needs x6h_frozen=True: the frozen list then stores every
+activation through the guarded entry points (jr_bn_relu_apply_grouped_guard,
+jr_bn_relu_maxpool3x3s2_fwd_grouped_guard; limit 2 * act_bound, one error word
+for all members), the conv scales stay constants -- predictions bitwise
+independent of the other images of the batch -- and an activation above the
+bound raises JRError (JR_ERR_DEVICE) at the next synchronize() / predictions().
 """
 from __future__ import annotations
 
@@ -39,13 +47,16 @@ class EnsembleEngine(Replica):
 
     def __init__(self, params: List[np.ndarray], batch: int, height: int = 299, width: int = 299, units: int = 1,
                  device: int | torch.device = 0, dtype: str = "f32", conv_math: Optional[str] = None,
-                 tiles: str = "pinned", head: str = "sigmoid", fuse_pool: Optional[bool] = None, lanes: int = 2):
+                 tiles: str = "pinned", head: str = "sigmoid", fuse_pool: Optional[bool] = None, lanes: int = 2,
+                 x6h_frozen: bool = False):
+        # x6h_frozen: forward(bn="frozen") on conv_math="x6h" through the guarded
+        # BN applies and fused stem pools (Replica._frozen_guard), as jr.Engine
         if not params:
             raise ValueError("at least one member")
         self.members = len(params)
         # (fuse_pool: the stem's BN + ReLU inside its max-pools, every member in one launch)
         super().__init__(build_inception_v3(height, width, units), device, dtype, conv_math, ("x8", "x6h", "f32"),
-                         head, True, fuse_pool, lanes)
+                         head, True, fuse_pool, lanes, x6h_frozen=x6h_frozen)
         self.batch = int(batch)
         self._alloc()
         self.load_params(params)
@@ -147,6 +158,7 @@ class EnsembleEngine(Replica):
         b = Build(B, self.lanes, self.nlanes, self.ws_lane, self.ws_bytes, node_lanes(self.g, self.plan, self.nlanes))
         if frozen:
             b.stats_shift = self.frozen.data_ptr() - self.stats.data_ptr()
+            b.guard = self._frozen_guard()
         for i, n in enumerate(self.g.nodes):
             if n.kind != "conv":
                 self._fwd_pool(b, i, n)
@@ -181,10 +193,12 @@ class EnsembleEngine(Replica):
         for mem, co in zip(u.members, u.col_off):
             if mem.y.buf in self.fused_bufs:
                 continue        # applied inside its max-pool
-            b.add(b.fwd, L.jr_bn_relu_apply_grouped,
+            fn, lim = ((L.jr_bn_relu_apply_grouped, ()) if b.guard is None
+                       else (L.jr_bn_relu_apply_grouped_guard, (b.guard,)))
+            b.add(b.fwd, fn,
                   (self.dt, M, raw, co, u.cout, self.raw_ms[uid], rows, mem.cout, mean + 4 * co + b.stats_shift,
                    inv + 4 * co + b.stats_shift, self.stats_ms, self._beta(mem), self.nparam, self._A(mem.y.buf),
-                   mem.y.c_off, g.bufs[mem.y.buf].c, self.act_ms[mem.y.buf], s),
+                   mem.y.c_off, g.bufs[mem.y.buf].c, self.act_ms[mem.y.buf]) + lim + (s,),
                   "bn_relu", ln, [("r", uid)], [("a", mem.y.buf, mem.y.c_off)])
 
     def _fwd_pool(self, b: Build, i: int, n) -> None:
@@ -201,9 +215,11 @@ class EnsembleEngine(Replica):
                 pn = self._pool_producer(n)
                 puid = self.plan.unit_of[pn.idx].first.idx
                 mean = self.stats.data_ptr() + 4 * (self.stat_off[puid] + m * self.stats_ms) + b.stats_shift
-                b.add(b.fwd, L.jr_bn_relu_maxpool3x3s2_fwd_grouped,
+                fn, lim = ((L.jr_bn_relu_maxpool3x3s2_fwd_grouped, ()) if b.guard is None
+                           else (L.jr_bn_relu_maxpool3x3s2_fwd_grouped_guard, (b.guard,)))
+                b.add(b.fwd, fn,
                       (ctypes.byref(d), self.dt, B, self.raw_unit[puid].data_ptr() + self.esz * m * self.raw_ms[puid],
-                       mean, mean + 4 * pn.cout, self.stats_ms, self._beta(pn, m), self.nparam, yo, None, s),
+                       mean, mean + 4 * pn.cout, self.stats_ms, self._beta(pn, m), self.nparam, yo, None) + lim + (s,),
                       "bn_relu_maxpool_fwd", ln, [("r", puid)], out)
             elif n.kind == "maxpool":
                 b.add(b.fwd, L.jr_maxpool3x3s2_fwd, (ctypes.byref(d), self.dt, xi, yo, None, s), "maxpool_fwd", ln,

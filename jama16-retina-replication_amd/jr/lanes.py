@@ -162,6 +162,9 @@ class Build:
         # frozen BN (forward(bn="frozen")): byte distance from the batch statistics
         # to the frozen ones, added to what every BN apply and fused pool reads
         self.stats_shift = 0
+        # ... and, for JR_F32_X6H under frozen statistics, the limit of the guarded
+        # BN applies and fused pools (None: the unguarded entry points)
+        self.guard = None
 
     def add(self, lst, fn, args, name, lane, reads=(), writes=(), nbytes=0) -> None:
         c = Call(fn, args, name, lane, tuple(reads), tuple(writes), nbytes=int(nbytes))
