@@ -517,6 +517,68 @@ int jr_sgd_update(float* w, const float* grad, int64_t n, float lr, float grad_s
 int jr_adam_update(float* w, const float* grad, float* m, float* v, int64_t n, float lr_t,
                    float beta1, float beta2, float eps, float grad_scale, void* stream);
 
+/* ---- the optimizer recipe with its step scalars in DEVICE memory --------
+ * Weight decay, clipping of the global gradient norm, a guard against a
+ * non-finite gradient and a learning rate that may change between replays of
+ * a captured step (not in the reference: the engine uses these calls only
+ * when asked to).  Per step, on one stream:
+ *   jr_opt_set_hyper   (when a scalar changes; outside any captured graph)
+ *   jr_grad_sqnorm  ->  jr_opt_prepare  ->  jr_<optimizer>_update_ex
+ * Every fp32 operation is one correctly rounded op in the order written
+ * here (no FMA contraction). */
+typedef struct jr_opt_hyper { float lr, weight_decay, clip_norm, grad_scale; } jr_opt_hyper; /* written by jr_opt_set_hyper */
+typedef struct jr_opt_step { float scale, grad_norm; uint32_t skipped, skipped_total; } jr_opt_step; /* written by jr_opt_prepare */
+typedef struct jr_opt_range { int64_t begin, end; } jr_opt_range; /* decayed elements [begin, end) */
+/* One thread stores the four scalars into *hyper (device memory, 4-byte
+ * aligned).  They travel by value in the launch: no staging buffer the host
+ * could reuse while a copy is in flight.  clip_norm <= 0: no clipping.  For
+ * jr_adam_update_ex, lr carries the step's alpha (lr_t of jr_adam_update). */
+int jr_opt_set_hyper(jr_opt_hyper* hyper, float lr, float weight_decay, float clip_norm, float grad_scale,
+                     void* stream);
+/* S = sum_i (double)grad[i]^2 over the raw gradient, left as per-block partials
+ * (doubles; jr_grad_sqnorm_workspace_size(n) bytes, 8-byte aligned; grad
+ * 16-byte aligned).  A fixed grid of min(1024, ceil(floor(n/4)/256)) >= 1
+ * blocks of 256 threads; a thread adds its 16-byte quads in grid-stride order,
+ * a block sums in a fixed tree; no atomics, no hand-off between blocks: the
+ * same gradient gives bitwise the same partials in every run and on every
+ * data-parallel replica. */
+size_t jr_grad_sqnorm_workspace_size(int64_t n);
+int jr_grad_sqnorm(const float* grad, int64_t n, void* partials, size_t ws_bytes, void* stream);
+/* One block sums the partials of jr_grad_sqnorm(grad, n, ...) in a fixed
+ * tree (fp64) into S and writes *step:
+ *   n32       = (float)sqrt(S)
+ *   grad_norm = n32 * grad_scale
+ *   factor    = (clip_norm > 0 && grad_norm > clip_norm) ? clip_norm / grad_norm : 1
+ *   scale     = grad_scale * factor
+ * grad_norm not finite (inf or NaN, a norm that overflows fp32 included):
+ * scale = 0, skipped = 1, skipped_total += 1; else skipped = 0 (skipped_total
+ * is never reset by the library: zero *step once).  S == 0 gives factor 1. */
+int jr_opt_prepare(const void* partials, int64_t n, const jr_opt_hyper* hyper, jr_opt_step* step, void* stream);
+/* jr_nesterov_update / _momentum_ / _sgd_ / _adam_ with lr = hyper->lr and,
+ * per element,  g = grad * step->scale;  inside a decay range and with
+ * hyper->weight_decay != 0:  g = g + weight_decay * w  (a multiply, then an
+ * add), then the by-value call's expression.  This is L2 decay in the loss
+ * form: the decay term goes through the momentum / Adam moments (it is NOT
+ * decoupled decay), and the clip factor in step->scale covers the data
+ * gradient only, not the decay term.  step->skipped != 0: nothing at all is
+ * written, neither weights nor optimizer state.  The skip is a device
+ * decision the host does not wait for: a caller that counts steps on the
+ * host (Adam's t in its alpha, moving averages) counts a skipped step too.
+ * ranges: a DEVICE array of nranges element ranges, sorted, disjoint, at any
+ * element offsets (NULL with nranges == 0: nothing decays).  w, grad and the
+ * state buffers 16-byte aligned. */
+int jr_nesterov_update_ex(float* w, const float* grad, float* accum, int64_t n, float momentum,
+                          const jr_opt_range* ranges, int32_t nranges, const jr_opt_hyper* hyper,
+                          const jr_opt_step* step, void* stream);
+int jr_momentum_update_ex(float* w, const float* grad, float* accum, int64_t n, float momentum,
+                          const jr_opt_range* ranges, int32_t nranges, const jr_opt_hyper* hyper,
+                          const jr_opt_step* step, void* stream);
+int jr_sgd_update_ex(float* w, const float* grad, int64_t n, const jr_opt_range* ranges, int32_t nranges,
+                     const jr_opt_hyper* hyper, const jr_opt_step* step, void* stream);
+int jr_adam_update_ex(float* w, const float* grad, float* m, float* v, int64_t n, float beta1, float beta2, float eps,
+                      const jr_opt_range* ranges, int32_t nranges, const jr_opt_hyper* hyper, const jr_opt_step* step,
+                      void* stream);
+
 /* ---- bf16 filter copies (the bf16 conv path's weight operands) -------
  * From the fp32 master kernel [kh][kw][c_in][c_out] write
  *   w_hwio: bf16 [kh][kw][c_in][c_out]        (jr_conv2d_bwd_data, JR_BF16)

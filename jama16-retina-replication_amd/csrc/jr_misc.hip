@@ -13,18 +13,13 @@
 //   ApplyMomentum:               accum = accum*m + g; var -= accum*lr
 //   ApplyGradientDescent:        var -= g*lr
 #include "jr_common.h"
+#include "jr_opt_expr.h"   // nest1, sqrt_cr (shared with jr_opt.hip)
 
 namespace jr {
 
 static int grid_for(int64_t items) {
   const int64_t b = ceil_div(items, 256);
   return (int)std::min<int64_t>(std::max<int64_t>(b, 1), 256 * 32);
-}
-
-__device__ __forceinline__ float nest1(float& w, float g, float& a, float lr, float m) {
-  a = __fadd_rn(__fmul_rn(a, m), g);
-  w = __fsub_rn(w, __fadd_rn(__fmul_rn(g, lr), __fmul_rn(__fmul_rn(a, m), lr)));
-  return w;
 }
 
 __global__ void __launch_bounds__(256) k_nesterov(float* __restrict__ w, const float* __restrict__ grad,
@@ -65,20 +60,6 @@ __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ w, const float*
                                              float lr, float gs) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     w[i] = __fsub_rn(w[i], __fmul_rn(__fmul_rn(grad[i], gs), lr));
-}
-
-// Correctly rounded sqrt (IEEE, as Eigen's sqrt on the CPU): v_sqrt_f32 is
-// within 1 ulp, so check its neighbours with exact fma residuals and step
-// once (denormal inputs are scaled by 2^32 first).
-__device__ __forceinline__ float sqrt_cr(float x) {
-  const bool tiny = x < 0x1.0p-96f;
-  const float xs = tiny ? x * 0x1.0p+32f : x;
-  float s = __builtin_amdgcn_sqrtf(xs);
-  const float dn = __uint_as_float(__float_as_uint(s) - 1), up = __uint_as_float(__float_as_uint(s) + 1);
-  if (__builtin_fmaf(-dn, s, xs) <= 0.f) s = dn;
-  else if (__builtin_fmaf(-up, s, xs) > 0.f) s = up;
-  s = tiny ? s * 0x1.0p-16f : s;
-  return (xs == 0.f || !(xs < __builtin_inff())) ? __builtin_sqrtf(x) : s;
 }
 
 // TF ApplyAdam (training_ops.cc ApplyAdamNonCuda, Eigen, no contraction):

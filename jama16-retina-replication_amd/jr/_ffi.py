@@ -111,6 +111,22 @@ class WarpParam(Structure):
     _fields_ = [("m", c_float * 6), ("reserved", ctypes.c_uint32 * 2)]
 
 
+class OptHyper(Structure):
+    """include/jr.h jr_opt_hyper: the optimizer scalars in device memory (jr_opt_set_hyper writes them)."""
+    _fields_ = [("lr", c_float), ("weight_decay", c_float), ("clip_norm", c_float), ("grad_scale", c_float)]
+
+
+class OptStep(Structure):
+    """include/jr.h jr_opt_step: what jr_opt_prepare leaves for the update of this step."""
+    _fields_ = [("scale", c_float), ("grad_norm", c_float), ("skipped", ctypes.c_uint32),
+                ("skipped_total", ctypes.c_uint32)]
+
+
+class OptRange(Structure):
+    """include/jr.h jr_opt_range: decayed elements [begin, end) of the flat parameter buffer."""
+    _fields_ = [("begin", c_int64), ("end", c_int64)]
+
+
 class PoolDesc(Structure):
     _fields_ = [(n, c_int32) for n in (
         "n", "h", "w", "c", "ho", "wo", "x_c_off", "x_c_stride", "y_c_off", "y_c_stride")]
@@ -247,6 +263,17 @@ _SIGS = {
     "jr_sgd_update": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
     "jr_adam_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
                                c_float, c_float, c_float, c_void_p]),
+    "jr_opt_set_hyper": (c_int, [c_void_p, c_float, c_float, c_float, c_float, c_void_p]),
+    "jr_grad_sqnorm_workspace_size": (c_size_t, [c_int64]),
+    "jr_grad_sqnorm": (c_int, [c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "jr_opt_prepare": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "jr_nesterov_update_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int32, c_void_p,
+                                      c_void_p, c_void_p]),
+    "jr_momentum_update_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int32, c_void_p,
+                                      c_void_p, c_void_p]),
+    "jr_sgd_update_ex": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "jr_adam_update_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
+                                  c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "jr_cast_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "jr_cast_bf16_to_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "jr_u8_to_f32_scaled": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),
@@ -358,6 +385,7 @@ def call(name: str, *args) -> int:
     rc = getattr(lib, name)(*args)
     if isinstance(rc, int) and name not in ("jr_conv2d_workspace_size", "jr_bn_workspace_size",
                                             "jr_bn_relu_bwd_maxpool_workspace_size", "jr_augment_workspace_size",
+                                            "jr_grad_sqnorm_workspace_size",
                                             "jr_conv2d_get_config", "jr_conv2d_num_configs", "jr_conv2d_config_generation",
                                             "jr_conv_weights_bf16_tiles"):
         check(name, rc)

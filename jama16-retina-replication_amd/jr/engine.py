@@ -52,7 +52,7 @@ from . import _ffi
 from .inception import BN_EPS, Graph, PoolNode, build_inception_v3
 from .init import init_params
 from .lanes import Build, Call, Lanes, node_lanes, schedule
-from .plan import ConvUnit, bn_batch_groups, bn_moving_segments, build_plan
+from .plan import ConvUnit, bn_batch_groups, bn_moving_segments, build_plan, decay_ranges
 
 DTYPES = {"f32": _ffi.JR_F32, "bf16": _ffi.JR_BF16}
 
@@ -477,7 +477,20 @@ class Engine(Replica):
                  autotune: bool = False, tiles: str = "pinned", fuse_siblings: bool = True, lanes: int = 2,
                  conv_math: Optional[str] = None, defer_wgrad: Optional[bool] = None, fuse_pool: Optional[bool] = None,
                  fold_stats: Optional[bool] = None, bn_moving: Optional[float] = None, input_grad: bool = False,
-                 x6h_frozen: bool = False):
+                 x6h_frozen: bool = False, weight_decay: float = 0.0, clip_norm: Optional[float] = None,
+                 device_lr: bool = False):
+        # the optimizer recipe with its scalars in device memory (jr.h: jr_opt_*;
+        # off by default, on when any of the three is set): L2 weight decay on
+        # the filters and the dense kernel, clipping of the global gradient
+        # norm (None: none), and a learning rate set_lr may change between
+        # steps and between replays of a captured step
+        if not (float(weight_decay) >= 0.0 and np.isfinite(weight_decay)):
+            raise ValueError("weight_decay: a finite value >= 0")
+        if clip_norm is not None and not (float(clip_norm) > 0.0 and np.isfinite(clip_norm)):
+            raise ValueError("clip_norm: None or a finite norm > 0")
+        self.weight_decay = float(weight_decay)
+        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        self.opt_ex = bool(train) and (self.weight_decay != 0.0 or self.clip_norm is not None or bool(device_lr))
         # bn_moving: None, or the momentum of the moving averages of the BN
         # statistics every training step then updates (Keras: 0.99)
         if bn_moving is not None and not 0.0 <= float(bn_moving) <= 1.0:
@@ -638,6 +651,15 @@ class Engine(Replica):
             self.grads = self._t(self.nparam)
             self.accum = self._t(self.nparam)
             self.adam_v = self._t(self.nparam) if self.optimizer == "adam" else None
+            if self.opt_ex:
+                # the norm's per-block partials, jr_opt_hyper, jr_opt_step (zeroed: skipped_total
+                # counts from here) and the decay ranges of the internal layout
+                self.opt_partials = self._t(self.lib.jr_grad_sqnorm_workspace_size(self.nparam) // 8, torch.float64)
+                self.opt_hyper, self.opt_step_dev = self._t(4), self._t(4)
+                self.opt_ranges = decay_ranges(self.plan)
+                self._opt_ranges_dev = self._table(_ffi.OptRange, [_ffi.OptRange(b, e) for b, e in self.opt_ranges])
+                self._hyper_dev = None      # the scalars last enqueued for opt_hyper
+                self._push_hyper(self.lr, 1.0)
         if self._data_grads:
             self.dacts = [self._t(B * b.h * b.w * b.c, at) if b.id != g.input_buf else None
                           for b in g.bufs]
@@ -1422,7 +1444,27 @@ class Engine(Replica):
         L, s0, n = self.lib, b.S[0], self.nparam
         P, G, acc = self.params.data_ptr(), self.grads.data_ptr(), self.accum.data_ptr()
         greads = [("g", u.first.idx) for u in self.cunits] + [("g", "dense")]
-        if self.optimizer in ("nesterov", "momentum"):
+        if self.opt_ex:
+            # norm of the (reduced) raw gradient -> scale / skip of this step -> the
+            # update reading lr, weight decay, scale and skip from device memory
+            part, hy, st = self.opt_partials.data_ptr(), self.opt_hyper.data_ptr(), self.opt_step_dev.data_ptr()
+            R, nr = self._opt_ranges_dev.data_ptr(), len(self.opt_ranges)
+            b.add(b.opt, L.jr_grad_sqnorm, (G, n, part, ctypes.c_size_t(8 * self.opt_partials.numel()), s0),
+                  "grad_sqnorm", 0, greads, [("gnorm",)], nbytes=4 * n)
+            b.add(b.opt, L.jr_opt_prepare, (part, n, hy, st, s0), "opt_prepare", 0, [("gnorm",)], [("gnorm",)])
+            rd = greads + [("gnorm",)]
+            if self.optimizer in ("nesterov", "momentum"):
+                nesterov = self.optimizer == "nesterov"
+                b.add(b.opt, L.jr_nesterov_update_ex if nesterov else L.jr_momentum_update_ex,
+                      (P, G, acc, n, self.momentum, R, nr, hy, st, s0), self.optimizer + "_update_ex", 0, rd,
+                      [("p",), ("acc",)], nbytes=20 * n if nesterov else 0)
+            elif self.optimizer == "sgd":
+                b.add(b.opt, L.jr_sgd_update_ex, (P, G, n, R, nr, hy, st, s0), "sgd_update_ex", 0, rd, [("p",)])
+            else:   # adam: the step's alpha goes through jr_opt_set_hyper (apply_update)
+                b.add(b.opt, L.jr_adam_update_ex, (P, G, acc, self.adam_v.data_ptr(), n, self.adam_b1, self.adam_b2,
+                                                   self.adam_eps, R, nr, hy, st, s0), "adam_update_ex", 0, rd,
+                      [("p",), ("acc",)])
+        elif self.optimizer in ("nesterov", "momentum"):
             nesterov = self.optimizer == "nesterov"
             b.add(b.opt, L.jr_nesterov_update if nesterov else L.jr_momentum_update,
                   (P, G, acc, n, self.lr, self.momentum, 1.0, s0), self.optimizer, 0, greads, [("p",), ("acc",)],
@@ -1473,24 +1515,62 @@ class Engine(Replica):
         self.lanes.run(self._build_calls(B or self.batch)[1], hook)
         self.lanes.join()
 
+    def _adam_alpha(self) -> float:
+        """TF ApplyAdam (training_ops.cc): alpha = lr * sqrt(1 - beta2_power)
+        / (1 - beta1_power) of the next step, evaluated in the variable dtype
+        (fp32, left to right; np.sqrt of a float32 is correctly rounded like
+        Eigen's), from fp32 beta powers, which it then advances."""
+        f = np.float32
+        self.adam_t += 1
+        alpha = f(f(self.lr) * np.sqrt(f(1) - self.adam_b2p)) / (f(1) - self.adam_b1p)
+        self.adam_b1p = f(self.adam_b1p * f(self.adam_b1))
+        self.adam_b2p = f(self.adam_b2p * f(self.adam_b2))
+        return float(f(alpha))
+
+    def _push_hyper(self, lr: float, grad_scale: float) -> None:
+        """Enqueue jr_opt_set_hyper on the engine's stream when a scalar differs
+        from what the device holds (by value: nothing for the host to keep alive)."""
+        want = (float(lr), self.weight_decay, self.clip_norm or 0.0, float(grad_scale))
+        if want != self._hyper_dev:
+            _ffi.check("jr_opt_set_hyper", self.lib.jr_opt_set_hyper(self.opt_hyper.data_ptr(), *want, self._s))
+            self._hyper_dev = want
+
+    def set_lr(self, lr: float) -> None:
+        """The learning rate of the steps enqueued from here on, replays of a
+        captured step included (device path only: the default path binds the
+        rate into its call lists and captured graphs)."""
+        if not self.opt_ex:
+            raise ValueError("set_lr needs the device optimizer path: Engine(device_lr=True) "
+                             "(or weight_decay / clip_norm)")
+        self.lr = float(lr)
+        # (grad_scale stays what the last apply_update set; the next apply_update / replay sets its own)
+        if self.optimizer != "adam":    # Adam: apply_update writes the step's alpha
+            self._push_hyper(self.lr, self._hyper_dev[3])
+
+    def opt_step(self) -> Tuple[float, float, int, int]:
+        """(grad_norm, scale, skipped, skipped_total) of the last step (jr.h
+        jr_opt_step), after a synchronise."""
+        if not self.opt_ex:
+            raise ValueError("opt_step needs the device optimizer path (weight_decay, clip_norm or device_lr)")
+        self.synchronize()
+        raw = self.opt_step_dev.cpu()
+        scale, norm = (float(v) for v in raw[:2])
+        skipped, total = (int(v) for v in raw[2:].view(torch.int32))
+        return norm, scale, skipped, total
+
     def apply_update(self, B: Optional[int] = None, grad_scale: float = 1.0) -> None:
         opt = self._build_calls(B or self.batch)[2]
-        if grad_scale != 1.0 or self.optimizer == "adam":
+        if self.opt_ex:
+            # (a skipped step still counts as a step on the host: Adam's t and beta powers,
+            # and the BN moving averages and self.updates below, advance; only the device
+            # write of weights and optimizer state is withheld -- jr.h)
+            self._push_hyper(self._adam_alpha() if self.optimizer == "adam" else self.lr, grad_scale)
+        elif grad_scale != 1.0 or self.optimizer == "adam":
             c = opt[0]
             args = list(c.args)
             args[-2] = grad_scale
             if self.optimizer == "adam":
-                # TF ApplyAdam (training_ops.cc): alpha = lr * sqrt(1 - beta2_power)
-                # / (1 - beta1_power), evaluated in the variable dtype (fp32,
-                # left to right; np.sqrt of a float32 is correctly rounded like
-                # Eigen's), from fp32 beta powers (so Adam steps run eagerly:
-                # the scalar changes every step)
-                f = np.float32
-                self.adam_t += 1
-                alpha = f(f(self.lr) * np.sqrt(f(1) - self.adam_b2p)) / (f(1) - self.adam_b1p)
-                args[5] = float(f(alpha))
-                self.adam_b1p = f(self.adam_b1p * f(self.adam_b1))
-                self.adam_b2p = f(self.adam_b2p * f(self.adam_b2))
+                args[5] = self._adam_alpha()     # (so Adam steps run eagerly: the scalar changes every step)
             opt = [dataclasses.replace(c, args=tuple(args))] + list(opt[1:])
         self.lanes.run(opt)
         if self.bn_momentum is not None:
@@ -1525,6 +1605,8 @@ class Engine(Replica):
         if self.nlanes > 2:
             raise ValueError("HIP graph capture supports at most two lanes (more lanes run eagerly)")
         fwd, bwd, opt, _, _ = self._build_calls(B)
+        if self.opt_ex:     # the graph reads the scalars: written ahead of it, never inside it
+            self._push_hyper(self.lr, 1.0)
         torch.cuda.synchronize(self.device)
         _ffi.check("jr_graph_begin", self.lib.jr_graph_begin(self._s))
         ln = self.lanes
@@ -1544,6 +1626,8 @@ class Engine(Replica):
 
     def replay(self, B: Optional[int] = None) -> None:
         B = B or self.batch
+        if self.opt_ex:     # a captured step is single-GPU: grad_scale 1, whatever an eager apply_update left
+            self._push_hyper(self.lr, 1.0)
         _ffi.check("jr_graph_launch", self.lib.jr_graph_launch(ctypes.c_void_p(self._graphs[B]), self._s))
         if self.bn_momentum is not None:
             self.updates += 1

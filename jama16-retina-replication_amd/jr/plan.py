@@ -175,6 +175,23 @@ def build_plan(g: Graph, fuse_siblings: bool = True) -> Plan:
     return Plan(units, unit_of, layout, off, poff, kview)
 
 
+def decay_ranges(plan: Plan) -> List[Tuple[int, int]]:
+    """Sorted, disjoint element ranges [begin, end) of the internal parameter
+    buffer that L2 weight decay covers: every conv filter block (a fused
+    group's shared block included) and the dense kernel.  BN betas, the dense
+    bias and the alignment padding between tensors are never decayed; blocks
+    that touch are merged into one range."""
+    out: List[Tuple[int, int]] = []
+    for name, _, off, size in sorted(plan.layout, key=lambda e: e[2]):
+        if not name.endswith("/kernel") or size == 0:
+            continue
+        if out and out[-1][1] == off:
+            out[-1] = (out[-1][0], off + size)
+        else:
+            out.append((off, off + size))
+    return out
+
+
 def bn_moving_segments(units: List[ConvUnit], batch: int) -> List[Tuple[int, int, int, int]]:
     """(stats offset, moving offset, rows, c) per conv launch: the segment
     table of jr_bn_moving_update / jr_bn_moving_freeze at this batch.  The

@@ -131,7 +131,81 @@ def build_parser():
                         "bare) and save them beside every checkpoint (<path>.bnstats) for evaluate.py --bn moving; "
                         "training and validation still normalise with batch statistics.  Under torchrun every rank "
                         "keeps the averages of its own batches (they match its own BN); rank 0's are saved")
+    # the optimizer recipe (not in the reference: off by default; jr.schedule, jr.h jr_opt_*)
+    p.add_argument("--learning_rate", type=_positive_float, default=None, metavar="LR",
+                   help="base learning rate (default {})".format(LEARNING_RATE))
+    p.add_argument("--lr_decay", type=_decay_arg, default=None, metavar="RATE,EPOCHS",
+                   help="exponential staircase: multiply the learning rate by RATE every EPOCHS epochs")
+    p.add_argument("--lr_warmup", type=_count_arg, default=None, metavar="STEPS",
+                   help="linear warmup of the learning rate from LR/STEPS over the first STEPS steps")
+    p.add_argument("--weight_decay", type=_nonnegative_float, default=None, metavar="WD",
+                   help="L2 weight decay on the conv filters and the dense kernel (never BN betas or the bias)")
+    p.add_argument("--clip_norm", type=_positive_float, default=None, metavar="C",
+                   help="clip the global gradient norm (after the all-reduce) to C; a step whose norm is not "
+                        "finite is skipped either way once any of --lr_decay, --lr_warmup, --weight_decay, "
+                        "--clip_norm is given")
     return p
+
+
+def _float_arg(text, ok, what):
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
+    if not (np.isfinite(v) and ok(v)):
+        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
+    return v
+
+
+def _positive_float(text):
+    return _float_arg(text, lambda v: v > 0, "a finite value > 0")
+
+
+def _nonnegative_float(text):
+    return _float_arg(text, lambda v: v >= 0, "a finite value >= 0")
+
+
+def _count_arg(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected a count >= 0, got {text!r}")
+    if v < 0:
+        raise argparse.ArgumentTypeError(f"expected a count >= 0, got {text!r}")
+    return v
+
+
+def _decay_arg(text):
+    """'RATE,EPOCHS' -> (rate, epochs): a rate > 0 and a whole number of epochs >= 1."""
+    try:
+        rate, epochs = text.split(",")
+        rate, epochs = _positive_float(rate), int(epochs)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected RATE,EPOCHS, got {text!r}")
+    if epochs < 1:
+        raise argparse.ArgumentTypeError(f"expected RATE,EPOCHS with EPOCHS >= 1, got {text!r}")
+    return rate, epochs
+
+
+RECIPE_FLAGS = ("learning_rate", "lr_decay", "lr_warmup", "weight_decay", "clip_norm")
+
+
+def opt_recipe(args):
+    """The optimizer recipe of the flags as saved in the checkpoint .meta
+    (None: none of them is given, the reference's settings)."""
+    if all(getattr(args, f) is None for f in RECIPE_FLAGS):
+        return None
+    return {"learning_rate": LEARNING_RATE if args.learning_rate is None else args.learning_rate,
+            "lr_decay": None if args.lr_decay is None else list(args.lr_decay),
+            "lr_warmup": args.lr_warmup or 0, "weight_decay": args.weight_decay or 0.0, "clip_norm": args.clip_norm}
+
+
+def opt_engine_kwargs(args):
+    """Engine keywords of the recipe: the device optimizer path for every flag
+    but a bare --learning_rate (none at all without a flag)."""
+    if all(getattr(args, f) is None for f in RECIPE_FLAGS[1:]):
+        return {}
+    return {"weight_decay": args.weight_decay or 0.0, "clip_norm": args.clip_norm, "device_lr": True}
 
 
 def _range_arg(text):
@@ -258,10 +332,11 @@ Use SGD: {bool(args.vanilla_sgd)}
 
     engine = Engine(max(TRAIN_BATCH_SIZE, VAL_BATCH_SIZE), args.image_size, args.image_size,
                     device=local, optimizer="sgd" if args.vanilla_sgd else ("nesterov" if USE_NESTEROV else "momentum"),
-                    lr=LEARNING_RATE, momentum=MOMENTUM, seed=args.seed, dtype=args.dtype,
+                    lr=LEARNING_RATE if args.learning_rate is None else args.learning_rate, momentum=MOMENTUM,
+                    seed=args.seed, dtype=args.dtype,
                     conv_math=args.conv_math if args.dtype == "f32" else "bf16",
                     tiles="pinned" if args.tiles == "pinned" else "heuristic",
-                    **({} if args.bn_moving is None else {"bn_moving": args.bn_moving}))
+                    **({} if args.bn_moving is None else {"bn_moving": args.bn_moving}), **opt_engine_kwargs(args))
     table = None
     if args.tile_table:
         table = load_tile_table(args.tile_table)
@@ -279,13 +354,18 @@ Use SGD: {bool(args.vanilla_sgd)}
     # one parameter table per training batch, each rank from its own stream
     aug_spec = augment_spec(args)
     aug_rng = np.random.Generator(np.random.PCG64([args.augment_seed, rank])) if aug_spec else None
-    aug_meta = {"augment": {"spec": aug_spec.to_meta(), "seed": args.augment_seed}} if aug_spec else {}
+    # what the run adds to the checkpoint .meta: the augmentation and the optimizer recipe in use
+    run_meta = {"augment": {"spec": aug_spec.to_meta(), "seed": args.augment_seed}} if aug_spec else {}
     # the geometry draws from a generator of its own: the colour draws of a seed
     # are the same with and without it
     geo_spec = warp_spec(args)
     geo_rng = np.random.Generator(np.random.PCG64([args.augment_seed, rank, 1])) if geo_spec else None
     if geo_spec:
-        aug_meta["augment_warp"] = {"spec": geo_spec.to_meta(), "seed": args.augment_seed}
+        run_meta["augment_warp"] = {"spec": geo_spec.to_meta(), "seed": args.augment_seed}
+    recipe = opt_recipe(args)
+    if recipe:
+        run_meta["optimizer"] = recipe
+    device_opt = bool(opt_engine_kwargs(args))
     if dist:
         from jr.dist import BucketAllReduce
         sess.allreduce = BucketAllReduce(engine, world)
@@ -329,9 +409,15 @@ Use SGD: {bool(args.vanilla_sgd)}
     steps_per_epoch = None
     if dist:   # every rank runs the same number of steps (matching collectives)
         steps_per_epoch = -(-train_dataset.num_records() // TRAIN_BATCH_SIZE) // world
+    # the schedule counts optimizer steps; an epoch of --lr_decay is this many of them
+    # (every rank computes the same value from the same integers: jr.schedule)
+    sched_epoch = -(-train_dataset.num_records() // TRAIN_BATCH_SIZE) // world if device_opt else None
+    if device_opt and args.max_steps_per_epoch is not None:
+        sched_epoch = min(sched_epoch, args.max_steps_per_epoch)
     for epoch in range(args.num_epochs):
         sess.reset("brier")
         batch_num = 0
+        step_lr, norms, clipped, skipped = None, [], 0, 0
         it = iter(train_dataset)
         try:
             for images, labels in it:
@@ -339,6 +425,12 @@ Use SGD: {bool(args.vanilla_sgd)}
                     break
                 if args.max_steps_per_epoch is not None and batch_num >= args.max_steps_per_epoch:
                     break
+                if device_opt:
+                    from jr.schedule import learning_rate
+                    decay = recipe["lr_decay"] and (recipe["lr_decay"][0], recipe["lr_decay"][1] * max(sched_epoch, 1))
+                    step_lr = float(learning_rate(sess.global_step, recipe["learning_rate"], decay or None,
+                                                  recipe["lr_warmup"]))
+                    engine.set_lr(step_lr)
                 if aug_spec is not None:
                     from jr import augment
                     warp = augment.draw_warp(geo_spec, geo_rng, len(images), *size) if geo_spec else None
@@ -346,6 +438,13 @@ Use SGD: {bool(args.vanilla_sgd)}
                                                              augment.draw(aug_spec, aug_rng, len(images)), warp)
                 else:
                     i_global, xent, probs = sess.train_batch(images, labels)
+                if device_opt:      # train_batch synchronised for the loss: 16 more bytes
+                    norm, _, skip, _ = engine.opt_step()
+                    norms.append(norm)
+                    skipped += skip
+                    # (the kernel's own decision: fp32 norm against fp32 clip_norm)
+                    clipped += int(not skip and args.clip_norm is not None
+                                   and np.float32(norm) > np.float32(args.clip_norm))
                 sess.update(labels, probs, "brier")
                 if rank == 0:
                     print(status_line(epoch, args.num_epochs, batch_num, xent, i_global), end="\r")
@@ -357,6 +456,12 @@ Use SGD: {bool(args.vanilla_sgd)}
         train_brier = sess.value("brier")
         if rank == 0:
             print("\nEnd of epoch {0}! (Brier: {1:8.6})".format(epoch, train_brier))
+            if device_opt and norms:
+                finite = [v for v in norms if np.isfinite(v)]      # (a skipped step's norm is inf or NaN)
+                median = float(np.median(np.asarray(finite, np.float64))) if finite else float("nan")
+                print("Learning rate: {0:.6g}, median gradient norm: {1:.6g}, clipped steps: {2}, skipped steps: {3}"
+                      .format(step_lr, median, clipped, skipped))
+                train_writer.add_summary({"grad_norm": median, "learning_rate": step_lr}, epoch)
 
         # every rank gets the same val_auc (summed counts), so the early-stop
         # decisions below agree and the collectives stay matched
@@ -374,7 +479,7 @@ Use SGD: {bool(args.vanilla_sgd)}
                 print(f"New peak auc reached: {val_auc:10.8}")
                 checkpoint.save(args.save_model_path, engine.g, engine.params_numpy(),
                                 {"epoch": epoch, "val_auc": float(val_auc), "tile_table": engine.tile_table(),
-                                 **aug_meta}, **bn_state())
+                                 **run_meta}, **bn_state())
             saved = True
             waited_epochs = 0
 
