@@ -259,7 +259,8 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
   int tile, kt0, kt1;
   if constexpr (SK) {
     if (sk_it >= sk_end) break;
-    tile = (int)(sk_it / g.ktiles);
+    reload_args(g);                      // what the set-up reads, read here and not kept across the K loop
+    tile = fdiv((int)sk_it, g.dv.f[DV_KTILES]);   // (iteration indices stay below 2^31: the launcher checks)
     kt0 = (int)(sk_it - (long long)tile * g.ktiles);
     kt1 = (int)(sk_end - sk_it < (long long)(g.ktiles - kt0) ? kt0 + (sk_end - sk_it) : g.ktiles);
     sk_it += kt1 - kt0;
@@ -269,7 +270,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
     kt0 = blockIdx.z * g.kt_per_split;
     kt1 = min(g.ktiles, kt0 + g.kt_per_split);
   }
-  const int mt = tile / g.ntn, nt = tile - mt * g.ntn;
+  const int mt = fdiv(tile, g.dv.f[DV_NTN]), nt = tile - mt * g.ntn;
   const int m0 = mt * BM, n0 = nt * BN;
   const float* zp = g_zero_page;
   const int cred = OP == OP_FWD ? g.cp : g.cout;       // channel radix of the KC k index
@@ -282,7 +283,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
   // multiplies: the rebuilt address cost two v_mul_lo_u32 per piece and tile);
   // single const definitions (assigned in branches they became allocas read
   // through a per-lane select of their addresses)
-  const int wq = OP == OP_WGRAD ? BK / g.wo : 0, wr = OP == OP_WGRAD ? BK - wq * g.wo : 0;
+  const int wq = OP == OP_WGRAD ? fdiv(BK, g.dv.f[DV_WO]) : 0, wr = OP == OP_WGRAD ? BK - wq * g.wo : 0;
   const int dW0 = OP == OP_WGRAD ? (wq * g.sh * g.w + wr * g.sw) * g.xs : 0;
   const int dW1 = OP == OP_WGRAD ? (g.sh * g.w - g.wo * g.sw) * g.xs : 0;
   const int dW2 = OP == OP_WGRAD ? (g.h * g.w - g.ho * g.sh * g.w) * g.xs : 0;
@@ -309,8 +310,8 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
         int pix = 0;
         if (m < g.M) {
           const int hw = g.ho * g.wo;
-          const int b = m / hw, rem = m - b * hw;
-          const int oh = rem / g.wo, ow = rem - oh * g.wo;
+          const int b = fdiv(m, g.dv.f[DV_HW]), rem = m - b * hw;
+          const int oh = fdiv(rem, g.dv.f[DV_WO]), ow = rem - oh * g.wo;
           a_p0[i] = oh * g.sh - g.ph;
           a_p1[i] = ow * g.sw - g.pw;
           a_p2[i] = b * g.h * g.w;
@@ -319,16 +320,16 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
           a_p0[i] = -(1 << 28);
         }
         a_ptr[i] = g.A + ((long long)pix * g.xs + g.xo + q * 4);
-        const int rc = k / g.cp;
+        const int rc = fdiv(k, g.dv.f[DV_CP]);
         a_s2[i] = k - rc * g.cp;          // ci
-        a_s0[i] = rc / g.kw;              // r
+        a_s0[i] = fdiv(rc, g.dv.f[DV_KW]);   // r
         a_s1[i] = rc - a_s0[i] * g.kw;    // c
       } else {  // DGRAD: m = (b,u,v) of the phase, k = (a, bb, co)
         int pix = 0;
         if (m < g.M) {
           const int hw = g.hc * g.wc;
-          const int b = m / hw, rem = m - b * hw;
-          const int u = rem / g.wc, v = rem - u * g.wc;
+          const int b = fdiv(m, g.dv.f[DV_HCWC]), rem = m - b * hw;
+          const int u = fdiv(rem, g.dv.f[DV_WC]), v = rem - u * g.wc;
           a_p0[i] = u + g.ey;
           a_p1[i] = v + g.ex;
           a_p2[i] = b * g.ho * g.wo;
@@ -337,9 +338,9 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
           a_p0[i] = -(1 << 28);
         }
         a_ptr[i] = g.A + ((long long)pix * g.ys + g.yo + q * 4);
-        const int ab = k / g.cout;
+        const int ab = fdiv(k, g.dv.f[DV_COUT]);
         a_s2[i] = k - ab * g.cout;        // co
-        a_s0[i] = ab / g.nb;              // a
+        a_s0[i] = fdiv(ab, g.dv.f[DV_NB]);   // a
         a_s1[i] = ab - a_s0[i] * g.nb;    // bb
       }
     } else {  // WGRAD MC: m = (r,c,ci) fixed per slot, k = pixel advances
@@ -347,8 +348,8 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
       const int krow = flat / BM, col = flat - krow * BM;
       const int m = m0 + col;
       if (m < g.M) {
-        const int rc = m / g.cp, ci = m - rc * g.cp;
-        const int r = rc / g.kw, c = rc - r * g.kw;
+        const int rc = fdiv(m, g.dv.f[DV_CP]), ci = m - rc * g.cp;
+        const int r = fdiv(rc, g.dv.f[DV_KW]), c = rc - r * g.kw;
         a_p0[i] = r - g.ph;
         a_p1[i] = c - g.pw;
         a_p2[i] = ci;
@@ -357,9 +358,9 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
       }
       const int pix = kt0 * BK + krow;
       const int hw = g.ho * g.wo;
-      a_s0[i] = pix / hw;                       // b
+      a_s0[i] = fdiv(pix, g.dv.f[DV_HW]);   // b
       const int rem = pix - a_s0[i] * hw;
-      a_s1[i] = rem / g.wo;                     // oh
+      a_s1[i] = fdiv(rem, g.dv.f[DV_WO]); // oh
       a_s2[i] = rem - a_s1[i] * g.wo;           // ow
       if (m < g.M) a_ptr[i] = g.A + ((long long)(a_p0[i] * g.w + a_p1[i]) * g.xs + g.xo + a_p2[i]);
       a_off[i] = ((a_s0[i] * g.h + a_s1[i] * g.sh) * g.w + a_s2[i] * g.sw) * g.xs;
@@ -381,9 +382,9 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
       b_p0[i] = nn < g.N ? nn : -1;
       b_ptr[i] = g.B + ((long long)(nn < g.N ? nn : 0) * g.cout + q * 4);
       const int k = kt0 * BK + q * 4;
-      const int ab = k / g.cout;
+      const int ab = fdiv(k, g.dv.f[DV_COUT]);
       b_s2[i] = k - ab * g.cout;
-      b_s0[i] = ab / g.nb;
+      b_s0[i] = fdiv(ab, g.dv.f[DV_NB]);
       b_s1[i] = ab - b_s0[i] * g.nb;
     } else {  // MC: rows = k, cols = n
       const int flat = j * 256 + lane * 4;
@@ -400,9 +401,9 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
   int t_r = 0, t_c = 0, t_ch = 0;
   if constexpr (ut) {
     const int k = kt0 * BK;
-    const int rc = k / cred;
+    const int rc = fdiv(k, g.dv.f[OP == OP_FWD ? DV_CP : DV_COUT]);
     t_ch = k - rc * cred;
-    t_r = rc / (OP == OP_FWD ? g.kw : g.nb);
+    t_r = fdiv(rc, g.dv.f[OP == OP_FWD ? DV_KW : DV_NB]);
     t_c = rc - t_r * (OP == OP_FWD ? g.kw : g.nb);
   }
 
@@ -716,6 +717,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
   // the K loop, keeps an s_waitcnt vmcnt(0) in every K-tile (and so drains
   // the DMA ring it cannot see)
   __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0)
+  JR_ST(stamp.decoded();)
   if (kt0 < kt1) {
     // prologue: tiles kt0 .. kt0+NBUF-2 in flight
 #pragma unroll
@@ -768,13 +770,18 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs g) {
 
   if constexpr (SK) {
     sk_first = false;
+    reload_args(g);                      // what the hand-off and the epilogue read
     int owner, npieces, kind;
     if (sk_cut(g, tile, kt0, kt1, &owner, &npieces, &kind) &&
-        !sk_handoff<TM, TN>(g, acc, wave, lane, owner, npieces, kind, lb))
+        !sk_handoff<TM, TN>(g, acc, wave, lane, owner, npieces, kind, lb)) {
+      JR_ST(stamp.handoff(true);)
       continue;                      // another block finishes the tile
+    }
   }
+  JR_ST(stamp.handoff(false);)
   // ---------------------------------------------------------------- epilogue
   conv_epilogue<OP, WM, TM, TN, false>(g, acc, smem + wave * stage_floats<WN>(), m0 + wm0, n0 + wn0, lane);
+  JR_ST(stamp.epilogue();)
   if constexpr (!SK) break;
   }
   JR_ST(stamp.end(g.dbg);)
@@ -842,11 +849,19 @@ static void fill_scales(ConvArgs& a, const jr_conv_desc* d, int op, int dtype) {
 
 #ifdef JR_STAMPS
 static unsigned long long* g_dbg_stamps = nullptr;
-// diagnostic builds: every following conv GEMM launch writes 8 stamps per
-// block into p (ConvArgs::dbg; the caller sizes it for the grid)
+static int g_dbg_launch = 0;
+constexpr size_t kStampRegion = (size_t)kStampWords << 16;   // words per launch: 65,536 blocks
+// diagnostic builds: the following conv GEMM launches write kStampWords stamps
+// per block into p (ConvArgs::dbg), the i-th launch since this call (a DGRAD
+// op: one per stride phase) into its own region of kStampRegion words; the
+// caller sizes p for the launches it makes
 JR_API int jr_debug_set_stamps(void* p) {
   g_dbg_stamps = static_cast<unsigned long long*>(p);
+  g_dbg_launch = 0;
   return JR_OK;
+}
+static unsigned long long* next_stamp_region() {
+  return g_dbg_stamps ? g_dbg_stamps + kStampRegion * (size_t)g_dbg_launch++ : nullptr;
 }
 #endif
 
@@ -948,11 +963,20 @@ static int run_gemm(int dtype, ConvArgs a, const Plan& p, void* out, void* ws, s
     a.s_mb = (long long)wsm;
   }
   a.M = p.M; a.N = p.N; a.K = p.K;
-  JR_ST(a.dbg = g_dbg_stamps;)
+  JR_ST(a.dbg = next_stamp_region();)
   a.ktiles = p.ktiles;
   a.kt_per_split = p.kt_per_split;
   a.ntn = p.nt;
   a.slab_elems = (long long)p.M * p.N;
+  {   // reciprocals of the launch's runtime divisors (conv_divs reads these fields only)
+    jr_conv_desc dd{};
+    dd.ho = a.ho; dd.wo = a.wo; dd.kw = a.kw; dd.c_in = a.cin; dd.c_out = a.cout;
+    Phase ph{};
+    ph.hc = a.hc; ph.wc = a.wc; ph.nb = a.nb;
+    bool exact;
+    a.dv = conv_divs(&dd, dtype, ph, p, &exact);
+    if (!exact) return fail(JR_ERR_UNSUPPORTED, "conv: GEMM indices past 31 bits (no exact reciprocal for the decode)");
+  }
   if (p.splits > 1) {
     if (!ws || ws_bytes < plan_ws(p)) return fail(JR_ERR_WORKSPACE, "conv: workspace too small for split-K");
     a.C = static_cast<float*>(ws);
@@ -1477,6 +1501,9 @@ JR_API int jr_conv2d_debug_time(const jr_conv_desc* d, int cfg, int dbg, const v
   Plan p = plan_for(d, OP_FWD, JR_F32, Phase{}, cfg);
   p.splits = 1; p.kt_per_split = p.ktiles;
   a.M = p.M; a.N = p.N; a.K = p.K; a.ktiles = p.ktiles; a.kt_per_split = p.kt_per_split; a.ntn = p.nt;
+  bool exact;
+  a.dv = conv_divs(d, JR_F32, Phase{}, p, &exact);
+  if (!exact) return fail(JR_ERR_UNSUPPORTED, "debug_time: GEMM indices past 31 bits");
   hipStream_t s = as_stream(stream);
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0);
@@ -1525,4 +1552,41 @@ JR_API int jr_conv2d_get_config(const jr_conv_desc* d, int op, int dtype, int ph
   const OpPhases phases(d, op);
   const Phase* ph = phases.at(op, phase);
   return ph ? plan_for(d, op, dtype, *ph).cfg : -1;
+}
+
+// Test hooks of the division-free decode (host only, no GPU; not part of
+// jr.h: tests/test_conv_fastdiv.py binds them).  out: (mul, add, shift)
+// triples of the planner's FastDiv, mul = 0 where the form is not exact.
+static_assert(sizeof(FastDiv) == 3 * sizeof(uint32_t), "hooks copy FastDiv as three words");
+JR_API int jr_debug_fastdiv(uint64_t d, uint64_t nmax, uint32_t* out) {
+  if (!out) return fail(JR_ERR_INVALID, "conv fastdiv: null output");
+  const FastDiv f = fastdiv_for(d, nmax);
+  out[0] = f.m; out[1] = f.a; out[2] = f.s;
+  return JR_OK;
+}
+
+// the divisors, dividend bounds and reciprocals (DV_COUNT of each, in DV_*
+// order) of the GEMM that (d, op, dtype, phase) launches at config cfg (-1:
+// the planned one); returns DV_COUNT, or 0 where the launcher would refuse the
+// GEMM (a divisor without an exact reciprocal)
+JR_API int jr_debug_conv_divs(const jr_conv_desc* d, int op, int dtype, int phase, int cfg, uint64_t* div,
+                              uint64_t* nmax, uint32_t* out) {
+  int rc = validate(d, op, dtype);
+  if (rc) return rc;
+  if (!div || !nmax || !out) return fail(JR_ERR_INVALID, "conv divs: null output");
+  if (cfg < -1 || (cfg >= 0 && (cfg_tile(cfg) >= cfg_count(dtype) || cfg_splits(cfg) > kMaxSplits)))
+    return fail(JR_ERR_INVALID, "conv divs: bad config index");
+  const OpPhases phases(d, op);
+  const Phase* ph = phases.at(op, phase);
+  if (!ph) return fail(JR_ERR_INVALID, "conv divs: bad phase");
+  bool ok = true;
+  const Plan p = op == OP_DGRAD ? dgrad_phase_plan(d, dtype, *ph, cfg, &ok) : plan_for(d, op, dtype, *ph, cfg);
+  unsigned long long dd[DV_COUNT], nn[DV_COUNT];
+  bool exact;
+  const ConvDivs v = conv_divs(d, dtype, op == OP_DGRAD ? *ph : Phase{}, p, &exact, dd, nn);
+  for (int i = 0; i < DV_COUNT; ++i) {
+    div[i] = dd[i]; nmax[i] = nn[i];
+    out[3 * i] = v.f[i].m; out[3 * i + 1] = v.f[i].a; out[3 * i + 2] = v.f[i].s;
+  }
+  return exact ? DV_COUNT : 0;
 }

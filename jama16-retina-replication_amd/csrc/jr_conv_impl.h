@@ -39,7 +39,7 @@ struct ConvArgs {
   // halo-tiled FWD (jr_conv_halo.hip): halo rows per block and slot columns
   int halo_nr, halo_wp;
   // diagnostic builds only (-DJR_STAMPS, `make stamps`): per-block s_memtime /
-  // s_memrealtime stamps, 8 per block (jr_debug_set_stamps); nullptr otherwise
+  // s_memrealtime stamps, kStampWords per block (jr_debug_set_stamps); nullptr otherwise
   unsigned long long* dbg;
   // grouped launches (ensemble members, jr_conv2d_fwd_bn_stats_grouped): the
   // member is blockIdx.y of the GEMM; byte strides between consecutive
@@ -63,7 +63,18 @@ struct ConvArgs {
   const float* a_max;
   const float* b_max;
   float a_bnd, b_bnd;
+  // multiply-shift reciprocals of the launch's runtime divisors (the planner's
+  // conv_divs; fdiv below)
+  ConvDivs dv;
 };
+
+// n / d (0 <= n within the range the planner validated f for) without a
+// division: one 32 x 32 -> 64 multiply-add and a shift (jr_conv_plan.h
+// FastDiv; the launcher refuses a GEMM whose reciprocals conv_divs does not
+// call exact, so no kernel carries a division to fall back to).
+__device__ __forceinline__ int fdiv(int n, const FastDiv& f) {
+  return (int)((uint32_t)(((uint64_t)(uint32_t)n * f.m + f.a) >> 32) >> f.s);
+}
 
 // max of the 64 floats at p (every lane of the wave gets it)
 __device__ __forceinline__ float absmax64(const float* p, int lane) {
@@ -102,28 +113,59 @@ __device__ __forceinline__ void member_offsets(ConvArgs& g) {
   }
 }
 
+// Re-reads g from the kernel argument segment (the kernel's only argument is
+// its ConvArgs) through a pointer the optimiser cannot see through.  A kernel
+// that runs a segment loop (k_conv SK) calls this where a segment's set-up and
+// where its hand-off and epilogue start: read once at kernel entry, every
+// field those parts use stays live across the K loop, in SGPRs the loop has
+// not got (they came back as v_readlane / v_writelane spill traffic on every
+// segment).  member_offsets is applied again to the fresh copy.
+__device__ __forceinline__ void reload_args(ConvArgs& g) {
+  auto kp = (const __attribute__((address_space(4))) ConvArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  g = *(const ConvArgs*)kp;
+  member_offsets(g);
+}
+
 #ifdef JR_STAMPS
 // [0] realtime at start, [1] realtime at end (100 MHz), [2] cycles of the
-// prologue (ring fill to the first barrier), [3] cycles of the K loop, [4]
-// cycles of the epilogue, [5] cycles the loop spent in vmcnt waits +
+// set-up (decode + ring fill to the first barrier), [3] cycles of the K loop,
+// [4] cycles of the epilogue, [5] cycles the loop spent in vmcnt waits +
 // barriers, [6] HW_ID, [7] XCC_ID -- of wave 0 of the block
+// A stream-K block runs several (tile, K range) segments: every phase is a
+// sum over the block's segments, and the words go on: [8] cycles of the
+// hand-offs (publish / count / absorb, the x6h scale-back before them
+// included), [9] segments run, [10] the part of [2] before the first DMA
+// piece (row, tap and column decode), [11] segments that ended by handing
+// their piece on (no epilogue); [12..15] unused.
+constexpr int kStampWords = 16;
 struct Stamps {
-  unsigned long long r0, c0, cp, cl, w;
+  unsigned long long r0, ts, w, su, dc, lp, ho, ep, nseg, nmove;
+  __device__ __forceinline__ unsigned long long lap() {
+    const unsigned long long t = __builtin_amdgcn_s_memtime(), d = t - ts;
+    ts = t;
+    return d;
+  }
   __device__ __forceinline__ void start() {
     r0 = __builtin_amdgcn_s_memrealtime();
-    c0 = __builtin_amdgcn_s_memtime();
-    w = 0;
+    ts = __builtin_amdgcn_s_memtime();
+    w = su = dc = lp = ho = ep = nseg = nmove = 0;
   }
-  __device__ __forceinline__ void prologue() { cp = __builtin_amdgcn_s_memtime(); }
-  __device__ __forceinline__ void loop() { cl = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void decoded() { const unsigned long long d = lap(); dc += d; su += d; }
+  __device__ __forceinline__ void prologue() { su += lap(); ++nseg; }
+  __device__ __forceinline__ void loop() { lp += lap(); }
+  __device__ __forceinline__ void handoff(bool moved_on) { ho += lap(); nmove += moved_on ? 1 : 0; }
+  __device__ __forceinline__ void epilogue() { ep += lap(); }
   __device__ __forceinline__ unsigned long long now() { return __builtin_amdgcn_s_memtime(); }
   __device__ __forceinline__ void end(unsigned long long* dbg) {
-    const unsigned long long ce = __builtin_amdgcn_s_memtime(), re = __builtin_amdgcn_s_memrealtime();
+    ep += lap();
+    const unsigned long long re = __builtin_amdgcn_s_memrealtime();
     if (dbg == nullptr || threadIdx.x != 0) return;
-    unsigned long long* o = dbg + 8ull * (blockIdx.z * gridDim.x + blockIdx.x);
-    o[0] = r0; o[1] = re; o[2] = cp - c0; o[3] = cl - cp; o[4] = ce - cl; o[5] = w;
+    unsigned long long* o = dbg + (unsigned long long)kStampWords * (blockIdx.z * gridDim.x + blockIdx.x);
+    o[0] = r0; o[1] = re; o[2] = su; o[3] = lp; o[4] = ep; o[5] = w;
     o[6] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
     o[7] = __builtin_amdgcn_s_getreg((3 << 11) | 20);    // HW_REG_XCC_ID
+    o[8] = ho; o[9] = nseg; o[10] = dc; o[11] = nmove;
   }
 };
 #define JR_ST(x) x
@@ -134,8 +176,8 @@ struct Stamps {
 // Input pixel (over all images) of DGRAD row m of the phase.
 __device__ __forceinline__ long long dgrad_pix(const ConvArgs& g, int m) {
   const int hw = g.hc * g.wc;
-  const int b = m / hw, rem = m - b * hw;
-  const int u = rem / g.wc, v = rem - u * g.wc;
+  const int b = fdiv(m, g.dv.f[DV_HCWC]), rem = m - b * hw;
+  const int u = fdiv(rem, g.dv.f[DV_WC]), v = rem - u * g.wc;
   return ((long long)b * g.h + g.sh * u + g.py) * g.w + g.sw * v + g.px;
 }
 
@@ -148,7 +190,7 @@ __device__ __forceinline__ long long out_row(const ConvArgs& g, int m) {
     return dgrad_pix(g, m) * g.c_stride + g.c_off;
   } else {
     if (g.cp == g.cin) return (long long)m * g.N;
-    const int rc = m / g.cp, ci = m - rc * g.cp;
+    const int rc = fdiv(m, g.dv.f[DV_CP]), ci = m - rc * g.cp;
     if (ci >= g.cin) return -1;
     return ((long long)rc * g.cin + ci) * g.N;
   }
@@ -360,8 +402,8 @@ __device__ __forceinline__ bool sk_cut(const ConvArgs& g, int tile, int kt0, int
                                        int* kind) {
   if (kt0 == 0 && kt1 == g.ktiles) return false;
   const long long t0 = (long long)tile * g.ktiles;       // the tile's first iteration
-  *owner = (int)(t0 / g.sk_ipb);
-  *npieces = (int)((t0 + g.ktiles - 1) / g.sk_ipb) - *owner + 1;
+  *owner = fdiv((int)t0, g.dv.f[DV_IPB]);     // (iteration indices stay below 2^31: the launcher checks)
+  *npieces = fdiv((int)t0 + g.ktiles - 1, g.dv.f[DV_IPB]) - *owner + 1;
   *kind = kt0 == 0 ? 1 : 0;
   return true;
 }

@@ -307,6 +307,60 @@ int validate(const jr_conv_desc* d, int op, int dtype) {
   return JR_OK;
 }
 
+// ---------------------------------------------------- division-free decode
+FastDiv fastdiv_for(unsigned long long d, unsigned long long nmax) {
+  const FastDiv none{0u, 0u, 0u};
+  if (d == 0 || d > 0x7fffffffULL || nmax > 0xffffffffULL) return none;
+  if (d == 1) return nmax < 0xffffffffULL ? FastDiv{0xffffffffu, 0xffffffffu, 0u} : none;
+  unsigned s = 0;
+  while ((2ULL << s) <= d) ++s;                 // floor(log2 d)
+  if ((1ULL << s) == d) return FastDiv{0x80000000u, 0u, s - 1};   // n >> k, every 32-bit n
+  const unsigned long long two = 1ULL << (32 + s);
+  const unsigned long long m = (two + d - 1) / d;   // < 2^32 (d > 2^s)
+  const unsigned long long e = m * d - two;         // < d
+  // exact while n e < 2^(32+s): e < 2^31 and nmax < 2^32, so the product fits 64 bits
+  if (e != 0 && nmax > (two - 1) / e) return none;
+  return FastDiv{(unsigned)m, 0u, s};
+}
+
+ConvDivs conv_divs(const jr_conv_desc* d, int dtype, const Phase& ph, const Plan& p, bool* exact,
+                   unsigned long long* div, unsigned long long* nmax) {
+  const TileCfg& t = *cfg_entry(dtype, p.tile).t;
+  const unsigned long long cp = (unsigned long long)chan_pad(d->c_in, dtype);
+  // the stream-K walk keeps its iteration indices in 32-bit ints where it multiplies
+  const bool walk32 = (unsigned long long)std::max(p.mt * (long long)p.nt, 1LL) * std::max(p.ktiles, 1) + p.ktiles < (1ULL << 31);
+  // the largest row and reduction index a block decodes: tiles are whole, and
+  // a row past M may be decoded before it is dropped
+  const unsigned long long rows = (unsigned long long)std::max(p.mt, 1) * t.bm - 1;
+  const unsigned long long ks = (unsigned long long)std::max(p.ktiles, 1) * t.bk - 1;
+  const unsigned long long both = std::max(rows, ks);
+  const unsigned long long W = (unsigned long long)std::max(p.mt * p.nt, 1) * std::max(p.ktiles, 1);
+  unsigned long long dd[DV_COUNT] = {}, nn[DV_COUNT] = {};
+  dd[DV_HW] = (unsigned long long)d->ho * d->wo;   nn[DV_HW] = both;      // FWD rows, WGRAD pixels along k
+  dd[DV_WO] = (unsigned long long)d->wo;           nn[DV_WO] = std::max<unsigned long long>(both, t.bk);   // (WGRAD: BK / wo)
+  dd[DV_HCWC] = (unsigned long long)ph.hc * ph.wc; nn[DV_HCWC] = rows;    // DGRAD rows of the phase
+  dd[DV_WC] = (unsigned long long)ph.wc;           nn[DV_WC] = rows;
+  dd[DV_CP] = cp;                                  nn[DV_CP] = both;      // FWD k, WGRAD rows
+  dd[DV_COUT] = (unsigned long long)d->c_out;      nn[DV_COUT] = ks;      // DGRAD k
+  dd[DV_KW] = (unsigned long long)d->kw;           nn[DV_KW] = both;      // taps of FWD k / WGRAD rows
+  dd[DV_NB] = (unsigned long long)ph.nb;           nn[DV_NB] = ks;        // taps of DGRAD k
+  dd[DV_NTN] = (unsigned long long)p.nt;           nn[DV_NTN] = W;        // tile -> (mt, nt)
+  dd[DV_KTILES] = p.sk && walk32 ? (unsigned long long)p.ktiles : 0; nn[DV_KTILES] = W + p.ktiles;   // stream-K walk
+  dd[DV_IPB] = p.sk && walk32 ? (unsigned long long)p.sk_ipb : 0;    nn[DV_IPB] = W + p.ktiles;
+  ConvDivs out{};
+  // a divisor of 0 is one this launch never divides by (DV_HCWC outside DGRAD,
+  // a DGRAD phase no tap reaches, the walk of a plain grid); a stream-K walk
+  // past 32-bit iteration indices has no exact reciprocal either
+  *exact = !p.sk || walk32;
+  for (int i = 0; i < DV_COUNT; ++i) {
+    out.f[i] = fastdiv_for(dd[i], nn[i]);
+    if (dd[i] != 0 && out.f[i].m == 0) *exact = false;
+    if (div) div[i] = dd[i];
+    if (nmax) nmax[i] = nn[i];
+  }
+  return out;
+}
+
 // ------------------------------------------------------------ conv1 direct
 bool conv1_direct_ok(const jr_conv_desc* d, int dtype) {
   // opt-in (JR_CONV1_DIRECT=1, read once), fp32 only: per kernel (rocprofv3,

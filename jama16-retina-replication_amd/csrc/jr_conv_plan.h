@@ -253,6 +253,41 @@ size_t ws_bytes_for(const jr_conv_desc* d, int op, int dtype);
 
 int validate(const jr_conv_desc* d, int op, int dtype);
 
+// ------------------------------------------------- division-free decode
+// n / d for 0 <= n <= nmax as one 32 x 32 -> 64 multiply-add and a shift:
+//   q = (uint32)((n * m + a) >> 32) >> s
+// round-up form (a = 0): m = ceil(2^(32+s) / d), s = floor(log2 d) (d = 2^k,
+// k >= 1: m = 2^31, s = k - 1).  With e = m d - 2^(32+s) (0 <= e < d) the
+// quotient is exact while n e < 2^(32+s); e < 2^(s+1), so every n < 2^31 is.
+// d = 1 has no 32-bit round-up multiplier: m = a = 2^32 - 1, s = 0 gives
+// (n + 1)(2^32 - 1) >> 32 = n for n < 2^32 - 1.
+// m = 0: the form is not exact on [0, nmax] (or d = 0, or d >= 2^31): no reciprocal.
+struct FastDiv {
+  unsigned m, a, s;
+};
+FastDiv fastdiv_for(unsigned long long d, unsigned long long nmax);
+inline unsigned fastdiv_apply(const FastDiv& f, unsigned n) {
+  return (unsigned)(((unsigned long long)n * f.m + f.a) >> 32) >> f.s;
+}
+
+// The reciprocals of one GEMM launch (ConvArgs::dv): of every runtime divisor
+// the kernels' row, tap and column decode, the output addressing and the
+// stream-K walk divide by, each valid over the whole range its dividends
+// take in that launch (DV_*: the order of div[] / nmax[] below).
+enum { DV_HW, DV_WO, DV_HCWC, DV_WC, DV_CP, DV_COUT, DV_KW, DV_NB, DV_NTN, DV_KTILES, DV_IPB, DV_COUNT };
+struct ConvDivs {
+  FastDiv f[DV_COUNT];
+};
+// exact = false: some divisor of the launch has no exact reciprocal on its
+// range (FastDiv m = 0) -- the kernels carry no division to fall back to, so
+// the launcher refuses such a GEMM (row, reduction or stream-K iteration
+// indices of 2^31 and up: beyond validate's 32-bit tensor sizes in practice).
+// div / nmax (optional): the divisors (0: unused by this launch) and the
+// largest dividend of each.
+// (of d: ho, wo, kw, c_in, c_out; of ph: hc, wc, nb -- zeros outside DGRAD)
+ConvDivs conv_divs(const jr_conv_desc* d, int dtype, const Phase& ph, const Plan& p, bool* exact,
+                   unsigned long long* div = nullptr, unsigned long long* nmax = nullptr);
+
 // conv2d_1 as a direct VALU convolution (the jr_conv_direct kernel): the geometry
 // test, its statistics partials (P of R rows) and their workspace
 constexpr int kD1Rows = 1024;   // output pixels per block (= R of the statistics partials)
