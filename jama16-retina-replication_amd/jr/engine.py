@@ -173,12 +173,29 @@ class Replica:
         self.slices = {b: sorted(o) for b, o in slices.items()}
         self._aug_ws = None             # the augmented upload's workspace and tables, at first use
 
+    def _after_fill(self, t: torch.Tensor) -> torch.Tensor:
+        """The stream-ordering rule of every allocation (DESIGN.md "Step
+        audit"): a buffer is allocated and filled on torch's current stream,
+        and lane 0 -- where every step starts, and which the other lanes
+        fork from -- then waits for that stream.  The lanes are streams of
+        their own and order nothing with the current stream implicitly:
+        without the wait a fill that lands late overwrites what a lane wrote
+        (the zero fill of `moving` after _reset_bn_moving's mean 0 / variance
+        1).  The one place: _t, _table and _dev_bytes all end here."""
+        cur = torch.cuda.current_stream(self.device)
+        if cur != self.stream:
+            self.stream.wait_stream(cur)
+        return t
+
     def _t(self, n: int, dtype=torch.float32) -> torch.Tensor:
-        return torch.zeros(int(n), dtype=dtype, device=self.device)
+        return self._after_fill(torch.zeros(int(n), dtype=dtype, device=self.device))
+
+    def _dev_bytes(self, data: bytes) -> torch.Tensor:
+        return self._after_fill(torch.frombuffer(bytearray(data), dtype=torch.uint8).to(self.device))
 
     def _table(self, struct, rows) -> torch.Tensor:
         """A device copy of a ctypes struct array."""
-        return torch.frombuffer(bytearray(bytes((struct * len(rows))(*rows))), dtype=torch.uint8).to(self.device)
+        return self._dev_bytes(bytes((struct * len(rows))(*rows)))
 
     def _a_all(self, b: int) -> list:
         return [("a", b, o) for o in self.slices[b]]
@@ -257,6 +274,11 @@ class Replica:
         their own.  The scale is a constant, not a measurement: a frozen x6h
         prediction stays bitwise independent of the other images of the batch."""
         return 2.0 * self.act_bound if self.x6h and self.x6h_frozen else None
+
+    @staticmethod
+    def _frozen_reads(b: Build) -> list:
+        """A frozen call list's BN applies and fused pools read self.frozen, not the batch statistics."""
+        return [("frozen",)] if b.stats_shift else []
 
     def _wmax(self, u: ConvUnit) -> int:
         return self.absmax.data_ptr() + 4 * 64 * self._arow[u.first.idx] * self.members
@@ -787,7 +809,8 @@ class Engine(Replica):
                     self.dacts[u.x].data_ptr(), ws, wsb, s))
         self.synchronize()
         if self.train_mode:
-            self.grads.zero_()
+            with torch.cuda.stream(self.stream):
+                self.grads.zero_()
         self._own_tiles()
 
     def conv_configs(self) -> dict:
@@ -883,15 +906,20 @@ class Engine(Replica):
     # ------------------------------------------------------------ parameters
     def load_params(self, flat: np.ndarray) -> None:
         """Keras-layout flat parameters (jr.init.param_layout order)."""
-        self.params.copy_(torch.from_numpy(self.plan.to_internal(self.g, flat)).to(self.device))
+        host = torch.from_numpy(self.plan.to_internal(self.g, flat))
+        with torch.cuda.stream(self.stream):     # in order with the steps that read and update them
+            self.params.copy_(host.to(self.device))
+            if self.train_mode:
+                self.accum.zero_()
+                self.grads.zero_()
+                # optimizer state restarts with the parameters: Adam's v slot and
+                # its fp32 beta powers (TF initialises beta1_power / beta2_power to
+                # beta1 / beta2 with the slots)
+                if self.adam_v is not None:
+                    self.adam_v.zero_()
+        # (and a caller's torch work on these tensors, on its own stream, sees the new values)
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
         if self.train_mode:
-            self.accum.zero_()
-            self.grads.zero_()
-            # optimizer state restarts with the parameters: Adam's v slot and
-            # its fp32 beta powers (TF initialises beta1_power / beta2_power to
-            # beta1 / beta2 with the slots)
-            if self.adam_v is not None:
-                self.adam_v.zero_()
             self.adam_t = 0
             self.adam_b1p, self.adam_b2p = np.float32(self.adam_b1), np.float32(self.adam_b2)
 
@@ -1002,6 +1030,10 @@ class Engine(Replica):
     def _w_reads(self) -> list:
         return [("w16",) if (self.dt == _ffi.JR_BF16 or self.x8p) else ("p",)] + ([("wmax",)] if self.x6h else [])
 
+    def _dmax_reads(self, u: ConvUnit) -> list:
+        """x6h: the data- and filter-gradient GEMMs scale dy by the launch's magnitude row."""
+        return [("dmax", u.first.idx)] if self.x6h else []
+
     def _dbeta(self, m) -> int:
         return self._gp(f"batch_normalization_{m.idx + 1}/beta")
 
@@ -1075,8 +1107,8 @@ class Engine(Replica):
             b.add(b.fwd, fn,
                   (dt, len(u.members), ctypes.byref(segs), raw, 0, u.cout, M, u.cout, mean + b.stats_shift,
                    invstd + b.stats_shift) + lim + (s,),
-                  "bn_relu", ln, [("r", uid), ("p",)], [("a", m.y.buf, m.y.c_off) for m in u.members],
-                  nbytes=2 * M * u.cout * self.esz)
+                  "bn_relu", ln, [("r", uid), ("p",)] + self._frozen_reads(b),
+                  [("a", m.y.buf, m.y.c_off) for m in u.members], nbytes=2 * M * u.cout * self.esz)
             return
         for m, co in zip(u.members, u.col_off):
             if m.y.buf in self.fused_bufs:
@@ -1086,7 +1118,8 @@ class Engine(Replica):
                   (dt, raw, co, u.cout, M, m.cout, self.mean[m.idx].data_ptr() + b.stats_shift,
                    self.invstd[m.idx].data_ptr() + b.stats_shift, self._beta(m), self._A(m.y.buf), m.y.c_off,
                    g.bufs[m.y.buf].c) + lim + (s,),
-                  "bn_relu", ln, [("r", uid), ("p",)], [("a", m.y.buf, m.y.c_off)], nbytes=2 * M * m.cout * self.esz)
+                  "bn_relu", ln, [("r", uid), ("p",)] + self._frozen_reads(b), [("a", m.y.buf, m.y.c_off)],
+                  nbytes=2 * M * m.cout * self.esz)
 
     def _fwd_pool(self, b: Build, i: int, n: PoolNode) -> None:
         L, dt, B, ln = self.lib, self.dt, b.B, b.lane_of[i]
@@ -1103,7 +1136,7 @@ class Engine(Replica):
                   (ctypes.byref(d), dt, self.raw_unit[puid].data_ptr(), self.mean[pn.idx].data_ptr() + b.stats_shift,
                    self.invstd[pn.idx].data_ptr() + b.stats_shift, self._beta(pn), self._A(n.y.buf),
                    self.argmax[i].data_ptr()) + lim + (s,),
-                  "bn_relu_maxpool_fwd", ln, [("r", puid), ("p",)], out + [("am", i)],
+                  "bn_relu_maxpool_fwd", ln, [("r", puid), ("p",)] + self._frozen_reads(b), out + [("am", i)],
                   nbytes=B * n.c * (n.h * n.w * self.esz + n.ho * n.wo * (self.esz + 1)))
         elif n.kind == "maxpool":
             b.add(b.fwd, L.jr_maxpool3x3s2_fwd,
@@ -1156,7 +1189,7 @@ class Engine(Replica):
             arr[k] = sg
             arr[k].block0 = blocks
             blocks += sg.blocks
-        table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+        table = self._dev_bytes(bytes(arr))
         b.keep.append(table)
         nbytes = sum(4 * sg.m * sg.n * (sg.splits + 1) for sg, _ in b.pending)
         b.add(b.bwd, self.lib.jr_wgrad_reduce, (table.data_ptr(), len(b.pending), blocks, b.S[0]), "wgrad_reduce", 0,
@@ -1284,14 +1317,14 @@ class Engine(Replica):
             return
         b.add(b.bwd, self.lib.jr_conv2d_bwd_data,
               (ctypes.byref(d), self.cdt, draw, self._wd(u), self._D(u.x), acc, b.WS[ln], b.wsb, b.S[ln]),
-              "conv_dgrad", ln, [dkey] + self._w_reads(), self._d_all(u.x) + [("ws", ln)])
+              "conv_dgrad", ln, [dkey] + self._w_reads() + self._dmax_reads(u), self._d_all(u.x) + [("ws", ln)])
         b.written.add(u.x)
 
     def _bwd_wgrad(self, b: Build, ln: int, wl: int, u: ConvUnit, d, draw: int, dkey) -> None:
         """The filter gradient on lane wl: deferred (split-K slabs kept for
         the next jr_wgrad_reduce) or final; the stem's on lane 1 (wl != ln)
         use their own workspace."""
-        uid, reads = u.first.idx, self._ax_reads(u.x) + [dkey]
+        uid, reads = u.first.idx, self._ax_reads(u.x) + [dkey] + self._dmax_reads(u)
         if uid in b.defer:
             sg, _, nb = b.defer[uid]
             b.add(b.bwd, self.lib.jr_conv2d_bwd_filter_slabs,

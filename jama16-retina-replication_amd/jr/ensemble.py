@@ -199,7 +199,7 @@ class EnsembleEngine(Replica):
                   (self.dt, M, raw, co, u.cout, self.raw_ms[uid], rows, mem.cout, mean + 4 * co + b.stats_shift,
                    inv + 4 * co + b.stats_shift, self.stats_ms, self._beta(mem), self.nparam, self._A(mem.y.buf),
                    mem.y.c_off, g.bufs[mem.y.buf].c, self.act_ms[mem.y.buf]) + lim + (s,),
-                  "bn_relu", ln, [("r", uid)], [("a", mem.y.buf, mem.y.c_off)])
+                  "bn_relu", ln, [("r", uid)] + self._frozen_reads(b), [("a", mem.y.buf, mem.y.c_off)])
 
     def _fwd_pool(self, b: Build, i: int, n) -> None:
         """Pools: the member-major buffers of a full batch are one batch of
@@ -220,7 +220,7 @@ class EnsembleEngine(Replica):
                 b.add(b.fwd, fn,
                       (ctypes.byref(d), self.dt, B, self.raw_unit[puid].data_ptr() + self.esz * m * self.raw_ms[puid],
                        mean, mean + 4 * pn.cout, self.stats_ms, self._beta(pn, m), self.nparam, yo, None) + lim + (s,),
-                      "bn_relu_maxpool_fwd", ln, [("r", puid)], out)
+                      "bn_relu_maxpool_fwd", ln, [("r", puid)] + self._frozen_reads(b), out)
             elif n.kind == "maxpool":
                 b.add(b.fwd, L.jr_maxpool3x3s2_fwd, (ctypes.byref(d), self.dt, xi, yo, None, s), "maxpool_fwd", ln,
                       self._a_all(n.x), out)

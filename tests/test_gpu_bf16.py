@@ -137,6 +137,18 @@ def _run_all(ffi, L, case, seed, cfg=None, extra_ws=0, raw=None):
     return out
 
 
+def _reset_configs(ffi, L, case):
+    """Back to the planner for every op and phase of the case's geometry:
+    libjr's forced tile configs are process-wide, and what _run_all forces
+    must not reach tests that run later in the same process."""
+    n, h, w, cin, cout, kh, kw, s, pad = case
+    d = _desc(ffi, n, h, w, cin, cout, kh, kw, s, pad, (cin + 7) // 8 * 8)[0]
+    for op in (0, 2):
+        ffi.check("reset", L.jr_conv2d_set_config(ctypes.byref(d), op, 1, 0, -1))
+    for ph in range(s * s if cin % 8 == 0 else 0):
+        ffi.check("reset", L.jr_conv2d_set_config(ctypes.byref(d), 1, 1, ph, -1))
+
+
 def _check(out):
     assert out["fwd"] < TOL_BF16_OUT, out
     if "dgrad" in out:
@@ -175,12 +187,15 @@ def test_conv_bf16_every_tile_config(case):
     L = ffi.load()
     n, h, w, cin, cout, kh, kw, s, pad = case
     extra = 3 * 4 * max(n * h * w * 8 * cout, kh * kw * 8 * cout) * 4
-    for t in range(L.jr_conv2d_num_configs(1)):
-        for sp in (0, 1, 3):
-            out = _run_all(ffi, L, case, seed=11, cfg=t | (sp << 8), extra_ws=extra)
-            assert out["fwd"] < TOL_BF16_OUT and out["wgrad"] < TOL_F32_OUT, (t, sp, out)
-            if "dgrad" in out:
-                assert out["dgrad"] < TOL_BF16_OUT, (t, sp, out)
+    try:
+        for t in range(L.jr_conv2d_num_configs(1)):
+            for sp in (0, 1, 3):
+                out = _run_all(ffi, L, case, seed=11, cfg=t | (sp << 8), extra_ws=extra)
+                assert out["fwd"] < TOL_BF16_OUT and out["wgrad"] < TOL_F32_OUT, (t, sp, out)
+                if "dgrad" in out:
+                    assert out["dgrad"] < TOL_BF16_OUT, (t, sp, out)
+    finally:
+        _reset_configs(ffi, L, case)
 
 
 @pytest.mark.parametrize("case", [(2, 17, 17, 128, 192, 1, 7, 1, "same"), (2, 17, 17, 160, 160, 7, 1, 1, "same"),
@@ -197,40 +212,42 @@ def test_conv_bf16_halo_configs(case):
     ffi = _lib()
     L = ffi.load()
     n, h, w, cin, cout, kh, kw, s, pad = case
-    taken = 0
-    extra = 4 * 4 * n * h * w * 8 * cout
-    for t in HALO_IDS:
-        for sp in (0, 2):
-            out = _run_all(ffi, L, case, seed=21, cfg=t | (sp << 8), extra_ws=extra)
-            assert out["fwd"] < TOL_BF16_OUT and out["wgrad"] < TOL_F32_OUT, (t, sp, out)
-            assert out["dgrad"] < TOL_BF16_OUT, (t, sp, out)
-            d, ho, wo = _desc(ffi, n, h, w, cin, cout, kh, kw, s, pad, (cin + 7) // 8 * 8)
-            taken += (L.jr_conv2d_get_config(ctypes.byref(d), 0, 1, 0) & 0xFF) == t
-    assert taken > 0, case
-    # fused BN statistics through the halo epilogue
-    rng = np.random.default_rng(5)
-    x = bf16_round(rng.standard_normal((n, h, w, cin)))
-    wt32 = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
-    d, ho, wo = _desc(ffi, n, h, w, cin, cout, kh, kw, s, pad, cin)
-    hwio, wtt = _weights(ffi, L, wt32)
-    X = dev_bf16(x)
-    wsb = L.jr_conv2d_workspace_size(ctypes.byref(d), 0, 1)
-    ws = torch.zeros(wsb // 4 + 4, device="cuda")
-    Y = torch.zeros(n * ho * wo * cout, dtype=torch.bfloat16, device="cuda")
-    MEAN, INV = torch.zeros(cout, device="cuda"), torch.zeros(cout, device="cuda")
-    for t in HALO_IDS:
-        ffi.check("set", L.jr_conv2d_set_config(ctypes.byref(d), 0, 1, 0, t))
-        if (L.jr_conv2d_get_config(ctypes.byref(d), 0, 1, 0) & 0xFF) != t:
-            continue
-        ffi.check("fwd+stats", L.jr_conv2d_fwd_bn_stats(ctypes.byref(d), 1, X.data_ptr(), wtt.data_ptr(), Y.data_ptr(),
-                                                         ctypes.c_float(1e-3), MEAN.data_ptr(), INV.data_ptr(),
-                                                         ws.data_ptr(), wsb, None))
-        y = host(Y).reshape(n * ho * wo, cout).astype(np.float64)   # statistics are of y as stored
-        mu = y.mean(0)
-        inv = 1.0 / np.sqrt(y.var(0) + 1e-3)
-        assert np.max(np.abs(MEAN.cpu().numpy() - mu)) <= 1e-5 * np.abs(y).max(), t
-        assert np.max(np.abs(INV.cpu().numpy() / inv - 1)) <= 1e-5, t
-    ffi.check("reset", L.jr_conv2d_set_config(ctypes.byref(d), 0, 1, 0, -1))
+    try:
+        taken = 0
+        extra = 4 * 4 * n * h * w * 8 * cout
+        for t in HALO_IDS:
+            for sp in (0, 2):
+                out = _run_all(ffi, L, case, seed=21, cfg=t | (sp << 8), extra_ws=extra)
+                assert out["fwd"] < TOL_BF16_OUT and out["wgrad"] < TOL_F32_OUT, (t, sp, out)
+                assert out["dgrad"] < TOL_BF16_OUT, (t, sp, out)
+                d, ho, wo = _desc(ffi, n, h, w, cin, cout, kh, kw, s, pad, (cin + 7) // 8 * 8)
+                taken += (L.jr_conv2d_get_config(ctypes.byref(d), 0, 1, 0) & 0xFF) == t
+        assert taken > 0, case
+        # fused BN statistics through the halo epilogue
+        rng = np.random.default_rng(5)
+        x = bf16_round(rng.standard_normal((n, h, w, cin)))
+        wt32 = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
+        d, ho, wo = _desc(ffi, n, h, w, cin, cout, kh, kw, s, pad, cin)
+        hwio, wtt = _weights(ffi, L, wt32)
+        X = dev_bf16(x)
+        wsb = L.jr_conv2d_workspace_size(ctypes.byref(d), 0, 1)
+        ws = torch.zeros(wsb // 4 + 4, device="cuda")
+        Y = torch.zeros(n * ho * wo * cout, dtype=torch.bfloat16, device="cuda")
+        MEAN, INV = torch.zeros(cout, device="cuda"), torch.zeros(cout, device="cuda")
+        for t in HALO_IDS:
+            ffi.check("set", L.jr_conv2d_set_config(ctypes.byref(d), 0, 1, 0, t))
+            if (L.jr_conv2d_get_config(ctypes.byref(d), 0, 1, 0) & 0xFF) != t:
+                continue
+            ffi.check("fwd+stats", L.jr_conv2d_fwd_bn_stats(
+                ctypes.byref(d), 1, X.data_ptr(), wtt.data_ptr(), Y.data_ptr(), ctypes.c_float(1e-3), MEAN.data_ptr(),
+                INV.data_ptr(), ws.data_ptr(), wsb, None))
+            y = host(Y).reshape(n * ho * wo, cout).astype(np.float64)   # statistics are of y as stored
+            mu = y.mean(0)
+            inv = 1.0 / np.sqrt(y.var(0) + 1e-3)
+            assert np.max(np.abs(MEAN.cpu().numpy() - mu)) <= 1e-5 * np.abs(y).max(), t
+            assert np.max(np.abs(INV.cpu().numpy() / inv - 1)) <= 1e-5, t
+    finally:
+        _reset_configs(ffi, L, case)
 
 
 def test_conv_weights_bf16_layouts():

@@ -36,6 +36,29 @@ def _same(a, b):
     return np.array_equal(_bits(a), _bits(b))
 
 
+def _diff(what, cfg, k, a, b, units=None):
+    """The message of a failed bitwise comparison: which array, which step,
+    how many words differ, the first differing word and -- for arrays in the
+    statistics layout ([mean(c) | invstd(c)] per conv launch, `units` =
+    [(c, rows)]) -- the first differing BN launch and which half of it."""
+    a, b = _bits(a).reshape(-1), _bits(b).reshape(-1)
+    if a.shape != b.shape:
+        return f"{cfg} step {k}: {what}: shapes {a.shape} vs {b.shape}"
+    bad = np.flatnonzero(a != b)
+    msg = f"{cfg} step {k}: {what}: {bad.size} of {a.size} words differ"
+    if bad.size:
+        i = int(bad[0])
+        msg += f", first at word {i} (0x{int(a[i]):08x} vs 0x{int(b[i]):08x})"
+        o = 0
+        for j, (c, _) in enumerate(units or ()):
+            if i < o + 2 * c:
+                half = "mean" if i < o + c else "invstd / variance"
+                msg += f": BN launch {j} (c = {c}), {half}, channel {(i - o) % c}"
+                break
+            o += 2 * c
+    return msg
+
+
 # ---------------------------------------------------------------- a. kernels
 SEGS = [(16, 2), (48, 16), (192, 1420864), (448, 2), (192, 16), (448, 1420864), (16, 1420864)]   # (c, rows)
 CANARY = np.float32(-7777.25)
@@ -162,27 +185,36 @@ def test_sidecar_is_the_restatement_and_leaves_the_step_alone(cfg):
     for c, _ in on["units"]:
         want[o + c:o + 2 * c] = 1.0
         o += 2 * c
-    assert _same(off["moving"][-1], want) and off["updates"] == 0        # never touched without the feature
+    # never touched without the feature
+    assert _same(off["moving"][-1], want), _diff("moving without the side-car vs mean 0 / variance 1", cfg, 2,
+                                                 off["moving"][-1], want, on["units"])
+    assert off["updates"] == 0
     for k in range(3):
         st, o = on["stats"][k], 0
         for c, rows in on["units"]:
             want[o:o + c], want[o + c:o + 2 * c] = update_ref(want[o:o + c], want[o + c:o + 2 * c], st[o:o + c],
                                                               st[o + c:o + 2 * c], rows, 0.99)
             o += 2 * c
-        assert _same(on["moving"][k], want), (cfg, k)
+        assert _same(on["moving"][k], want), _diff("moving, side-car vs restatement", cfg, k, on["moving"][k], want,
+                                                   on["units"])
     assert on["updates"] == 3
-    assert _same(on["params"], off["params"]) and on["loss"] == off["loss"]
-    assert all(_same(a, b) for a, b in zip(on["stats"], off["stats"]))
+    assert _same(on["params"], off["params"]), _diff("params, side-car on vs off", cfg, 2, on["params"], off["params"])
+    assert on["loss"] == off["loss"], (cfg, "loss per step, side-car on vs off", on["loss"], off["loss"])
+    for k, (a, b) in enumerate(zip(on["stats"], off["stats"])):
+        assert _same(a, b), _diff("stats, side-car on vs off", cfg, k, a, b, on["units"])
 
 
 @pytest.mark.parametrize("cfg", ["x6h", "bf16"])
 def test_sidecar_one_lane_and_replayed_graph_are_bitwise(cfg):
     on = _sidecar(cfg)
-    for other in (_run_steps(cfg, lanes=1), _run_steps(cfg, graph=True)):
-        assert other["loss"] == on["loss"] and _same(other["params"], on["params"])
+    for name, other in (("one lane", _run_steps(cfg, lanes=1)), ("replayed graph", _run_steps(cfg, graph=True))):
+        assert other["loss"] == on["loss"], (cfg, f"loss per step, {name} vs two lanes", other["loss"], on["loss"])
+        assert _same(other["params"], on["params"]), _diff(f"params, {name} vs two lanes", cfg, 2, other["params"],
+                                                           on["params"])
         assert other["updates"] == 3
         for k in range(3):
-            assert _same(other["moving"][k], on["moving"][k]), (cfg, k)
+            assert _same(other["moving"][k], on["moving"][k]), _diff(f"moving, {name} vs two lanes", cfg, k,
+                                                                     other["moving"][k], on["moving"][k], on["units"])
 
 
 # ------------------------------------------------------- c. trajectory vs fp64
