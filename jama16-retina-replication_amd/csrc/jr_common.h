@@ -66,6 +66,20 @@ __device__ __forceinline__ uint16_t f2bf(float f) {
   return *reinterpret_cast<uint16_t*>(&h);
 }
 
+// Sum of a block's 256 doubles in a fixed tree (the same pairs in every run);
+// red: 256 doubles of LDS.  Every thread returns the sum.
+__device__ __forceinline__ double block_sum256(double s, double* red) {
+  const int t = threadIdx.x;
+  red[t] = s;
+  __syncthreads();
+#pragma unroll
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) red[t] += red[t + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
 // BatchNormalization(scale=False) pre-activation, in one fixed rounding
 // order: every kernel that applies or differentiates it (jr_bn.hip, the
 // fused BN + max-pool of jr_pool.hip) sees bit-identical values and ReLU masks.

@@ -88,15 +88,10 @@ __global__ void __launch_bounds__(256) k_head_loss(int mode, const float* __rest
       s += (double)l;
     }
   }
-  red[t] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
+  const double sum = block_sum256(s, red);
   if (t == 0) {
     const double denom = mode == JR_HEAD_SIGMOID ? (double)n * units : (double)n;
-    loss[0] = (float)(red[0] / denom);
+    loss[0] = (float)(sum / denom);
   }
 }
 

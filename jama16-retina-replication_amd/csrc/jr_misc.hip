@@ -1,86 +1,15 @@
-// jr_misc.hip — optimizers, dtype casts, input scaling, Brier accumulator.
+// jr_misc.hip — dtype casts, input scaling, operand splits, Brier accumulator.
 //
-// Optimizers replace the TF ApplyMomentum / ApplyGradientDescent ops that
-// .minimize adds at train.py:147-153.  One launch updates
-// the whole flat parameter buffer (21,770,401 fp32 values); each lane moves
-// 16-byte vectors and the arithmetic is the unfused TF expression order.
-// NOTE: hipcc contracts a*b+c into an FMA by default (-ffp-contract=fast),
-// and without OCML_BASIC_ROUNDED_OPERATIONS __fmul_rn / __fadd_rn are the
-// plain operators, so this file is compiled with -ffp-contract=off
-// (Makefile): every multiply and add rounds on its own,
-// the IEEE fp32 evaluation of TF's (Eigen, non-fused) expressions:
-//   ApplyMomentum(use_nesterov): accum = accum*m + g; var -= g*lr + accum*m*lr
-//   ApplyMomentum:               accum = accum*m + g; var -= accum*lr
-//   ApplyGradientDescent:        var -= g*lr
+// NOTE: hipcc contracts a*b+c into an FMA by default (-ffp-contract=fast);
+// this file is compiled with -ffp-contract=off (Makefile): k_brier's fp64
+// s += d * d rounds the square and the sum each on its own.
 #include "jr_common.h"
-#include "jr_opt_expr.h"   // nest1, sqrt_cr (shared with jr_opt.hip)
 
 namespace jr {
 
 static int grid_for(int64_t items) {
   const int64_t b = ceil_div(items, 256);
   return (int)std::min<int64_t>(std::max<int64_t>(b, 1), 256 * 32);
-}
-
-__global__ void __launch_bounds__(256) k_nesterov(float* __restrict__ w, const float* __restrict__ grad,
-                                                  float* __restrict__ accum, int64_t n, float lr, float m,
-                                                  float gs) {
-  const int64_t n4 = n >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    float4 wv = reinterpret_cast<float4*>(w)[i];
-    float4 av = reinterpret_cast<float4*>(accum)[i];
-    const float4 gv = reinterpret_cast<const float4*>(grad)[i];
-    nest1(wv.x, __fmul_rn(gv.x, gs), av.x, lr, m);
-    nest1(wv.y, __fmul_rn(gv.y, gs), av.y, lr, m);
-    nest1(wv.z, __fmul_rn(gv.z, gs), av.z, lr, m);
-    nest1(wv.w, __fmul_rn(gv.w, gs), av.w, lr, m);
-    reinterpret_cast<float4*>(w)[i] = wv;
-    reinterpret_cast<float4*>(accum)[i] = av;
-  }
-  // tail
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < (n & 3)) {
-    const int64_t i = n4 * 4 + t;
-    nest1(w[i], __fmul_rn(grad[i], gs), accum[i], lr, m);
-  }
-}
-
-__global__ void __launch_bounds__(256) k_momentum(float* __restrict__ w, const float* __restrict__ grad,
-                                                  float* __restrict__ accum, int64_t n, float lr, float m,
-                                                  float gs) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float g = __fmul_rn(grad[i], gs);
-    const float a = __fadd_rn(__fmul_rn(accum[i], m), g);
-    accum[i] = a;
-    w[i] = __fsub_rn(w[i], __fmul_rn(a, lr));
-  }
-}
-
-__global__ void __launch_bounds__(256) k_sgd(float* __restrict__ w, const float* __restrict__ grad, int64_t n,
-                                             float lr, float gs) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    w[i] = __fsub_rn(w[i], __fmul_rn(__fmul_rn(grad[i], gs), lr));
-}
-
-// TF ApplyAdam (training_ops.cc ApplyAdamNonCuda, Eigen, no contraction):
-//   m += (g - m) * (1 - beta1);  v += (g*g - v) * (1 - beta2);
-//   var -= (m * alpha) / (sqrt(v) + epsilon),
-//   alpha = lr * sqrt(1 - beta2^t) / (1 - beta1^t) (lr_t, computed on the host);
-// every operation a correctly rounded _rn intrinsic in that order, so the
-// update is bitwise the IEEE fp32 evaluation of TF's expression.
-__global__ void __launch_bounds__(256) k_adam(float* __restrict__ w, const float* __restrict__ grad,
-                                              float* __restrict__ mm, float* __restrict__ vv, int64_t n,
-                                              float lr_t, float b1, float b2, float eps, float gs) {
-  const float one_b1 = __fsub_rn(1.f, b1), one_b2 = __fsub_rn(1.f, b2);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float g = __fmul_rn(grad[i], gs);
-    const float m0 = mm[i], v0 = vv[i];
-    const float m1 = __fadd_rn(m0, __fmul_rn(__fsub_rn(g, m0), one_b1));
-    const float v1 = __fadd_rn(v0, __fmul_rn(__fsub_rn(__fmul_rn(g, g), v0), one_b2));
-    mm[i] = m1;
-    vv[i] = v1;
-    w[i] = __fsub_rn(w[i], __fdiv_rn(__fmul_rn(m1, lr_t), __fadd_rn(sqrt_cr(v1), eps)));
-  }
 }
 
 __global__ void k_f32_to_bf16(const float* __restrict__ s, uint16_t* d, int64_t n) {
@@ -120,14 +49,9 @@ __global__ void k_brier(const float* __restrict__ p, const float* __restrict__ y
     const double d = (double)p[i] - (double)y[i];
     s += d * d;
   }
-  red[t] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
+  const double sum = block_sum256(s, red);
   if (t == 0) {
-    acc[0] += red[0];
+    acc[0] += sum;
     acc[1] += (double)n;
   }
 }
@@ -135,42 +59,6 @@ __global__ void k_brier(const float* __restrict__ p, const float* __restrict__ y
 }  // namespace jr
 
 using namespace jr;
-
-JR_API int jr_nesterov_update(float* w, const float* grad, float* accum, int64_t n, float lr, float momentum,
-                              float grad_scale, void* stream) {
-  if (!w || !grad || !accum || n < 0) return fail(JR_ERR_INVALID, "nesterov: bad arguments");
-  if (((uintptr_t)w | (uintptr_t)grad | (uintptr_t)accum) & 15)
-    return fail(JR_ERR_INVALID, "nesterov: buffers must be 16-byte aligned");
-  if (n == 0) return JR_OK;
-  hipLaunchKernelGGL(k_nesterov, dim3(grid_for(std::max<int64_t>(n / 4, 4))), dim3(256), 0, as_stream(stream), w,
-                     grad, accum, n, lr, momentum, grad_scale);
-  return check_launch("nesterov");
-}
-
-JR_API int jr_momentum_update(float* w, const float* grad, float* accum, int64_t n, float lr, float momentum,
-                              float grad_scale, void* stream) {
-  if (!w || !grad || !accum || n < 0) return fail(JR_ERR_INVALID, "momentum: bad arguments");
-  if (n == 0) return JR_OK;
-  hipLaunchKernelGGL(k_momentum, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), w, grad, accum, n, lr,
-                     momentum, grad_scale);
-  return check_launch("momentum");
-}
-
-JR_API int jr_sgd_update(float* w, const float* grad, int64_t n, float lr, float grad_scale, void* stream) {
-  if (!w || !grad || n < 0) return fail(JR_ERR_INVALID, "sgd: bad arguments");
-  if (n == 0) return JR_OK;
-  hipLaunchKernelGGL(k_sgd, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), w, grad, n, lr, grad_scale);
-  return check_launch("sgd");
-}
-
-JR_API int jr_adam_update(float* w, const float* grad, float* m, float* v, int64_t n, float lr_t, float beta1,
-                          float beta2, float eps, float grad_scale, void* stream) {
-  if (!w || !grad || !m || !v || n < 0) return fail(JR_ERR_INVALID, "adam: bad arguments");
-  if (n == 0) return JR_OK;
-  hipLaunchKernelGGL(k_adam, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), w, grad, m, v, n, lr_t, beta1,
-                     beta2, eps, grad_scale);
-  return check_launch("adam");
-}
 
 // ---------------------------------------------------------------- bf16 filters
 // One block = one 32 (c_in) x 32 (c_out) tile of one tap of one layer:

@@ -1,18 +1,25 @@
-// jr_opt.hip — the optimizer recipe with its step scalars in device memory:
-// the global gradient norm, the clip factor and the non-finite guard, and the
-// four updates reading (lr, weight_decay) and (scale, skipped) from there, so a
-// captured step replays under a changing learning rate (contracts: jr.h).
+// jr_opt.hip — the optimizers: one update body behind the by-value calls
+// (lr and grad_scale as launch arguments) and the device-scalar recipe (the
+// global gradient norm, the clip factor and the non-finite guard, and the four
+// updates reading (lr, weight_decay) and (scale, skipped) from device memory,
+// so a captured step replays under a changing learning rate; contracts: jr.h).
 //
-// Compiled with -ffp-contract=off like jr_misc.hip (Makefile): every fp32
-// operation below is one correctly rounded op in the written order, which
-// tests/opt_ref.py restates in numpy float32 bit for bit.
+// The updates replace the TF ApplyMomentum / ApplyGradientDescent / ApplyAdam
+// ops that .minimize adds at train.py:147-153.  One launch
+// updates the whole flat parameter buffer (21,770,401 fp32 values); each lane
+// moves 16-byte vectors and the arithmetic is the unfused TF expression order.
+// NOTE: hipcc contracts a*b+c into an FMA by default (-ffp-contract=fast),
+// and without OCML_BASIC_ROUNDED_OPERATIONS __fmul_rn / __fadd_rn are the
+// plain operators, so this file is compiled with -ffp-contract=off
+// (Makefile): every fp32 operation below is one correctly rounded op in the
+// written order, the IEEE fp32 evaluation of TF's (Eigen, non-fused)
+// expressions, which tests/opt_ref.py restates in numpy float32 bit for bit.
 #include "jr_common.h"
-#include "jr_opt_expr.h"
 
 namespace jr {
 
 constexpr int kNormBlocks = 1024;   // the norm's fixed grid: at most this many blocks of 256
-constexpr int kTileQuads = 256;     // an update block's unit of work: one quad per thread, as jr_nesterov_update
+constexpr int kTile = 256;          // an update block's unit of work: one vector (a quad or an element) per thread
 
 static int norm_blocks(int64_t n) {
   return (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n >> 2, 256), 1), kNormBlocks);
@@ -23,19 +30,6 @@ __global__ void k_set_hyper(jr_opt_hyper* h, float lr, float wd, float clip, flo
   h->weight_decay = wd;
   h->clip_norm = clip;
   h->grad_scale = gs;
-}
-
-// Sum of 256 doubles in a fixed tree (the same pairs in every run).
-__device__ __forceinline__ double block_sum256(double s, double* red) {
-  const int t = threadIdx.x;
-  red[t] = s;
-  __syncthreads();
-#pragma unroll
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  return red[0];
 }
 
 // Each thread adds the squares of its quads in stride order (x, y, z, w of a
@@ -107,10 +101,30 @@ __device__ __forceinline__ unsigned decay_mask4(const jr_opt_range* __restrict__
   return m;
 }
 
+// Correctly rounded sqrt (IEEE, as Eigen's sqrt on the CPU): v_sqrt_f32 is
+// within 1 ulp, so check its neighbours with exact fma residuals and step
+// once (denormal inputs are scaled by 2^32 first).
+__device__ __forceinline__ float sqrt_cr(float x) {
+  const bool tiny = x < 0x1.0p-96f;
+  const float xs = tiny ? x * 0x1.0p+32f : x;
+  float s = __builtin_amdgcn_sqrtf(xs);
+  const float dn = __uint_as_float(__float_as_uint(s) - 1), up = __uint_as_float(__float_as_uint(s) + 1);
+  if (__builtin_fmaf(-dn, s, xs) <= 0.f) s = dn;
+  else if (__builtin_fmaf(-up, s, xs) > 0.f) s = up;
+  s = tiny ? s * 0x1.0p-16f : s;
+  return (xs == 0.f || !(xs < __builtin_inff())) ? __builtin_sqrtf(x) : s;
+}
+
 enum { kNesterov = 0, kMomentum = 1, kSgd = 2, kAdam = 3 };
 
-// One element: g' = g*scale (+ wd*w inside a decay range), then the
-// by-value kernel's expression of jr_misc.hip with lr from device memory.
+// One element: g' = g*scale (+ wd*w inside a decay range), then
+//   ApplyMomentum(use_nesterov): accum = accum*m + g'; var -= g'*lr + accum*m*lr
+//   ApplyMomentum:               accum = accum*m + g'; var -= accum*lr
+//   ApplyGradientDescent:        var -= g'*lr
+//   ApplyAdam (training_ops.cc ApplyAdamNonCuda):
+//     m += (g' - m) * (1 - beta1);  v += (g'*g' - v) * (1 - beta2);
+//     var -= (m * alpha) / (sqrt(v) + epsilon); lr is the step's alpha =
+//     rate * sqrt(1 - beta2^t) / (1 - beta1^t) (lr_t, computed on the host).
 // p0: momentum, or Adam's beta1 (p1: beta2, p2: epsilon).
 template <int OPT>
 __device__ __forceinline__ void update1(float& w, float g, float& a, float& v, bool decay, float scale, float wd,
@@ -118,7 +132,8 @@ __device__ __forceinline__ void update1(float& w, float g, float& a, float& v, b
   g = __fmul_rn(g, scale);
   if (decay) g = __fadd_rn(g, __fmul_rn(wd, w));
   if constexpr (OPT == kNesterov) {
-    nest1(w, g, a, lr, p0);
+    a = __fadd_rn(__fmul_rn(a, p0), g);
+    w = __fsub_rn(w, __fadd_rn(__fmul_rn(g, lr), __fmul_rn(__fmul_rn(a, p0), lr)));
   } else if constexpr (OPT == kMomentum) {
     a = __fadd_rn(__fmul_rn(a, p0), g);
     w = __fsub_rn(w, __fmul_rn(a, lr));
@@ -132,80 +147,159 @@ __device__ __forceinline__ void update1(float& w, float g, float& a, float& v, b
   }
 }
 
-// A block takes tiles of kTileQuads quads in grid-stride order, the loop of
-// the by-value kernels.  The range search runs once per tile on block-uniform
-// values and classes the tile: outside every range, inside one range, or
-// mixed -- only a mixed tile's quads walk the table themselves.  Every quad
-// moves as 16 bytes; the decay only picks the arithmetic per element.
-template <int OPT>
-__global__ void __launch_bounds__(256) k_update_ex(float* __restrict__ w, const float* __restrict__ grad,
-                                                   float* __restrict__ s1, float* __restrict__ s2, int64_t n, float p0,
-                                                   float p1, float p2, const jr_opt_range* __restrict__ R, int nr,
-                                                   const jr_opt_hyper* __restrict__ hyper,
-                                                   const jr_opt_step* __restrict__ step) {
-  if (step->skipped) return;   // a non-finite norm: nothing is written
-  const float scale = step->scale, lr = hyper->lr, wd = hyper->weight_decay;
-  if (wd == 0.f) nr = 0;
+// Where an update takes its step scalars from.  ByValue: launch arguments;
+// weight decay 0, no range table, never skipped -- all three known when the
+// body is compiled.  FromDevice: jr_opt_hyper / jr_opt_step, read at the start
+// of every block, and weight decay inside the ranges of the table.
+struct ByValue {
+  float lr, scale;
+};
+struct FromDevice {
+  const jr_opt_range* R;
+  int nr;
+  const jr_opt_hyper* hyper;
+  const jr_opt_step* step;
+};
+
+template <int W>
+struct alignas(4 * W) Vec {
+  float e[W];
+};
+
+// Every update kernel.  A block takes tiles of kTile vectors of W elements in
+// grid-stride order, thread i of tile t the vector t * kTile + i; W = 4 moves
+// every quad as 16 bytes and leaves the last n % 4 elements to block 0, W = 1
+// is for buffers that are not 16-byte aligned.  FromDevice: the range search
+// runs once per tile on block-uniform values and classes the tile: outside
+// every range, inside one range, or mixed -- only a mixed tile's quads walk
+// the table themselves; the decay only picks the arithmetic per element.
+template <int OPT, int W, class SRC>
+__device__ __forceinline__ void update_body(float* __restrict__ w, const float* __restrict__ grad,
+                                            float* __restrict__ s1, float* __restrict__ s2, int64_t n, float p0, float p1,
+                                            float p2, const SRC src) {
+  constexpr bool kDev = std::is_same<SRC, FromDevice>::value;
+  static_assert(W == 4 || (W == 1 && !kDev), "the decay classes are per quad");
   constexpr bool kS1 = OPT != kSgd, kS2 = OPT == kAdam;
   constexpr unsigned kMixed = 16u;
-  const int64_t n4 = n >> 2;
-  const int64_t tiles = (n4 + kTileQuads - 1) / kTileQuads;
-  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-    const int64_t i = t * kTileQuads + threadIdx.x;
-    float4 wv, gv, av, vv;
-    if (i < n4) {
-      wv = reinterpret_cast<const float4*>(w)[i];
-      gv = reinterpret_cast<const float4*>(grad)[i];
-      if constexpr (kS1) av = reinterpret_cast<const float4*>(s1)[i];
-      if constexpr (kS2) vv = reinterpret_cast<const float4*>(s2)[i];
-    }
-    unsigned cls = 0u;   // block-uniform: 0, 15 (every element decays) or kMixed
-    int r0 = 0;
-    if (nr) {
-      const int64_t e0 = t * kTileQuads * 4, e1 = e0 + kTileQuads * 4;
-      r0 = range_after(R, nr, e0);
-      if (r0 < nr && R[r0].begin < e1) cls = (R[r0].begin <= e0 && R[r0].end >= e1) ? 15u : kMixed;
-    }
-    if (i < n4) {
-      const unsigned d = cls == kMixed ? decay_mask4(R, nr, r0, i * 4) : cls;
-      float za = 0.f, zv = 0.f;   // unused state of the optimizer
-      update1<OPT>(wv.x, gv.x, kS1 ? av.x : za, kS2 ? vv.x : zv, d & 1u, scale, wd, lr, p0, p1, p2);
-      update1<OPT>(wv.y, gv.y, kS1 ? av.y : za, kS2 ? vv.y : zv, d & 2u, scale, wd, lr, p0, p1, p2);
-      update1<OPT>(wv.z, gv.z, kS1 ? av.z : za, kS2 ? vv.z : zv, d & 4u, scale, wd, lr, p0, p1, p2);
-      update1<OPT>(wv.w, gv.w, kS1 ? av.w : za, kS2 ? vv.w : zv, d & 8u, scale, wd, lr, p0, p1, p2);
-      reinterpret_cast<float4*>(w)[i] = wv;
-      if constexpr (kS1) reinterpret_cast<float4*>(s1)[i] = av;
-      if constexpr (kS2) reinterpret_cast<float4*>(s2)[i] = vv;
-    }
+  using V = Vec<W>;
+  float scale, lr, wd = 0.f, za = 0.f, zv = 0.f;   // za, zv: the state an optimizer does not have
+  int nr = 0;
+  if constexpr (kDev) {
+    if (src.step->skipped) return;   // a non-finite norm: nothing is written
+    scale = src.step->scale, lr = src.hyper->lr, wd = src.hyper->weight_decay;
+    nr = wd == 0.f ? 0 : src.nr;
+  } else {
+    scale = src.scale, lr = src.lr;
   }
-  // tail: the last n % 4 elements, one thread each
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const int64_t e = n4 * 4 + threadIdx.x;
-    bool d = false;
-    if (nr) {
-      const int r = range_after(R, nr, e);
-      d = r < nr && R[r].begin <= e;
+  const int64_t nv = W == 4 ? n >> 2 : n;
+  int64_t t = blockIdx.x;   // the tile of i: block-uniform
+  for (int64_t i = t * kTile + threadIdx.x; i < nv; i += (int64_t)gridDim.x * kTile, t += gridDim.x) {
+    V wv = reinterpret_cast<const V*>(w)[i], av, vv;
+    const V gv = reinterpret_cast<const V*>(grad)[i];
+    if constexpr (kS1) av = reinterpret_cast<const V*>(s1)[i];
+    if constexpr (kS2) vv = reinterpret_cast<const V*>(s2)[i];
+    unsigned d = 0u;   // bit j: element j of the vector decays
+    if constexpr (kDev) {
+      if (nr) {
+        const int64_t e0 = t * kTile * 4, e1 = e0 + kTile * 4;
+        const int r0 = range_after(src.R, nr, e0);
+        unsigned cls = 0u;   // block-uniform: 0, 15 (every element decays) or kMixed
+        if (r0 < nr && src.R[r0].begin < e1) cls = (src.R[r0].begin <= e0 && src.R[r0].end >= e1) ? 15u : kMixed;
+        d = cls == kMixed ? decay_mask4(src.R, nr, r0, i * 4) : cls;
+      }
     }
-    float za = 0.f, zv = 0.f;
+#pragma unroll
+    for (int j = 0; j < W; ++j)
+      update1<OPT>(wv.e[j], gv.e[j], kS1 ? av.e[j] : za, kS2 ? vv.e[j] : zv, d >> j & 1u, scale, wd, lr, p0, p1, p2);
+    reinterpret_cast<V*>(w)[i] = wv;
+    if constexpr (kS1) reinterpret_cast<V*>(s1)[i] = av;
+    if constexpr (kS2) reinterpret_cast<V*>(s2)[i] = vv;
+  }
+  // tail: the last n % W elements, one thread each
+  if (blockIdx.x == 0 && threadIdx.x < (n & (W - 1))) {
+    const int64_t e = nv * W + threadIdx.x;
+    bool d = false;
+    if constexpr (kDev) {
+      if (nr) {
+        const int r = range_after(src.R, nr, e);
+        d = r < nr && src.R[r].begin <= e;
+      }
+    }
     update1<OPT>(w[e], grad[e], kS1 ? s1[e] : za, kS2 ? s2[e] : zv, d, scale, wd, lr, p0, p1, p2);
   }
 }
 
+__host__ __device__ static inline bool aligned16(const void* a, const void* b, const void* c = nullptr,
+                                                 const void* d = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
+
+// The by-value updates that take any 4-byte alignment: quads when every buffer is
+// 16-byte aligned (the host sizes the grid by the same test), else single elements.
 template <int OPT>
-static int launch_update_ex(const char* what, float* w, const float* grad, float* s1, float* s2, int64_t n, float p0,
-                            float p1, float p2, const jr_opt_range* ranges, int32_t nranges,
+__device__ __forceinline__ void update_by_alignment(float* __restrict__ w, const float* __restrict__ grad,
+                                                    float* __restrict__ s1, float* __restrict__ s2, int64_t n, float p0,
+                                                    float p1, float p2, const ByValue src) {
+  if (aligned16(w, grad, s1, s2))
+    update_body<OPT, 4>(w, grad, s1, s2, n, p0, p1, p2, src);
+  else
+    update_body<OPT, 1>(w, grad, s1, s2, n, p0, p1, p2, src);
+}
+
+// The kernels keep one name per optimizer and scalar source: traces and the
+// tools that read them find the step's end by it.
+__global__ void __launch_bounds__(256) k_nesterov(float* __restrict__ w, const float* __restrict__ grad,
+                                                  float* __restrict__ accum, int64_t n, float lr, float m, float gs) {
+  update_body<kNesterov, 4>(w, grad, accum, nullptr, n, m, 0.f, 0.f, ByValue{lr, gs});
+}
+
+__global__ void __launch_bounds__(256) k_momentum(float* __restrict__ w, const float* __restrict__ grad,
+                                                  float* __restrict__ accum, int64_t n, float lr, float m, float gs) {
+  update_by_alignment<kMomentum>(w, grad, accum, nullptr, n, m, 0.f, 0.f, ByValue{lr, gs});
+}
+
+__global__ void __launch_bounds__(256) k_sgd(float* __restrict__ w, const float* __restrict__ grad, int64_t n,
+                                             float lr, float gs) {
+  update_by_alignment<kSgd>(w, grad, nullptr, nullptr, n, 0.f, 0.f, 0.f, ByValue{lr, gs});
+}
+
+__global__ void __launch_bounds__(256) k_adam(float* __restrict__ w, const float* __restrict__ grad,
+                                              float* __restrict__ mm, float* __restrict__ vv, int64_t n, float lr_t,
+                                              float b1, float b2, float eps, float gs) {
+  update_by_alignment<kAdam>(w, grad, mm, vv, n, b1, b2, eps, ByValue{lr_t, gs});
+}
+
+#define JR_UPDATE_EX_KERNEL(NAME, OPT)                                                                               \
+  __global__ void __launch_bounds__(256) NAME(                                                                       \
+      float* __restrict__ w, const float* __restrict__ grad, float* __restrict__ s1, float* __restrict__ s2, int64_t n, \
+      float p0, float p1, float p2, const jr_opt_range* __restrict__ R, int nr, const jr_opt_hyper* __restrict__ hyper, \
+      const jr_opt_step* __restrict__ step) {                                                                        \
+    update_body<OPT, 4>(w, grad, s1, s2, n, p0, p1, p2, FromDevice{R, nr, hyper, step});                             \
+  }
+JR_UPDATE_EX_KERNEL(k_nesterov_ex, kNesterov)
+JR_UPDATE_EX_KERNEL(k_momentum_ex, kMomentum)
+JR_UPDATE_EX_KERNEL(k_sgd_ex, kSgd)
+JR_UPDATE_EX_KERNEL(k_adam_ex, kAdam)
+#undef JR_UPDATE_EX_KERNEL
+
+static dim3 update_grid(int64_t vectors) {
+  return dim3((unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div(vectors, kTile), 1), 256 * 32));
+}
+
+static int launch_update_ex(const char* what, int opt, float* w, const float* grad, float* s1, float* s2, int64_t n,
+                            float p0, float p1, float p2, const jr_opt_range* ranges, int32_t nranges,
                             const jr_opt_hyper* hyper, const jr_opt_step* step, void* stream) {
-  const bool state_ok = (OPT == kSgd || s1) && (OPT != kAdam || s2);
+  static constexpr decltype(&k_nesterov_ex) kernels[] = {k_nesterov_ex, k_momentum_ex, k_sgd_ex, k_adam_ex};
+  const bool state_ok = (opt == kSgd || s1) && (opt != kAdam || s2);
   if (!w || !grad || !state_ok || !hyper || !step || n < 0 || nranges < 0 || (nranges > 0 && !ranges))
     return fail(JR_ERR_INVALID, std::string(what) + ": bad arguments");
-  if (((uintptr_t)w | (uintptr_t)grad | (uintptr_t)s1 | (uintptr_t)s2) & 15)
+  if (!aligned16(w, grad, s1, s2))
     return fail(JR_ERR_INVALID, std::string(what) + ": buffers must be 16-byte aligned");
   if (((uintptr_t)ranges & 7) || ((uintptr_t)hyper & 3) || ((uintptr_t)step & 3))
     return fail(JR_ERR_INVALID, std::string(what) + ": misaligned range table, hyper or step struct");
   if (n == 0) return JR_OK;
-  const int64_t tiles = std::max<int64_t>(ceil_div(n >> 2, kTileQuads), 1);
-  hipLaunchKernelGGL(k_update_ex<OPT>, dim3((unsigned)std::min<int64_t>(tiles, 256 * 32)), dim3(256), 0,
-                     as_stream(stream), w, grad, s1, s2, n, p0, p1, p2, ranges, (int)nranges, hyper, step);
+  hipLaunchKernelGGL(kernels[opt], update_grid(n >> 2), dim3(256), 0, as_stream(stream), w, grad, s1, s2, n, p0, p1,
+                     p2, ranges, (int)nranges, hyper, step);
   return check_launch(what);
 }
 
@@ -244,28 +338,64 @@ JR_API int jr_opt_prepare(const void* partials, int64_t n, const jr_opt_hyper* h
   return check_launch("opt_prepare");
 }
 
+JR_API int jr_nesterov_update(float* w, const float* grad, float* accum, int64_t n, float lr, float momentum,
+                              float grad_scale, void* stream) {
+  if (!w || !grad || !accum || n < 0) return fail(JR_ERR_INVALID, "nesterov: bad arguments");
+  if (!aligned16(w, grad, accum)) return fail(JR_ERR_INVALID, "nesterov: buffers must be 16-byte aligned");
+  if (n == 0) return JR_OK;
+  hipLaunchKernelGGL(k_nesterov, update_grid(n >> 2), dim3(256), 0, as_stream(stream), w, grad, accum, n, lr,
+                     momentum, grad_scale);
+  return check_launch("nesterov");
+}
+
+JR_API int jr_momentum_update(float* w, const float* grad, float* accum, int64_t n, float lr, float momentum,
+                              float grad_scale, void* stream) {
+  if (!w || !grad || !accum || n < 0) return fail(JR_ERR_INVALID, "momentum: bad arguments");
+  if (n == 0) return JR_OK;
+  hipLaunchKernelGGL(k_momentum, update_grid(aligned16(w, grad, accum) ? n >> 2 : n), dim3(256), 0, as_stream(stream),
+                     w, grad, accum, n, lr, momentum, grad_scale);
+  return check_launch("momentum");
+}
+
+JR_API int jr_sgd_update(float* w, const float* grad, int64_t n, float lr, float grad_scale, void* stream) {
+  if (!w || !grad || n < 0) return fail(JR_ERR_INVALID, "sgd: bad arguments");
+  if (n == 0) return JR_OK;
+  hipLaunchKernelGGL(k_sgd, update_grid(aligned16(w, grad) ? n >> 2 : n), dim3(256), 0, as_stream(stream), w, grad, n,
+                     lr, grad_scale);
+  return check_launch("sgd");
+}
+
+JR_API int jr_adam_update(float* w, const float* grad, float* m, float* v, int64_t n, float lr_t, float beta1,
+                          float beta2, float eps, float grad_scale, void* stream) {
+  if (!w || !grad || !m || !v || n < 0) return fail(JR_ERR_INVALID, "adam: bad arguments");
+  if (n == 0) return JR_OK;
+  hipLaunchKernelGGL(k_adam, update_grid(aligned16(w, grad, m, v) ? n >> 2 : n), dim3(256), 0, as_stream(stream), w,
+                     grad, m, v, n, lr_t, beta1, beta2, eps, grad_scale);
+  return check_launch("adam");
+}
+
 JR_API int jr_nesterov_update_ex(float* w, const float* grad, float* accum, int64_t n, float momentum,
                                  const jr_opt_range* ranges, int32_t nranges, const jr_opt_hyper* hyper,
                                  const jr_opt_step* step, void* stream) {
-  return launch_update_ex<kNesterov>("nesterov_ex", w, grad, accum, nullptr, n, momentum, 0.f, 0.f, ranges, nranges,
-                                     hyper, step, stream);
+  return launch_update_ex("nesterov_ex", kNesterov, w, grad, accum, nullptr, n, momentum, 0.f, 0.f, ranges, nranges,
+                          hyper, step, stream);
 }
 
 JR_API int jr_momentum_update_ex(float* w, const float* grad, float* accum, int64_t n, float momentum,
                                  const jr_opt_range* ranges, int32_t nranges, const jr_opt_hyper* hyper,
                                  const jr_opt_step* step, void* stream) {
-  return launch_update_ex<kMomentum>("momentum_ex", w, grad, accum, nullptr, n, momentum, 0.f, 0.f, ranges, nranges,
-                                     hyper, step, stream);
+  return launch_update_ex("momentum_ex", kMomentum, w, grad, accum, nullptr, n, momentum, 0.f, 0.f, ranges, nranges,
+                          hyper, step, stream);
 }
 
 JR_API int jr_sgd_update_ex(float* w, const float* grad, int64_t n, const jr_opt_range* ranges, int32_t nranges,
                             const jr_opt_hyper* hyper, const jr_opt_step* step, void* stream) {
-  return launch_update_ex<kSgd>("sgd_ex", w, grad, nullptr, nullptr, n, 0.f, 0.f, 0.f, ranges, nranges, hyper, step,
-                                stream);
+  return launch_update_ex("sgd_ex", kSgd, w, grad, nullptr, nullptr, n, 0.f, 0.f, 0.f, ranges, nranges, hyper, step,
+                          stream);
 }
 
 JR_API int jr_adam_update_ex(float* w, const float* grad, float* m, float* v, int64_t n, float beta1, float beta2,
                              float eps, const jr_opt_range* ranges, int32_t nranges, const jr_opt_hyper* hyper,
                              const jr_opt_step* step, void* stream) {
-  return launch_update_ex<kAdam>("adam_ex", w, grad, m, v, n, beta1, beta2, eps, ranges, nranges, hyper, step, stream);
+  return launch_update_ex("adam_ex", kAdam, w, grad, m, v, n, beta1, beta2, eps, ranges, nranges, hyper, step, stream);
 }

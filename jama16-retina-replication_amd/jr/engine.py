@@ -1473,9 +1473,29 @@ class Engine(Replica):
         return self.dinput[:B * ib.h * ib.w * 4].view(B, ib.h, ib.w, 4)[..., :ib.c].cpu().numpy()
 
     # ---- optimizer
+    def _opt_desc(self) -> tuple:
+        """self.optimizer's update: (by-value function, _ex function, state
+        buffers, hyper-parameters passed by value, written resources, nbytes).
+        Both functions take (params, grads, *state, n, ...; stream last): by value
+        (lr, *hyper, grad_scale), _ex (*hyper, ranges, nranges, hyper and step struct)."""
+        L, acc, pa = self.lib, self.accum.data_ptr(), [("p",), ("acc",)]
+        if self.optimizer == "nesterov":
+            return L.jr_nesterov_update, L.jr_nesterov_update_ex, (acc,), (self.momentum,), pa, 20 * self.nparam
+        if self.optimizer == "momentum":
+            return L.jr_momentum_update, L.jr_momentum_update_ex, (acc,), (self.momentum,), pa, 0
+        if self.optimizer == "sgd":
+            return L.jr_sgd_update, L.jr_sgd_update_ex, (), (), [("p",)], 0
+        return (L.jr_adam_update, L.jr_adam_update_ex, (acc, self.adam_v.data_ptr()),
+                (self.adam_b1, self.adam_b2, self.adam_eps), pa, 0)
+
+    def _by_value_args(self, lr: float, grad_scale: float) -> tuple:
+        """The by-value update's arguments (lr: Adam's alpha of the step)."""
+        _, _, state, hyper, _, _ = self._opt_desc()
+        return (self.params.data_ptr(), self.grads.data_ptr(), *state, self.nparam, lr, *hyper, grad_scale, self._s)
+
     def _opt_update(self, b: Build) -> None:
-        L, s0, n = self.lib, b.S[0], self.nparam
-        P, G, acc = self.params.data_ptr(), self.grads.data_ptr(), self.accum.data_ptr()
+        L, s0, n, G = self.lib, b.S[0], self.nparam, self.grads.data_ptr()
+        fn, fn_ex, state, hyper, writes, nbytes = self._opt_desc()
         greads = [("g", u.first.idx) for u in self.cunits] + [("g", "dense")]
         if self.opt_ex:
             # norm of the (reduced) raw gradient -> scale / skip of this step -> the
@@ -1485,28 +1505,10 @@ class Engine(Replica):
             b.add(b.opt, L.jr_grad_sqnorm, (G, n, part, ctypes.c_size_t(8 * self.opt_partials.numel()), s0),
                   "grad_sqnorm", 0, greads, [("gnorm",)], nbytes=4 * n)
             b.add(b.opt, L.jr_opt_prepare, (part, n, hy, st, s0), "opt_prepare", 0, [("gnorm",)], [("gnorm",)])
-            rd = greads + [("gnorm",)]
-            if self.optimizer in ("nesterov", "momentum"):
-                nesterov = self.optimizer == "nesterov"
-                b.add(b.opt, L.jr_nesterov_update_ex if nesterov else L.jr_momentum_update_ex,
-                      (P, G, acc, n, self.momentum, R, nr, hy, st, s0), self.optimizer + "_update_ex", 0, rd,
-                      [("p",), ("acc",)], nbytes=20 * n if nesterov else 0)
-            elif self.optimizer == "sgd":
-                b.add(b.opt, L.jr_sgd_update_ex, (P, G, n, R, nr, hy, st, s0), "sgd_update_ex", 0, rd, [("p",)])
-            else:   # adam: the step's alpha goes through jr_opt_set_hyper (apply_update)
-                b.add(b.opt, L.jr_adam_update_ex, (P, G, acc, self.adam_v.data_ptr(), n, self.adam_b1, self.adam_b2,
-                                                   self.adam_eps, R, nr, hy, st, s0), "adam_update_ex", 0, rd,
-                      [("p",), ("acc",)])
-        elif self.optimizer in ("nesterov", "momentum"):
-            nesterov = self.optimizer == "nesterov"
-            b.add(b.opt, L.jr_nesterov_update if nesterov else L.jr_momentum_update,
-                  (P, G, acc, n, self.lr, self.momentum, 1.0, s0), self.optimizer, 0, greads, [("p",), ("acc",)],
-                  nbytes=20 * n if nesterov else 0)
-        elif self.optimizer == "sgd":
-            b.add(b.opt, L.jr_sgd_update, (P, G, n, self.lr, 1.0, s0), "sgd", 0, greads, [("p",)])
-        else:   # adam: lr_t of the step is filled in by apply_update
-            b.add(b.opt, L.jr_adam_update, (P, G, acc, self.adam_v.data_ptr(), n, self.lr, self.adam_b1, self.adam_b2,
-                                            self.adam_eps, 1.0, s0), "adam", 0, greads, [("p",), ("acc",)])
+            b.add(b.opt, fn_ex, (self.params.data_ptr(), G, *state, n, *hyper, R, nr, hy, st, s0),
+                  self.optimizer + "_update_ex", 0, greads + [("gnorm",)], writes, nbytes=nbytes)
+        else:   # (adam: apply_update binds the step's alpha in place of self.lr)
+            b.add(b.opt, fn, self._by_value_args(self.lr, 1.0), self.optimizer, 0, greads, writes, nbytes=nbytes)
         if self.bn_momentum is not None:
             # the moving averages of this step's batch statistics (one launch; jr.h)
             b.add(b.opt, L.jr_bn_moving_update, self._bn_update_args(b.B, self.bn_momentum, s0), "bn_moving", 0,
@@ -1599,12 +1601,9 @@ class Engine(Replica):
             # write of weights and optimizer state is withheld -- jr.h)
             self._push_hyper(self._adam_alpha() if self.optimizer == "adam" else self.lr, grad_scale)
         elif grad_scale != 1.0 or self.optimizer == "adam":
-            c = opt[0]
-            args = list(c.args)
-            args[-2] = grad_scale
-            if self.optimizer == "adam":
-                args[5] = self._adam_alpha()     # (so Adam steps run eagerly: the scalar changes every step)
-            opt = [dataclasses.replace(c, args=tuple(args))] + list(opt[1:])
+            # (so Adam steps run eagerly: the scalar changes every step)
+            lr = self._adam_alpha() if self.optimizer == "adam" else self.lr
+            opt = [dataclasses.replace(opt[0], args=self._by_value_args(lr, grad_scale))] + list(opt[1:])
         self.lanes.run(opt)
         if self.bn_momentum is not None:
             self.updates += 1

@@ -125,7 +125,7 @@ def test_optimizers_bitwise_tf_order():
         assert np.array_equal(host(W), w), t
 
 
-@pytest.mark.parametrize("opt", ["adam", "momentum"])
+@pytest.mark.parametrize("opt", ["adam", "momentum", "sgd"])
 def test_engine_optimizer_step(opt):
     """Engine(optimizer=...) applies the restated update to its own gradient."""
     from jr.engine import Engine
@@ -144,6 +144,8 @@ def test_engine_optimizer_step(opt):
         eng.synchronize()
         if opt == "adam":
             w, m, v, _ = R.adam_f32(w, g, m, v, t, lr=1e-3)
-        else:
+        elif opt == "momentum":
             w, m = _f32(*R.momentum(w, g, m, np.float32(3e-3), np.float32(0.9)))
+        else:
+            w = w - g * np.float32(3e-3)
         assert np.array_equal(eng.params.cpu().numpy(), w), (opt, t)

@@ -7,6 +7,9 @@
   four steps, with decay ranges that split a quad, hold one element, leave an
   undecayed tail and cross tile boundaries; nothing written on a skipped step;
   with no decay, no clipping and grad_scale 1 bitwise the by-value kernels;
+* every by-value jr_*_update bitwise the same restatement with scale =
+  grad_scale, at sizes around a quad and a tile, and on buffers that are not
+  16-byte aligned where the call accepts them;
 * the Engine's device path: bitwise the default path when the recipe changes
   nothing, the restatement under clipping, weight decay, a grad_scale, a NaN
   gradient, bf16 storage, and replays of a captured step under a changing
@@ -243,6 +246,61 @@ def test_update_ex_equals_by_value_kernels(opt):
         assert np.array_equal(host(W), host(Wl)), (opt, t)
         for a, b in zip(S, Sl):
             assert np.array_equal(host(a), host(b)), (opt, t)
+
+
+# ---- the by-value calls: the same body with lr and grad_scale as arguments, no decay, never skipped
+def _by_value(L, opt, W, G, S, n, lr, grad_scale):
+    if opt in ("nesterov", "momentum"):
+        fn = L.jr_nesterov_update if opt == "nesterov" else L.jr_momentum_update
+        return fn(W.data_ptr(), G.data_ptr(), S[0].data_ptr(), n, lr, 0.9, grad_scale, None)
+    if opt == "sgd":
+        return L.jr_sgd_update(W.data_ptr(), G.data_ptr(), n, lr, grad_scale, None)
+    return L.jr_adam_update(W.data_ptr(), G.data_ptr(), S[0].data_ptr(), S[1].data_ptr(), n, lr, 0.9, 0.999, 1e-8,
+                            grad_scale, None)
+
+
+def _two_steps_by_value(opt, n, grad_scale, place):
+    """Two steps from non-zero state against opt_ref.update_ref (scale = grad_scale, weight decay 0);
+    place(array) -> the device tensor the call gets."""
+    ffi, L = _lib()
+    rng = np.random.default_rng(13)
+    w = rng.standard_normal(n).astype(np.float32)
+    state = tuple(rng.standard_normal(n).astype(np.float32) ** (2 if k else 1)       # Adam's v is a mean of squares
+                  for k in range(len(_state0(opt, n))))
+    W, S = place(w), [place(s) for s in state]
+    for t in (1, 2):
+        g = rng.standard_normal(n).astype(np.float32)
+        lr = float(opt_ref.adam_alpha(1e-3, t)) if opt == "adam" else 3e-3
+        G = place(g)
+        ffi.check(opt, _by_value(L, opt, W, G, S, n, lr, grad_scale))
+        w, state = opt_ref.update_ref(opt, w, g, state, grad_scale, lr, 0.0, None)
+        assert np.array_equal(host(W), w), (opt, n, t)
+        for k, s in enumerate(state):
+            assert np.array_equal(host(S[k]), s), (opt, n, t, k)
+        assert np.array_equal(host(G), g)
+
+
+# no quad, tail only, one quad, quad + tail, one tile of 256 quads - and + one element, several blocks with a tail
+@pytest.mark.parametrize("grad_scale", [1.0, 0.3])       # 0.3: the first multiply rounds
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1023, 1025, 3 * 4096 + 5])
+@pytest.mark.parametrize("opt", OPTS)
+def test_by_value_bitwise_restatement(opt, n, grad_scale):
+    _two_steps_by_value(opt, n, grad_scale, dev)
+
+
+@pytest.mark.parametrize("n", [5, 1025])
+@pytest.mark.parametrize("opt", ["momentum", "sgd", "adam"])
+def test_by_value_accepts_buffers_off_16_bytes(opt, n):
+    """Every buffer a [1:] view (4-byte, not 16-byte aligned): the same values, the element before each view untouched."""
+    bases = []
+
+    def place(a):
+        base = dev(np.concatenate([np.float32([-7.5]), a]))
+        bases.append(base)
+        assert base.data_ptr() % 16 == 0 and base[1:].data_ptr() % 16 == 4
+        return base[1:]
+    _two_steps_by_value(opt, n, 0.3, place)
+    assert bases and all(host(b)[0] == np.float32(-7.5) for b in bases)
 
 
 # ---- the Engine: 107^2, B = 2, conv_math="x8", nesterov

@@ -222,3 +222,24 @@ def test_new_entry_points_validate_without_gpu():
                  (P, P, P, P, 8, 0.9, 0.999, 1e-8, P, 1, None, P, None), (P, P, P, P, 8, 0.9, 0.999, 1e-8, P, 1, P, None, None)):
         assert L.jr_adam_update_ex(*args) == -1, args
     assert "adam_ex" in _ffi.last_error()
+
+
+def test_quad_only_updates_refuse_misaligned_buffers():
+    """jr_nesterov_update and the four _ex updates move quads only: a buffer at a
+    4-byte but not 16-byte aligned address is refused, and the message says why."""
+    from jr import _ffi
+    L = _ffi.load()
+    P = 4096
+    calls = {      # what -> (number of buffers, call on them)
+        "nesterov": (3, lambda w, g, a: L.jr_nesterov_update(w, g, a, 8, 0.1, 0.9, 1.0, None)),
+        "nesterov_ex": (3, lambda w, g, a: L.jr_nesterov_update_ex(w, g, a, 8, 0.9, P, 1, P, P, None)),
+        "momentum_ex": (3, lambda w, g, a: L.jr_momentum_update_ex(w, g, a, 8, 0.9, P, 1, P, P, None)),
+        "sgd_ex": (2, lambda w, g: L.jr_sgd_update_ex(w, g, 8, P, 1, P, P, None)),
+        "adam_ex": (4, lambda w, g, m, v: L.jr_adam_update_ex(w, g, m, v, 8, 0.9, 0.999, 1e-8, P, 1, P, P, None)),
+    }
+    for what, (nbuf, call) in calls.items():
+        for k in range(nbuf):
+            bufs = [P] * nbuf
+            bufs[k] = P + 4
+            assert call(*bufs) == -1, (what, k)
+            assert _ffi.last_error().startswith(what + ":") and "16-byte aligned" in _ffi.last_error(), (what, k)
