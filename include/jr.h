@@ -579,6 +579,48 @@ int jr_adam_update_ex(float* w, const float* grad, float* m, float* v, int64_t n
                       const jr_opt_range* ranges, int32_t nranges, const jr_opt_hyper* hyper, const jr_opt_step* step,
                       void* stream);
 
+/* ---- RMSProp (TF ApplyRMSProp, the CPU functor [TF-3P, from reading,
+ *      version unpinned]; not in the reference: the optimizer the published
+ *      Inception-v3 recipe was tuned for, decay 0.9, momentum 0.9, epsilon 1) --
+ * Per element, every fp32 operation one correctly rounded op in this order:
+ *   g   = grad * grad_scale            (_ex: grad * step->scale, then
+ *                                       g = g + weight_decay * w inside a range)
+ *   ms  = ms + (g*g - ms) * (1 - rho)
+ *   mom = mom*momentum + (g*lr) / sqrt(ms + eps)   (sqrt and / correctly rounded)
+ *   w   = w - mom
+ * TF starts ms at ones and mom at zeros; the library initialises neither.
+ * jr_rmsprop_update takes any 4-byte alignment (16-byte moves when all four
+ * buffers are 16-byte aligned); jr_rmsprop_update_ex follows every rule of
+ * the _ex calls above (lr = hyper->lr, the skip, the ranges, the alignment). */
+int jr_rmsprop_update(float* w, const float* grad, float* mom, float* ms, int64_t n, float lr, float rho,
+                      float momentum, float eps, float grad_scale, void* stream);
+int jr_rmsprop_update_ex(float* w, const float* grad, float* mom, float* ms, int64_t n, float rho, float momentum,
+                         float eps, const jr_opt_range* ranges, int32_t nranges, const jr_opt_hyper* hyper,
+                         const jr_opt_step* step, void* stream);
+
+/* ---- the moving average of the weights (TF ExponentialMovingAverage
+ *      [TF-3P, from reading, version unpinned]; not in the reference) -------
+ * The counter and the step's decay live in DEVICE memory, so a captured step
+ * replays correctly and a step the non-finite guard skipped is not counted.
+ * Per step, on one stream, after the optimizer's update:
+ *   jr_ema_prepare  ->  jr_ema_update
+ * step: the jr_opt_step of this step's jr_opt_prepare, or NULL (never skipped). */
+typedef struct jr_ema_state { float decay, one_minus_decay; uint32_t updates, warm; } jr_ema_state;
+/* One thread stores decay, one_minus_decay = 1 - decay, updates and warm
+ * (0 or 1) into *state (device memory, 4-byte aligned).  decay in [0, 1). */
+int jr_ema_set(jr_ema_state* state, float decay, uint32_t warm, uint32_t updates, void* stream);
+/* One thread.  step && step->skipped: one_minus_decay = 0, updates unchanged.
+ * Otherwise, each operation rounded once:
+ *   t = (float)updates
+ *   d = warm ? min(decay, (1 + t) / (10 + t)) : decay
+ *   one_minus_decay = 1 - d;  updates += 1 */
+int jr_ema_prepare(jr_ema_state* state, const jr_opt_step* step, void* stream);
+/* shadow = shadow - (shadow - w) * state->one_minus_decay, a subtract, a
+ * multiply, a subtract, per element; step && step->skipped: nothing is
+ * written.  shadow and w 16-byte aligned (else JR_ERR_INVALID, no launch). */
+int jr_ema_update(float* shadow, const float* w, int64_t n, const jr_ema_state* state, const jr_opt_step* step,
+                  void* stream);
+
 /* ---- bf16 filter copies (the bf16 conv path's weight operands) -------
  * From the fp32 master kernel [kh][kw][c_in][c_out] write
  *   w_hwio: bf16 [kh][kw][c_in][c_out]        (jr_conv2d_bwd_data, JR_BF16)

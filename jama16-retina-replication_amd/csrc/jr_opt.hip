@@ -1,11 +1,14 @@
 // jr_opt.hip — the optimizers: one update body behind the by-value calls
 // (lr and grad_scale as launch arguments) and the device-scalar recipe (the
-// global gradient norm, the clip factor and the non-finite guard, and the four
+// global gradient norm, the clip factor and the non-finite guard, and the five
 // updates reading (lr, weight_decay) and (scale, skipped) from device memory,
-// so a captured step replays under a changing learning rate; contracts: jr.h).
+// so a captured step replays under a changing learning rate; contracts: jr.h),
+// and the moving average of the weights with its counter in device memory.
 //
 // The updates replace the TF ApplyMomentum / ApplyGradientDescent / ApplyAdam
-// ops that .minimize adds at train.py:147-153.  One launch
+// ops that .minimize adds at train.py:147-153; ApplyRMSProp
+// and ExponentialMovingAverage are the two parts of the published Inception-v3
+// recipe the reference does not use [TF-3P, from reading, version unpinned].  One launch
 // updates the whole flat parameter buffer (21,770,401 fp32 values); each lane
 // moves 16-byte vectors and the arithmetic is the unfused TF expression order.
 // NOTE: hipcc contracts a*b+c into an FMA by default (-ffp-contract=fast),
@@ -115,7 +118,7 @@ __device__ __forceinline__ float sqrt_cr(float x) {
   return (xs == 0.f || !(xs < __builtin_inff())) ? __builtin_sqrtf(x) : s;
 }
 
-enum { kNesterov = 0, kMomentum = 1, kSgd = 2, kAdam = 3 };
+enum { kNesterov = 0, kMomentum = 1, kSgd = 2, kAdam = 3, kRmsprop = 4 };
 
 // One element: g' = g*scale (+ wd*w inside a decay range), then
 //   ApplyMomentum(use_nesterov): accum = accum*m + g'; var -= g'*lr + accum*m*lr
@@ -125,7 +128,11 @@ enum { kNesterov = 0, kMomentum = 1, kSgd = 2, kAdam = 3 };
 //     m += (g' - m) * (1 - beta1);  v += (g'*g' - v) * (1 - beta2);
 //     var -= (m * alpha) / (sqrt(v) + epsilon); lr is the step's alpha =
 //     rate * sqrt(1 - beta2^t) / (1 - beta1^t) (lr_t, computed on the host).
-// p0: momentum, or Adam's beta1 (p1: beta2, p2: epsilon).
+//   ApplyRMSProp (training_ops.cc, the CPU functor; a: mom, v: ms):
+//     ms += (g'*g' - ms) * (1 - rho);  mom = mom*momentum + (g'*lr) / sqrt(ms + epsilon);
+//     var -= mom
+// p0: momentum, or Adam's beta1 (p1: beta2, p2: epsilon), or RMSProp's rho
+// (p1: momentum, p2: epsilon).
 template <int OPT>
 __device__ __forceinline__ void update1(float& w, float g, float& a, float& v, bool decay, float scale, float wd,
                                         float lr, float p0, float p1, float p2) {
@@ -139,6 +146,10 @@ __device__ __forceinline__ void update1(float& w, float g, float& a, float& v, b
     w = __fsub_rn(w, __fmul_rn(a, lr));
   } else if constexpr (OPT == kSgd) {
     w = __fsub_rn(w, __fmul_rn(g, lr));
+  } else if constexpr (OPT == kRmsprop) {
+    v = __fadd_rn(v, __fmul_rn(__fsub_rn(__fmul_rn(g, g), v), __fsub_rn(1.f, p0)));
+    a = __fadd_rn(__fmul_rn(a, p1), __fdiv_rn(__fmul_rn(g, lr), sqrt_cr(__fadd_rn(v, p2))));
+    w = __fsub_rn(w, a);
   } else {
     const float one_b1 = __fsub_rn(1.f, p0), one_b2 = __fsub_rn(1.f, p1);
     a = __fadd_rn(a, __fmul_rn(__fsub_rn(g, a), one_b1));
@@ -179,7 +190,7 @@ __device__ __forceinline__ void update_body(float* __restrict__ w, const float* 
                                             float p2, const SRC src) {
   constexpr bool kDev = std::is_same<SRC, FromDevice>::value;
   static_assert(W == 4 || (W == 1 && !kDev), "the decay classes are per quad");
-  constexpr bool kS1 = OPT != kSgd, kS2 = OPT == kAdam;
+  constexpr bool kS1 = OPT != kSgd, kS2 = OPT == kAdam || OPT == kRmsprop;
   constexpr unsigned kMixed = 16u;
   using V = Vec<W>;
   float scale, lr, wd = 0.f, za = 0.f, zv = 0.f;   // za, zv: the state an optimizer does not have
@@ -269,6 +280,12 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ w, const float
   update_by_alignment<kAdam>(w, grad, mm, vv, n, b1, b2, eps, ByValue{lr_t, gs});
 }
 
+__global__ void __launch_bounds__(256) k_rmsprop(float* __restrict__ w, const float* __restrict__ grad,
+                                                 float* __restrict__ mom, float* __restrict__ ms, int64_t n, float lr,
+                                                 float rho, float m, float eps, float gs) {
+  update_by_alignment<kRmsprop>(w, grad, mom, ms, n, rho, m, eps, ByValue{lr, gs});
+}
+
 #define JR_UPDATE_EX_KERNEL(NAME, OPT)                                                                               \
   __global__ void __launch_bounds__(256) NAME(                                                                       \
       float* __restrict__ w, const float* __restrict__ grad, float* __restrict__ s1, float* __restrict__ s2, int64_t n, \
@@ -280,6 +297,7 @@ JR_UPDATE_EX_KERNEL(k_nesterov_ex, kNesterov)
 JR_UPDATE_EX_KERNEL(k_momentum_ex, kMomentum)
 JR_UPDATE_EX_KERNEL(k_sgd_ex, kSgd)
 JR_UPDATE_EX_KERNEL(k_adam_ex, kAdam)
+JR_UPDATE_EX_KERNEL(k_rmsprop_ex, kRmsprop)
 #undef JR_UPDATE_EX_KERNEL
 
 static dim3 update_grid(int64_t vectors) {
@@ -289,8 +307,9 @@ static dim3 update_grid(int64_t vectors) {
 static int launch_update_ex(const char* what, int opt, float* w, const float* grad, float* s1, float* s2, int64_t n,
                             float p0, float p1, float p2, const jr_opt_range* ranges, int32_t nranges,
                             const jr_opt_hyper* hyper, const jr_opt_step* step, void* stream) {
-  static constexpr decltype(&k_nesterov_ex) kernels[] = {k_nesterov_ex, k_momentum_ex, k_sgd_ex, k_adam_ex};
-  const bool state_ok = (opt == kSgd || s1) && (opt != kAdam || s2);
+  static constexpr decltype(&k_nesterov_ex) kernels[] = {k_nesterov_ex, k_momentum_ex, k_sgd_ex, k_adam_ex,
+                                                        k_rmsprop_ex};
+  const bool state_ok = (opt == kSgd || s1) && ((opt != kAdam && opt != kRmsprop) || s2);
   if (!w || !grad || !state_ok || !hyper || !step || n < 0 || nranges < 0 || (nranges > 0 && !ranges))
     return fail(JR_ERR_INVALID, std::string(what) + ": bad arguments");
   if (!aligned16(w, grad, s1, s2))
@@ -301,6 +320,53 @@ static int launch_update_ex(const char* what, int opt, float* w, const float* gr
   hipLaunchKernelGGL(kernels[opt], update_grid(n >> 2), dim3(256), 0, as_stream(stream), w, grad, s1, s2, n, p0, p1,
                      p2, ranges, (int)nranges, hyper, step);
   return check_launch(what);
+}
+
+// ---- the moving average of the weights (contracts: jr.h) ----
+__global__ void k_ema_set(jr_ema_state* st, float decay, uint32_t warm, uint32_t updates) {
+  st->decay = decay;
+  st->one_minus_decay = __fsub_rn(1.f, decay);
+  st->updates = updates;
+  st->warm = warm;
+}
+
+__global__ void k_ema_prepare(jr_ema_state* st, const jr_opt_step* __restrict__ step) {
+  if (step && step->skipped) {
+    st->one_minus_decay = 0.f;
+    return;
+  }
+  const float decay = st->decay;
+  const uint32_t updates = st->updates;
+  const float t = (float)updates;
+  const float d = st->warm ? fminf(decay, __fdiv_rn(__fadd_rn(1.f, t), __fadd_rn(10.f, t))) : decay;
+  st->one_minus_decay = __fsub_rn(1.f, d);
+  st->updates = updates + 1u;
+}
+
+__device__ __forceinline__ float ema1(float s, float w, float omd) {
+  return __fsub_rn(s, __fmul_rn(__fsub_rn(s, w), omd));
+}
+
+// The loop of update_body at W = 4: tiles of kTile quads in grid-stride order,
+// the last n % 4 elements on block 0.
+__global__ void __launch_bounds__(256) k_ema_update(float* __restrict__ shadow, const float* __restrict__ w, int64_t n,
+                                                    const jr_ema_state* __restrict__ st,
+                                                    const jr_opt_step* __restrict__ step) {
+  if (step && step->skipped) return;   // a skipped step: nothing is written
+  using V = Vec<4>;
+  const float omd = st->one_minus_decay;
+  const int64_t nv = n >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * kTile + threadIdx.x; i < nv; i += (int64_t)gridDim.x * kTile) {
+    V sv = reinterpret_cast<const V*>(shadow)[i];
+    const V wv = reinterpret_cast<const V*>(w)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sv.e[j] = ema1(sv.e[j], wv.e[j], omd);
+    reinterpret_cast<V*>(shadow)[i] = sv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const int64_t e = nv * 4 + threadIdx.x;
+    shadow[e] = ema1(shadow[e], w[e], omd);
+  }
 }
 
 }  // namespace jr
@@ -398,4 +464,45 @@ JR_API int jr_adam_update_ex(float* w, const float* grad, float* m, float* v, in
                              float eps, const jr_opt_range* ranges, int32_t nranges, const jr_opt_hyper* hyper,
                              const jr_opt_step* step, void* stream) {
   return launch_update_ex("adam_ex", kAdam, w, grad, m, v, n, beta1, beta2, eps, ranges, nranges, hyper, step, stream);
+}
+
+JR_API int jr_rmsprop_update(float* w, const float* grad, float* mom, float* ms, int64_t n, float lr, float rho,
+                             float momentum, float eps, float grad_scale, void* stream) {
+  if (!w || !grad || !mom || !ms || n < 0) return fail(JR_ERR_INVALID, "rmsprop: bad arguments");
+  if (n == 0) return JR_OK;
+  hipLaunchKernelGGL(k_rmsprop, update_grid(aligned16(w, grad, mom, ms) ? n >> 2 : n), dim3(256), 0,
+                     as_stream(stream), w, grad, mom, ms, n, lr, rho, momentum, eps, grad_scale);
+  return check_launch("rmsprop");
+}
+
+JR_API int jr_rmsprop_update_ex(float* w, const float* grad, float* mom, float* ms, int64_t n, float rho,
+                                float momentum, float eps, const jr_opt_range* ranges, int32_t nranges,
+                                const jr_opt_hyper* hyper, const jr_opt_step* step, void* stream) {
+  return launch_update_ex("rmsprop_ex", kRmsprop, w, grad, mom, ms, n, rho, momentum, eps, ranges, nranges, hyper,
+                          step, stream);
+}
+
+JR_API int jr_ema_set(jr_ema_state* state, float decay, uint32_t warm, uint32_t updates, void* stream) {
+  if (!state || ((uintptr_t)state & 3) || !(decay >= 0.f && decay < 1.f))
+    return fail(JR_ERR_INVALID, "ema_set: bad arguments");
+  hipLaunchKernelGGL(k_ema_set, dim3(1), dim3(1), 0, as_stream(stream), state, decay, warm ? 1u : 0u, updates);
+  return check_launch("ema_set");
+}
+
+JR_API int jr_ema_prepare(jr_ema_state* state, const jr_opt_step* step, void* stream) {
+  if (!state || ((uintptr_t)state & 3) || ((uintptr_t)step & 3))
+    return fail(JR_ERR_INVALID, "ema_prepare: bad arguments");
+  hipLaunchKernelGGL(k_ema_prepare, dim3(1), dim3(1), 0, as_stream(stream), state, step);
+  return check_launch("ema_prepare");
+}
+
+JR_API int jr_ema_update(float* shadow, const float* w, int64_t n, const jr_ema_state* state, const jr_opt_step* step,
+                         void* stream) {
+  if (!shadow || !w || !state || n < 0) return fail(JR_ERR_INVALID, "ema_update: bad arguments");
+  if (!aligned16(shadow, w)) return fail(JR_ERR_INVALID, "ema_update: buffers must be 16-byte aligned");
+  if (((uintptr_t)state & 3) || ((uintptr_t)step & 3))
+    return fail(JR_ERR_INVALID, "ema_update: misaligned state or step struct");
+  if (n == 0) return JR_OK;
+  hipLaunchKernelGGL(k_ema_update, update_grid(n >> 2), dim3(256), 0, as_stream(stream), shadow, w, n, state, step);
+  return check_launch("ema_update");
 }

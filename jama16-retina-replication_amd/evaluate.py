@@ -123,6 +123,11 @@ def build_parser():
                         "(profiles/frozen_x6h.txt, 299^2, batch 32): the grouped 10-member frozen forward is 4-7 %% "
                         "faster than on x8; one engine per member (--per_member, --attribution) is about 2x slower "
                         "on x6h than on x8, frozen or not")
+    # the moving average of the weights (not in the reference; train.py --weight_ema)
+    p.add_argument("--weights", default="trained", choices=["trained", "averaged"],
+                   help="which weights of every checkpoint to evaluate: trained (the data file; default) or averaged "
+                        "(the moving average train.py --weight_ema saved beside it as <path>.ema).  With --bn moving, "
+                        "averaged needs --bn_calibrate_dir: the saved BN statistics belong to the trained weights")
     # test-time augmentation (not in the reference, which scores one view of every image)
     p.add_argument("--tta", default="none", choices=["none", "flips", "d4"],
                    help="average every member's prediction over views of each test batch, resampled on the GPU: "
@@ -160,28 +165,43 @@ def expand_model_paths(load_model_path: str):
     return [load_model_path]
 
 
+def load_averaged(paths, graph):
+    """Every member's averaged weights (<path>.ema, flat Keras layout);
+    SystemExit naming the first member that has none."""
+    from jr import checkpoint
+    flats = []
+    for path in paths:
+        ema = checkpoint.load_ema(path, graph)
+        if ema is None:
+            raise SystemExit(f"{path}: checkpoint carries no averaged weights (trained without train.py "
+                             "--weight_ema); --weights trained evaluates the weights it has")
+        flats.append(ema[0])
+    return flats
+
+
 def make_engines(paths, meta, batch_size, device=0, conv_math="x6h", dtype="f32", grouped=False, input_grad=False,
-                 x6h_frozen=False):
+                 x6h_frozen=False, flats=None):
     """The ensemble's inference engines, parameters loaded; conv tiles from
     the committed MI355X table of the eval workload (tiles="pinned"; the
     heuristic where none matches): every member and every run sums in the
     same order.  grouped: ONE jr.ensemble.EnsembleEngine holding every member
     (one launch per layer for all members); else one jr.Engine per member
     (input_grad: each with the buffers of Engine.input_gradient).
-    x6h_frozen: the engines' guarded frozen forward on x6h (--x6h_frozen)."""
+    x6h_frozen: the engines' guarded frozen forward on x6h (--x6h_frozen).
+    flats: every member's parameters in place of its data file (--weights averaged)."""
     from jr import checkpoint
     from jr.engine import Engine
     if grouped and conv_math != "x8p":
         from jr.ensemble import EnsembleEngine
-        params = [checkpoint.load(path, None)[0] for path in paths]
+        params = flats if flats is not None else [checkpoint.load(path, None)[0] for path in paths]
         return EnsembleEngine(params, batch_size, meta["height"], meta["width"], meta.get("units", 1), device=device,
                               dtype=dtype, conv_math=conv_math if dtype == "f32" else "bf16", x6h_frozen=x6h_frozen)
     engines = []
-    for path in paths:
+    for k, path in enumerate(paths):
         eng = Engine(batch_size, meta["height"], meta["width"], meta.get("units", 1), device=device,
                      train=False, dtype=dtype, conv_math=conv_math if dtype == "f32" else "bf16",
                      input_grad=input_grad, x6h_frozen=x6h_frozen)
-        flat, _ = checkpoint.load(path, eng.g)
+        flat = flats[k] if flats is not None else checkpoint.load(path, eng.g)[0]
         eng.load_params(flat)
         engines.append(eng)
     return engines
@@ -367,6 +387,10 @@ def main(argv=None):
         parser.print_help()
         return 2
 
+    if args.weights == "averaged" and args.bn == "moving" and args.bn_calibrate_dir is None:
+        raise SystemExit("--weights averaged --bn moving needs --bn_calibrate_dir DIR: the BN statistics saved with a "
+                         "checkpoint belong to its trained weights, not to the averaged ones")
+
     import torch
     from jr import _ffi, checkpoint
 
@@ -411,6 +435,12 @@ Using operating treshold: {},
     # (before any engine is built: d4 refuses images that are not square)
     n_views = len(tta_views(args.tta, meta["height"], meta["width"])) if args.tta != "none" else 1
     conv_math, bn_stats, bn_info = args.conv_math, None, None
+    flats = None
+    if args.weights == "averaged":              # before any engine is built
+        from jr.inception import build_inception_v3
+        flats = load_averaged(load_model_paths, build_inception_v3(meta["height"], meta["width"], meta.get("units", 1)))
+        if rank == 0:
+            print("Weights: averaged (the moving averages saved by train.py --weight_ema)")
     if args.bn == "moving":
         if args.bn_calibrate_dir is None:       # before any engine is built
             from jr.inception import build_inception_v3
@@ -429,7 +459,7 @@ Using operating treshold: {},
                   f"buffers; maps to {attribution['dir']}", file=sys.stderr)
     engines = make_engines(load_model_paths, meta, batch_size, device=local, conv_math=conv_math,
                            dtype=args.dtype, grouped=not (args.per_member or attribution),
-                           input_grad=attribution is not None, x6h_frozen=args.x6h_frozen)
+                           input_grad=attribution is not None, x6h_frozen=args.x6h_frozen, flats=flats)
     if args.bn == "moving":
         k = freeze_engines(engines, bn_stats, args.bn_calibrate_dir, args.bn_calibrate_batches, batch_size)
         if rank == 0 and bn_info is not None:

@@ -127,6 +127,12 @@ class OptRange(Structure):
     _fields_ = [("begin", c_int64), ("end", c_int64)]
 
 
+class EmaState(Structure):
+    """include/jr.h jr_ema_state: the weight average's decay and counter in device memory."""
+    _fields_ = [("decay", c_float), ("one_minus_decay", c_float), ("updates", ctypes.c_uint32),
+                ("warm", ctypes.c_uint32)]
+
+
 class PoolDesc(Structure):
     _fields_ = [(n, c_int32) for n in (
         "n", "h", "w", "c", "ho", "wo", "x_c_off", "x_c_stride", "y_c_off", "y_c_stride")]
@@ -274,6 +280,13 @@ _SIGS = {
     "jr_sgd_update_ex": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "jr_adam_update_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
                                   c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "jr_rmsprop_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
+                                  c_float, c_float, c_float, c_void_p]),
+    "jr_rmsprop_update_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
+                                     c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "jr_ema_set": (c_int, [c_void_p, c_float, ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
+    "jr_ema_prepare": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "jr_ema_update": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "jr_cast_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "jr_cast_bf16_to_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "jr_u8_to_f32_scaled": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),

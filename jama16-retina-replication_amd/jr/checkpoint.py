@@ -17,6 +17,12 @@ per layer, sha256 of the file); checkpoints without them are unchanged:
   <path>.bnstats                raw little-endian float32: per conv2d_bn layer
                                 in graph order, moving_mean[c] then
                                 moving_variance[c]
+
+A checkpoint saved with averaged weights (train.py --weight_ema) has a file
+more, and its .meta a "weight_ema" entry (decay, warm flag, update count,
+sha256 of the file); the data file still holds the trained weights:
+  <path>.ema                    raw little-endian float32, the moving average
+                                of the parameters in the data file's layout
 """
 from __future__ import annotations
 
@@ -31,6 +37,7 @@ from .init import param_layout
 
 DATA_SUFFIX = ".data-00000-of-00001"
 BN_SUFFIX = ".bnstats"
+EMA_SUFFIX = ".ema"
 FORMAT = "jr-checkpoint-v1"
 
 
@@ -39,9 +46,12 @@ def _bn_names(graph):
              n.cout) for n in graph.convs]
 
 
-def save(path: str, graph, flat: np.ndarray, extra: dict | None = None, bn_moving: dict | None = None) -> None:
+def save(path: str, graph, flat: np.ndarray, extra: dict | None = None, bn_moving: dict | None = None,
+         weight_ema: dict | None = None) -> None:
     """bn_moving: None, or {"stats": {Keras name: values} (Engine.bn_moving_numpy),
-    "momentum": float, "updates": int} -- written as <path>.bnstats."""
+    "momentum": float, "updates": int} -- written as <path>.bnstats.
+    weight_ema: None, or {"flat": the averaged parameters (Engine.ema_numpy),
+    "decay": float, "warm": bool, "updates": int} -- written as <path>.ema."""
     layout, total = param_layout(graph.params)
     flat = np.ascontiguousarray(flat, dtype="<f4")
     if flat.size != total:
@@ -64,6 +74,14 @@ def save(path: str, graph, flat: np.ndarray, extra: dict | None = None, bn_movin
         meta["bn_moving"] = {"momentum": float(bn_moving["momentum"]), "updates": int(bn_moving["updates"]),
                              "channels": [c for _, _, c in _bn_names(graph)],
                              "sha256": hashlib.sha256(bn_raw).hexdigest()}
+    ema_raw = None
+    if weight_ema is not None:
+        ema = np.ascontiguousarray(weight_ema["flat"], dtype="<f4").reshape(-1)
+        if ema.size != total:
+            raise ValueError(f"averaged parameter vector has {ema.size} values, layout needs {total}")
+        ema_raw = ema.tobytes()
+        meta["weight_ema"] = {"decay": float(weight_ema["decay"]), "warm": bool(weight_ema["warm"]),
+                              "updates": int(weight_ema["updates"]), "sha256": hashlib.sha256(ema_raw).hexdigest()}
     index = {"format": FORMAT, "total": total, "sha256": hashlib.sha256(raw).hexdigest(),
              "tensors": [{"name": n, "shape": list(s), "offset": o, "size": z} for n, s, o, z in layout]}
     tmp = path + DATA_SUFFIX + ".tmp"
@@ -76,6 +94,12 @@ def save(path: str, graph, flat: np.ndarray, extra: dict | None = None, bn_movin
         os.replace(path + BN_SUFFIX + ".tmp", path + BN_SUFFIX)
     elif os.path.exists(path + BN_SUFFIX):      # statistics of a checkpoint this one replaces
         os.remove(path + BN_SUFFIX)
+    if ema_raw is not None:
+        with open(path + EMA_SUFFIX + ".tmp", "wb") as f:
+            f.write(ema_raw)
+        os.replace(path + EMA_SUFFIX + ".tmp", path + EMA_SUFFIX)
+    elif os.path.exists(path + EMA_SUFFIX):     # the average of a checkpoint this one replaces
+        os.remove(path + EMA_SUFFIX)
     with open(path + ".index", "w") as f:
         json.dump(index, f)
     with open(path + ".meta", "w") as f:
@@ -144,3 +168,22 @@ def load_bn_moving(path: str, graph) -> Optional[dict]:
         out[mean], out[var] = flat[off:off + c].copy(), flat[off + c:off + 2 * c].copy()
         off += 2 * c
     return out
+
+
+def load_ema(path: str, graph) -> Optional[Tuple[np.ndarray, dict]]:
+    """(flat float32 averaged parameters, the .meta "weight_ema" entry) of a
+    checkpoint (Engine.load_ema, or Engine.load_params to run on them), or None
+    when it carries none (saved without train.py --weight_ema).  A size or
+    checksum mismatch of <path>.ema raises."""
+    info = read_meta(path).get("weight_ema")
+    if info is None:
+        return None
+    if not os.path.exists(path + EMA_SUFFIX):
+        raise ValueError(f"{path}: .meta names averaged weights but {path + EMA_SUFFIX} is missing")
+    raw = open(path + EMA_SUFFIX, "rb").read()
+    _, total = param_layout(graph.params)
+    if len(raw) != 4 * total:
+        raise ValueError(f"{path}: averaged weights size mismatch")
+    if hashlib.sha256(raw).hexdigest() != info["sha256"]:
+        raise ValueError(f"{path}: averaged weights checksum mismatch")
+    return np.frombuffer(raw, dtype="<f4").astype(np.float32), dict(info)

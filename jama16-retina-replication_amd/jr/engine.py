@@ -25,6 +25,9 @@ that step, MI355X-native:
   through the guarded entry points (Replica._frozen_guard: a constant scale,
   predictions bitwise batch-independent, an activation above the bound raises
   JRError(JR_ERR_DEVICE) at the next synchronize() / predictions()).
+* Optional (weight_ema=decay): two more launches per step keep a moving
+  average of the weights (jr_ema_prepare, jr_ema_update; the counter and the
+  warm-up decay live on the device); averaged_weights() runs forwards on it.
 * Optional (input_grad=True): a third call list, the data-gradient chain of
   one logit per image down to the image after a frozen forward
   (input_gradient: jr_head_logit_bwd, jr_bn_relu_bwd_frozen, the data
@@ -39,6 +42,7 @@ that step, MI355X-native:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import dataclasses
 import json
@@ -500,7 +504,8 @@ class Engine(Replica):
                  conv_math: Optional[str] = None, defer_wgrad: Optional[bool] = None, fuse_pool: Optional[bool] = None,
                  fold_stats: Optional[bool] = None, bn_moving: Optional[float] = None, input_grad: bool = False,
                  x6h_frozen: bool = False, weight_decay: float = 0.0, clip_norm: Optional[float] = None,
-                 device_lr: bool = False):
+                 device_lr: bool = False, rmsprop_rho: float = 0.9, rmsprop_momentum: float = 0.9,
+                 rmsprop_eps: float = 1.0, weight_ema: Optional[float] = None, weight_ema_warm: bool = True):
         # the optimizer recipe with its scalars in device memory (jr.h: jr_opt_*;
         # off by default, on when any of the three is set): L2 weight decay on
         # the filters and the dense kernel, clipping of the global gradient
@@ -513,6 +518,15 @@ class Engine(Replica):
         self.weight_decay = float(weight_decay)
         self.clip_norm = None if clip_norm is None else float(clip_norm)
         self.opt_ex = bool(train) and (self.weight_decay != 0.0 or self.clip_norm is not None or bool(device_lr))
+        # weight_ema: None, or the decay in [0, 1) of the moving average of the
+        # weights every training step then updates (jr.h: jr_ema_*; TF
+        # ExponentialMovingAverage, 0.9999 in the published Inception-v3 recipe);
+        # weight_ema_warm: decay = min(decay, (1 + t) / (10 + t)) at update t
+        if weight_ema is not None and not 0.0 <= float(weight_ema) < 1.0:
+            raise ValueError("weight_ema: None or a decay in [0, 1)")
+        self.weight_ema = None if weight_ema is None or not train else float(weight_ema)
+        self.weight_ema_warm = bool(weight_ema_warm)
+        self.ema, self.ema_state, self._averaged = None, None, False
         # bn_moving: None, or the momentum of the moving averages of the BN
         # statistics every training step then updates (Keras: 0.99)
         if bn_moving is not None and not 0.0 <= float(bn_moving) <= 1.0:
@@ -536,7 +550,7 @@ class Engine(Replica):
         self.batch, self.train_mode = batch, train
         self._data_grads = train or self.input_grad     # gradient buffers and data-gradient plans exist
         self._frozen_fwd = None         # batch size of the frozen forward since the last set_batch, if any
-        if optimizer not in ("nesterov", "momentum", "sgd", "adam"):
+        if optimizer not in ("nesterov", "momentum", "sgd", "adam", "rmsprop"):
             raise ValueError(f"unknown optimizer {optimizer}")
         self.optimizer = optimizer
         self.lr, self.momentum = float(lr), float(momentum)
@@ -546,6 +560,11 @@ class Engine(Replica):
         # AdamOptimizer._finish does
         self.adam_b1, self.adam_b2, self.adam_eps, self.adam_t = 0.9, 0.999, 1e-8, 0
         self.adam_b1p, self.adam_b2p = np.float32(self.adam_b1), np.float32(self.adam_b2)
+        # RMSProp (TF RMSPropOptimizer; the published Inception-v3 recipe: 0.9,
+        # 0.9, 1.0): accum holds mom (from zeros), adam_v holds ms (from ones).
+        # No per-step host scalar: it captures and follows set_lr like momentum
+        self.rmsprop_rho, self.rmsprop_momentum, self.rmsprop_eps = (float(rmsprop_rho), float(rmsprop_momentum),
+                                                                     float(rmsprop_eps))
         # backward order per conv launch: the data gradient (the critical
         # path to the next layer's BN backward) before the filter gradient
         # (JR_DGRAD_FIRST=0: filter gradient first)
@@ -672,7 +691,10 @@ class Engine(Replica):
         if self.train_mode:
             self.grads = self._t(self.nparam)
             self.accum = self._t(self.nparam)
-            self.adam_v = self._t(self.nparam) if self.optimizer == "adam" else None
+            self.adam_v = self._t(self.nparam) if self.optimizer in ("adam", "rmsprop") else None
+            if self.weight_ema is not None:
+                # the averaged weights (internal layout, padding included) and jr_ema_state
+                self.ema, self.ema_state = self._t(self.nparam), self._t(4)
             if self.opt_ex:
                 # the norm's per-block partials, jr_opt_hyper, jr_opt_step (zeroed: skipped_total
                 # counts from here) and the decay ranges of the internal layout
@@ -916,12 +938,76 @@ class Engine(Replica):
                 # its fp32 beta powers (TF initialises beta1_power / beta2_power to
                 # beta1 / beta2 with the slots)
                 if self.adam_v is not None:
-                    self.adam_v.zero_()
+                    self.adam_v.fill_(1.0 if self.optimizer == "rmsprop" else 0.0)    # (RMSProp's ms starts at ones)
+                if self.ema is not None:
+                    # the average restarts at the new parameters, its counter at zero
+                    self.ema.copy_(self.params)
+                    self._ema_set(0)
         # (and a caller's torch work on these tensors, on its own stream, sees the new values)
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
         if self.train_mode:
             self.adam_t = 0
             self.adam_b1p, self.adam_b2p = np.float32(self.adam_b1), np.float32(self.adam_b2)
+
+    def _ema_set(self, updates: int) -> None:
+        _ffi.check("jr_ema_set", self.lib.jr_ema_set(self.ema_state.data_ptr(), self.weight_ema,
+                                                     int(self.weight_ema_warm), int(updates), self._s))
+
+    def _need_ema(self) -> None:
+        if self.ema is None:
+            raise ValueError("no averaged weights: Engine(weight_ema=decay) keeps them")
+
+    def ema_numpy(self) -> np.ndarray:
+        """The moving average of the weights in the Keras layout."""
+        self._need_ema()
+        torch.cuda.synchronize(self.device)
+        return self.plan.to_keras(self.g, self.ema.cpu().numpy())
+
+    def load_ema(self, flat: np.ndarray, updates: int = 0) -> None:
+        """A saved average (Keras layout, ema_numpy / jr.checkpoint.load_ema)
+        and the number of updates it has seen."""
+        self._need_ema()
+        if self._averaged:
+            raise RuntimeError("load_ema inside averaged_weights()")
+        host = torch.from_numpy(self.plan.to_internal(self.g, flat))
+        with torch.cuda.stream(self.stream):
+            self.ema.copy_(host.to(self.device))
+            self._ema_set(updates)
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+
+    def ema_updates(self) -> int:
+        """The device's count of averaged steps (skipped steps are not counted)."""
+        self._need_ema()
+        self.synchronize()
+        return int(self.ema_state.cpu()[2:3].view(torch.int32)[0])
+
+    def _swap_ema(self) -> None:
+        with torch.cuda.stream(self.stream):
+            tmp = self.params.clone()
+            self.params.copy_(self.ema)
+            self.ema.copy_(tmp)
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside: `params` holds the averaged weights and `ema` the trained
+        ones (the CONTENTS are swapped on the engine's stream -- the call
+        lists hold addresses -- and swapped back on exit); a forward runs on
+        the averaged weights, its own prep rebuilding the filter copies and
+        scales.  Does not nest; no update, training step or replay inside."""
+        self._need_ema()
+        if self._averaged:
+            raise RuntimeError("averaged_weights() does not nest")
+        self._swap_ema()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._averaged = False
+            self._swap_ema()
+
+    def _no_update_on_average(self, what: str) -> None:
+        if self._averaged:
+            raise RuntimeError(f"{what} inside averaged_weights(): params hold the averaged weights")
 
     def params_numpy(self) -> np.ndarray:
         """Parameters in the Keras layout (checkpoints, the oracle)."""
@@ -1485,8 +1571,11 @@ class Engine(Replica):
             return L.jr_momentum_update, L.jr_momentum_update_ex, (acc,), (self.momentum,), pa, 0
         if self.optimizer == "sgd":
             return L.jr_sgd_update, L.jr_sgd_update_ex, (), (), [("p",)], 0
-        return (L.jr_adam_update, L.jr_adam_update_ex, (acc, self.adam_v.data_ptr()),
-                (self.adam_b1, self.adam_b2, self.adam_eps), pa, 0)
+        if self.optimizer == "adam":
+            return (L.jr_adam_update, L.jr_adam_update_ex, (acc, self.adam_v.data_ptr()),
+                    (self.adam_b1, self.adam_b2, self.adam_eps), pa, 0)
+        return (L.jr_rmsprop_update, L.jr_rmsprop_update_ex, (acc, self.adam_v.data_ptr()),
+                (self.rmsprop_rho, self.rmsprop_momentum, self.rmsprop_eps), pa, 28 * self.nparam)
 
     def _by_value_args(self, lr: float, grad_scale: float) -> tuple:
         """The by-value update's arguments (lr: Adam's alpha of the step)."""
@@ -1509,6 +1598,14 @@ class Engine(Replica):
                   self.optimizer + "_update_ex", 0, greads + [("gnorm",)], writes, nbytes=nbytes)
         else:   # (adam: apply_update binds the step's alpha in place of self.lr)
             b.add(b.opt, fn, self._by_value_args(self.lr, 1.0), self.optimizer, 0, greads, writes, nbytes=nbytes)
+        if self.ema is not None:
+            # the moving average of the updated weights, a pass of its own;
+            # the device path hands it the step struct: a skipped step is neither averaged nor counted
+            es, st = self.ema_state.data_ptr(), (self.opt_step_dev.data_ptr() if self.opt_ex else None)
+            gn = [("gnorm",)] if self.opt_ex else []
+            b.add(b.opt, L.jr_ema_prepare, (es, st, s0), "ema_prepare", 0, gn, [("ema",)])
+            b.add(b.opt, L.jr_ema_update, (self.ema.data_ptr(), self.params.data_ptr(), n, es, st, s0), "ema_update", 0,
+                  [("p",), ("ema",)] + gn, [("ema",)], nbytes=12 * n)
         if self.bn_momentum is not None:
             # the moving averages of this step's batch statistics (one launch; jr.h)
             b.add(b.opt, L.jr_bn_moving_update, self._bn_update_args(b.B, self.bn_momentum, s0), "bn_moving", 0,
@@ -1594,6 +1691,7 @@ class Engine(Replica):
         return norm, scale, skipped, total
 
     def apply_update(self, B: Optional[int] = None, grad_scale: float = 1.0) -> None:
+        self._no_update_on_average("apply_update")
         opt = self._build_calls(B or self.batch)[2]
         if self.opt_ex:
             # (a skipped step still counts as a step on the host: Adam's t and beta powers,
@@ -1612,6 +1710,7 @@ class Engine(Replica):
         """fwd + bwd (+ bucketed all-reduce) + optimizer, enqueued on the lanes;
         everything is joined back onto self.stream before the optimizer."""
         B = B or self.batch
+        self._no_update_on_average("train_step")
         if allreduce is None:
             self.forward(B)
             self.backward(B)
@@ -1632,6 +1731,7 @@ class Engine(Replica):
         (waits on events recorded mid-stream) crashed hipGraphInstantiate
         (DESIGN.md §3); more lanes run eagerly."""
         B = B or self.batch
+        self._no_update_on_average("capture")
         if self.optimizer == "adam":
             raise ValueError("Adam steps run eagerly (the step's alpha is a host scalar)")
         if self.nlanes > 2:
@@ -1658,6 +1758,7 @@ class Engine(Replica):
 
     def replay(self, B: Optional[int] = None) -> None:
         B = B or self.batch
+        self._no_update_on_average("replay")
         if self.opt_ex:     # a captured step is single-GPU: grad_scale 1, whatever an eager apply_update left
             self._push_hyper(self.lr, 1.0)
         _ffi.check("jr_graph_launch", self.lib.jr_graph_launch(ctypes.c_void_p(self._graphs[B]), self._s))

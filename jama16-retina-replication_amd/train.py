@@ -59,6 +59,12 @@ class _Parser(argparse.ArgumentParser):
         given = [f for f in GEOMETRY_FLAGS if getattr(ns, f) is not None]
         if given and not ns.augment:
             self.error("--{} needs --augment".format(given[0]))
+        if ns.optimizer is not None and ns.vanilla_sgd:
+            self.error("--optimizer and -sgd both name the optimizer: give one of them")
+        if ns.rmsprop is not None and ns.optimizer != "rmsprop":
+            self.error("--rmsprop needs --optimizer rmsprop")
+        if ns.weight_ema_no_warm and ns.weight_ema is None:
+            self.error("--weight_ema_no_warm needs --weight_ema")
         return ns
 
 
@@ -144,7 +150,67 @@ def build_parser():
                    help="clip the global gradient norm (after the all-reduce) to C; a step whose norm is not "
                         "finite is skipped either way once any of --lr_decay, --lr_warmup, --weight_decay, "
                         "--clip_norm is given")
+    # the rest of the published Inception-v3 recipe (not in the reference: off by default; jr.h jr_rmsprop_*, jr_ema_*)
+    p.add_argument("--optimizer", default=None, choices=["nesterov", "sgd", "adam", "rmsprop"],
+                   help="the optimizer (default: nesterov, or sgd with -sgd; not together with -sgd)")
+    p.add_argument("--rmsprop", type=_rmsprop_arg, default=None, metavar="RHO,MOMENTUM,EPS",
+                   help="RMSProp's decay, momentum and epsilon (default 0.9,0.9,1.0; with --optimizer rmsprop)")
+    p.add_argument("--weight_ema", type=_ema_decay_arg, nargs="?", const=0.9999, default=None, metavar="DECAY",
+                   help="keep a moving average of the weights (decay 0.9999 when given bare) on the GPU: validation, "
+                        "early stopping and the final sweep then run on the averaged weights, and every checkpoint "
+                        "carries both the trained weights and the average (<path>.ema, evaluate.py --weights averaged)")
+    p.add_argument("--weight_ema_no_warm", action="store_true",
+                   help="a fixed decay from the first step (default: min(DECAY, (1 + t) / (10 + t)) at update t)")
     return p
+
+
+RMSPROP_DEFAULT = (0.9, 0.9, 1.0)
+
+
+def _rmsprop_arg(text):
+    """'RHO,MOMENTUM,EPS' -> (rho, momentum, eps): rho and momentum in [0, 1), eps > 0."""
+    what = "RHO,MOMENTUM,EPS with RHO and MOMENTUM in [0, 1) and EPS > 0"
+    try:
+        rho, momentum, eps = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
+    if not (0.0 <= rho < 1.0 and 0.0 <= momentum < 1.0 and eps > 0.0 and np.isfinite(eps)):
+        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
+    return rho, momentum, eps
+
+
+def _ema_decay_arg(text):
+    return _float_arg(text, lambda v: 0.0 <= v < 1.0, "a decay in [0, 1)")
+
+
+def optimizer_name(args):
+    """The Engine's optimizer of the flags: --optimizer, else today's choice."""
+    if args.optimizer is not None:
+        return args.optimizer
+    return "sgd" if args.vanilla_sgd else ("nesterov" if USE_NESTEROV else "momentum")
+
+
+def optimizer_meta(args):
+    """What --optimizer / --rmsprop / --weight_ema add to the recipe saved in the
+    checkpoint .meta (nothing without them)."""
+    out = {}
+    if args.optimizer is not None:
+        out["name"] = args.optimizer
+        if args.optimizer == "rmsprop":
+            out["rmsprop"] = dict(zip(("rho", "momentum", "epsilon"), args.rmsprop or RMSPROP_DEFAULT))
+    if args.weight_ema is not None:
+        out["weight_ema"] = {"decay": args.weight_ema, "warm": not args.weight_ema_no_warm}
+    return out
+
+
+def ema_engine_kwargs(args):
+    """Engine keywords of --optimizer rmsprop and --weight_ema (none without them)."""
+    kw = {}
+    if args.optimizer == "rmsprop":
+        kw.update(zip(("rmsprop_rho", "rmsprop_momentum", "rmsprop_eps"), args.rmsprop or RMSPROP_DEFAULT))
+    if args.weight_ema is not None:
+        kw.update(weight_ema=args.weight_ema, weight_ema_warm=not args.weight_ema_no_warm)
+    return kw
 
 
 def _float_arg(text, ok, what):
@@ -331,12 +397,13 @@ Use SGD: {bool(args.vanilla_sgd)}
         seed=shuffle_seed + 1, decode_dtype="uint8", shard=shard)
 
     engine = Engine(max(TRAIN_BATCH_SIZE, VAL_BATCH_SIZE), args.image_size, args.image_size,
-                    device=local, optimizer="sgd" if args.vanilla_sgd else ("nesterov" if USE_NESTEROV else "momentum"),
+                    device=local, optimizer=optimizer_name(args),
                     lr=LEARNING_RATE if args.learning_rate is None else args.learning_rate, momentum=MOMENTUM,
                     seed=args.seed, dtype=args.dtype,
                     conv_math=args.conv_math if args.dtype == "f32" else "bf16",
                     tiles="pinned" if args.tiles == "pinned" else "heuristic",
-                    **({} if args.bn_moving is None else {"bn_moving": args.bn_moving}), **opt_engine_kwargs(args))
+                    **({} if args.bn_moving is None else {"bn_moving": args.bn_moving}), **opt_engine_kwargs(args),
+                    **ema_engine_kwargs(args))
     table = None
     if args.tile_table:
         table = load_tile_table(args.tile_table)
@@ -363,8 +430,11 @@ Use SGD: {bool(args.vanilla_sgd)}
     if geo_spec:
         run_meta["augment_warp"] = {"spec": geo_spec.to_meta(), "seed": args.augment_seed}
     recipe = opt_recipe(args)
-    if recipe:
-        run_meta["optimizer"] = recipe
+    if recipe or optimizer_meta(args):
+        run_meta["optimizer"] = {**(recipe or {}), **optimizer_meta(args)}
+    # --weight_ema: validation, early stopping and the final sweep read the averaged weights
+    import contextlib
+    averaged = engine.averaged_weights if args.weight_ema is not None else contextlib.nullcontext
     device_opt = bool(opt_engine_kwargs(args))
     if dist:
         from jr.dist import BucketAllReduce
@@ -380,7 +450,7 @@ Use SGD: {bool(args.vanilla_sgd)}
         """Data parallel: every rank applies the same update to the same
         reduced gradient, so the replicas must stay bitwise identical; compare
         a digest of every rank's parameters once per epoch (and dump them for
-        --replica_dump_dir)."""
+        --replica_dump_dir); with --weight_ema the digest covers the average too."""
         if not dist and not args.replica_dump_dir:
             return
         flat = engine.params_numpy()
@@ -389,7 +459,10 @@ Use SGD: {bool(args.vanilla_sgd)}
             np.save(os.path.join(args.replica_dump_dir, f"params_e{epoch}_r{rank}.npy"), flat)
         if dist:
             import hashlib
-            digest = hashlib.sha256(flat.tobytes()).hexdigest()
+            digest = hashlib.sha256(flat.tobytes())
+            if args.weight_ema is not None:
+                digest.update(engine.ema_numpy().tobytes())
+            digest = digest.hexdigest()
             got = [None] * world
             dist.all_gather_object(got, digest)
             if len(set(got)) != 1:
@@ -401,6 +474,13 @@ Use SGD: {bool(args.vanilla_sgd)}
             return {}
         return {"bn_moving": {"stats": engine.bn_moving_numpy(), "momentum": args.bn_moving,
                               "updates": engine.updates}}
+
+    def ema_state():
+        """checkpoint.save's weight_ema argument (--weight_ema), else nothing."""
+        if args.weight_ema is None:
+            return {}
+        return {"weight_ema": {"flat": engine.ema_numpy(), "decay": args.weight_ema,
+                               "warm": not args.weight_ema_no_warm, "updates": engine.ema_updates()}}
     train_writer = FileWriter(os.path.join(args.save_summaries_dir, "train")) if rank == 0 else None
 
     latest_peak_auc = 0.0
@@ -465,8 +545,9 @@ Use SGD: {bool(args.vanilla_sgd)}
 
         # every rank gets the same val_auc (summed counts), so the early-stop
         # decisions below agree and the collectives stay matched
-        val_auc = lib.evaluation.perform_test(sess=sess, init_op=val_dataset,
-                                              summary_writer=train_writer, epoch=epoch)
+        with averaged():
+            val_auc = lib.evaluation.perform_test(sess=sess, init_op=val_dataset,
+                                                  summary_writer=train_writer, epoch=epoch)
         if val_auc < latest_peak_auc + MIN_DELTA_AUC:
             if WAIT_EPOCHS == waited_epochs:
                 if rank == 0:
@@ -479,7 +560,7 @@ Use SGD: {bool(args.vanilla_sgd)}
                 print(f"New peak auc reached: {val_auc:10.8}")
                 checkpoint.save(args.save_model_path, engine.g, engine.params_numpy(),
                                 {"epoch": epoch, "val_auc": float(val_auc), "tile_table": engine.tile_table(),
-                                 **run_meta}, **bn_state())
+                                 **run_meta}, **bn_state(), **ema_state())
             saved = True
             waited_epochs = 0
 
@@ -494,12 +575,17 @@ Use SGD: {bool(args.vanilla_sgd)}
             stats = checkpoint.load_bn_moving(args.save_model_path, engine.g)
             if stats is not None:
                 engine.load_bn_moving(stats, checkpoint.read_meta(args.save_model_path)["bn_moving"]["updates"])
+        if args.weight_ema is not None:     # and the average saved with them
+            ema = checkpoint.load_ema(args.save_model_path, engine.g)
+            if ema is not None:
+                engine.load_ema(ema[0], ema[1]["updates"])
     sess.reset("tp", "fp", "fn", "tn")
     it = iter(train_dataset)
     try:
-        for images, labels in it:
-            probs = sess.predict(images, labels)
-            sess.update(labels, probs, "tp", "fp", "fn", "tn")
+        with averaged():
+            for images, labels in it:
+                probs = sess.predict(images, labels)
+                sess.update(labels, probs, "tp", "fp", "fn", "tn")
     finally:
         lib.dataset.close_iterator(it)
     sess.sync_metrics("tp", "fp", "fn", "tn")
