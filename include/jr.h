@@ -504,6 +504,84 @@ int jr_head_bwd(int mode, const float* feat, const float* w, const float* probs,
 int jr_head_logit_bwd(const float* w, const int32_t* target, int32_t n, int32_t c, int32_t units, float* dfeat,
                       void* stream);
 
+/* ---- the loss recipe: label smoothing, class weights, a focal term --------
+ * (not in the reference: label smoothing is the published Inception-v3
+ * recipe's, the positive-class weight and the focal term are what a strongly
+ * imbalanced screening label asks for.)  jr_head_fwd / jr_head_bwd with a
+ * jr_loss_spec; the kernels are the same, the plain calls are their neutral
+ * case.  spec is a HOST pointer, copied by value into the launch (nothing for
+ * the host to keep alive); NULL: the neutral spec.
+ *
+ * Notation: z logit, y the raw label, p = sigmoid(z) (softmax: p_u),
+ *   e = label_smoothing in [0, 1), g = focal_gamma >= 0,
+ *   c_u = class_weight[u] > 0 (u < units; the rest is ignored),
+ *   sp(z) = max(z, 0) + log1p(exp(-|z|))   (softplus: -log(1 - p) = sp(z),
+ *                                           -log p = sp(-z)),
+ *   1 - p = sigmoid(-z).  Every term is formed from z in these stable forms,
+ *   never from log(1 - p) of a stored p (p is exactly 1 in fp32 from z ~ 17).
+ *
+ * JR_HEAD_SIGMOID, per element (sample i, unit u):
+ *   t     = y (1 - e) + e / 2                   (tf.losses.sigmoid_cross_entropy)
+ *   L     = c_u t (1 - p)^g sp(-z) + (1 - t) p^g sp(z)
+ *   dL/dz = -c_u t (1 - p)^g [g p sp(-z) + (1 - p)] + (1 - t) p^g [g (1 - p) sp(z) + p]
+ *   loss  = sum L / (n units): the plain mean, NOT normalised by the weights;
+ *   the gradient carries the same 1 / (n units).  g = 0: TF
+ *   weighted_cross_entropy_with_logits(pos_weight = c_u) on the smoothed
+ *   target; g = 0 and c = 1: jr_head_fwd's loss with t for y.  (x^0 = 1.)
+ * JR_HEAD_SOFTMAX, per sample:
+ *   t_u  = y_u (1 - e) + e / units              (tf.losses.softmax_cross_entropy)
+ *   s    = sum_u c_u y_u                        (the sample weight, raw labels)
+ *   L    = s sum_u t_u (lse(z) - z_u),  loss = sum L / n
+ *   dz_u = s (p_u sum_v t_v - t_u) / n
+ *   focal_gamma != 0: JR_ERR_INVALID.
+ * A neutral spec (e = 0, g = 0, every used c_u = 1) and NULL give bitwise
+ * what jr_head_fwd / jr_head_bwd give: (p - y) / denom in that order.
+ * JR_ERR_INVALID, before any HIP call: e outside [0, 1), g < 0 or not
+ * finite, a used c_u not finite or <= 0, and everything the plain calls
+ * refuse.  jr_head_bwd_ex takes the logits jr_head_fwd(_ex) left, as well as
+ * the probabilities. */
+typedef struct jr_loss_spec { float label_smoothing, focal_gamma; float class_weight[16]; } jr_loss_spec;
+int jr_head_fwd_ex(int mode, const jr_loss_spec* spec, const float* feat, const float* w, const float* b,
+                   const float* labels, int32_t n, int32_t c, int32_t units, float* logits, float* probs,
+                   float* loss, void* stream);
+int jr_head_bwd_ex(int mode, const jr_loss_spec* spec, const float* logits, const float* feat, const float* w,
+                   const float* probs, const float* labels, int32_t n, int32_t c, int32_t units, float* dfeat,
+                   float* dw, float* db, void* stream);
+
+/* ---- dropout with its state in DEVICE memory (the published Inception-v3
+ *      recipe: rate 0.2 between the global average pool and the dense layer;
+ *      not in the reference) -------------------------------------------------
+ * Nothing stores a mask: it is a pure function of *state and the element
+ * index, so the backward recomputes it, and a captured step draws the next
+ * mask on every replay with no host work.  Per training step, on one stream:
+ *   jr_dropout_fwd  ...  jr_dropout_bwd  ...  jr_dropout_advance
+ * The mask of element i:
+ *   (r0, r1, r2, r3) = philox4x32_10(counter = (lo32(i >> 2), hi32(i >> 2), step, 0), key)
+ *   keep(i) = r[i & 3] >= threshold
+ * Philox4x32-10 (Salmon et al., SC'11; the Random123 known answers hold): ten
+ * rounds of
+ *   (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0))
+ * with M0 = 0xD2511F53, M1 = 0xCD9E8D57 (32 x 32 -> 64-bit products), the key
+ * bumped by (0x9E3779B9, 0xBB67AE85) mod 2^32 between rounds.
+ *   forward:   y  = keep ? x  * scale : 0.0f      (one multiply)
+ *   backward:  dx = keep ? dx * scale : 0.0f      (in place)
+ * rate 0 (threshold 0, scale 1) gives y == x bitwise.  One thread handles one
+ * quad (one Philox block, one 16-byte load and store), the last n % 4
+ * elements singly.  x, y, dx 16-byte aligned and state 4-byte aligned (else
+ * JR_ERR_INVALID, no launch); n <= 0 or a null pointer: JR_ERR_INVALID.
+ * The engine advances the counter once per ENQUEUED training step: a step the
+ * non-finite guard (jr_opt_prepare) skips is counted too -- it drew its mask. */
+typedef struct jr_dropout_state { uint32_t key[2], step, threshold; float scale; uint32_t pad[3]; } jr_dropout_state; /* DEVICE memory */
+/* One thread stores the state (it travels by value in the launch):
+ *   threshold = (uint32_t)floor((double)rate * 2^32)
+ *   scale     = (float)(1.0 / (1.0 - threshold / 2^32))     (both on the host)
+ * rate in [0, 1), else JR_ERR_INVALID. */
+int jr_dropout_set(jr_dropout_state* state, uint32_t key0, uint32_t key1, float rate, uint32_t step, void* stream);
+int jr_dropout_fwd(const float* x, float* y, int64_t n, const jr_dropout_state* state, void* stream);
+int jr_dropout_bwd(float* dx, int64_t n, const jr_dropout_state* state, void* stream);
+/* One thread: step += 1 (mod 2^32). */
+int jr_dropout_advance(jr_dropout_state* state, void* stream);
+
 /* ---- optimizers (train.py:147-153: GradientDescentOptimizer /
  *      MomentumOptimizer(use_nesterov=True) -> TF ApplyMomentum) ------- */
 /* accum = accum*momentum + g; w -= g*lr + accum*momentum*lr   (g = grad*grad_scale) */

@@ -133,6 +133,17 @@ class EmaState(Structure):
                 ("warm", ctypes.c_uint32)]
 
 
+class LossSpec(Structure):
+    """include/jr.h jr_loss_spec: the loss recipe of jr_head_fwd_ex / jr_head_bwd_ex (a HOST struct, copied by value)."""
+    _fields_ = [("label_smoothing", c_float), ("focal_gamma", c_float), ("class_weight", c_float * 16)]
+
+
+class DropoutState(Structure):
+    """include/jr.h jr_dropout_state: key, counter, threshold and scale in device memory (jr_dropout_set writes them)."""
+    _fields_ = [("key", ctypes.c_uint32 * 2), ("step", ctypes.c_uint32), ("threshold", ctypes.c_uint32),
+                ("scale", c_float), ("pad", ctypes.c_uint32 * 3)]
+
+
 class PoolDesc(Structure):
     _fields_ = [(n, c_int32) for n in (
         "n", "h", "w", "c", "ho", "wo", "x_c_off", "x_c_stride", "y_c_off", "y_c_stride")]
@@ -257,6 +268,15 @@ _SIGS = {
     "jr_head_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                             c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jr_head_logit_bwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    # the loss recipe (jr.h): the plain signatures behind (mode, spec); the backward takes the logits too
+    "jr_head_fwd_ex": (c_int, [c_int, POINTER(LossSpec), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                               c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jr_head_bwd_ex": (c_int, [c_int, POINTER(LossSpec), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                               c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jr_dropout_set": (c_int, [c_void_p, ctypes.c_uint32, ctypes.c_uint32, c_float, ctypes.c_uint32, c_void_p]),
+    "jr_dropout_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "jr_dropout_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "jr_dropout_advance": (c_int, [c_void_p, c_void_p]),
     "jr_conv2d_bwd_image": (c_int, [POINTER(ConvDesc), c_int, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "jr_attr_scale_input": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_float, c_void_p]),
     "jr_attr_accumulate": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p]),

@@ -28,6 +28,12 @@ that step, MI355X-native:
 * Optional (weight_ema=decay): two more launches per step keep a moving
   average of the weights (jr_ema_prepare, jr_ema_update; the counter and the
   warm-up decay live on the device); averaged_weights() runs forwards on it.
+* Optional (label_smoothing / class_weight / focal_gamma): the head calls of
+  every list are jr_head_fwd_ex / jr_head_bwd_ex with the loss recipe; and
+  (dropout=rate) the lists of a training step -- _build_calls(training=True):
+  train_step, capture, replay -- drop the pooled features before the dense
+  layer (jr_dropout_fwd / _bwd / _advance; key, counter, threshold and scale
+  in device memory, so a replay draws the next mask).  No other forward drops.
 * Optional (input_grad=True): a third call list, the data-gradient chain of
   one logit per image down to the image after a frozen forward
   (input_gradient: jr_head_logit_bwd, jr_bn_relu_bwd_frozen, the data
@@ -505,7 +511,9 @@ class Engine(Replica):
                  fold_stats: Optional[bool] = None, bn_moving: Optional[float] = None, input_grad: bool = False,
                  x6h_frozen: bool = False, weight_decay: float = 0.0, clip_norm: Optional[float] = None,
                  device_lr: bool = False, rmsprop_rho: float = 0.9, rmsprop_momentum: float = 0.9,
-                 rmsprop_eps: float = 1.0, weight_ema: Optional[float] = None, weight_ema_warm: bool = True):
+                 rmsprop_eps: float = 1.0, weight_ema: Optional[float] = None, weight_ema_warm: bool = True,
+                 label_smoothing: float = 0.0, class_weight=None, focal_gamma: float = 0.0,
+                 dropout: Optional[float] = None, dropout_seed: int = 0, dropout_stream: int = 0):
         # the optimizer recipe with its scalars in device memory (jr.h: jr_opt_*;
         # off by default, on when any of the three is set): L2 weight decay on
         # the filters and the dense kernel, clipping of the global gradient
@@ -527,6 +535,22 @@ class Engine(Replica):
         self.weight_ema = None if weight_ema is None or not train else float(weight_ema)
         self.weight_ema_warm = bool(weight_ema_warm)
         self.ema, self.ema_state, self._averaged = None, None, False
+        # the loss recipe (jr.h jr_loss_spec; off by default, on when any of the
+        # three is set): label smoothing, per-unit class weights (None: ones; one
+        # positive weight per unit), the focal exponent (sigmoid head only).  The
+        # head calls are then jr_head_fwd_ex / jr_head_bwd_ex in every forward, so
+        # loss_value() after a validation forward is the training objective
+        self.loss_spec = self._loss_spec(units, head, label_smoothing, class_weight, focal_gamma)
+        # dropout: None, or the rate in [0, 1) of the dropout between the global
+        # average pool and the dense layer in the forward of a TRAINING step alone
+        # (jr.h jr_dropout_*: the mask is a function of (dropout_seed,
+        # dropout_stream), the device's step counter and the element index;
+        # data-parallel replicas pass their rank as dropout_stream)
+        if dropout is not None and not 0.0 <= float(dropout) < 1.0:
+            raise ValueError("dropout: None or a rate in [0, 1)")
+        self.dropout = None if dropout is None or not train else float(dropout)
+        self.dropout_key = (int(dropout_seed) & 0xFFFFFFFF, int(dropout_stream) & 0xFFFFFFFF)
+        self.feat_drop, self.drop_state = None, None
         # bn_moving: None, or the momentum of the moving averages of the BN
         # statistics every training step then updates (Keras: 0.99)
         if bn_moving is not None and not 0.0 <= float(bn_moving) <= 1.0:
@@ -625,6 +649,29 @@ class Engine(Replica):
         self.load_params(init_params(self.g, seed))
         self._choose_tiles("autotune" if autotune else tiles)
 
+    @staticmethod
+    def _loss_spec(units: int, head: str, label_smoothing: float, class_weight, focal_gamma: float):
+        """The jr_loss_spec of the loss keywords, or None when none is set (the plain head calls)."""
+        eps, gamma = float(label_smoothing), float(focal_gamma)
+        if not 0.0 <= eps < 1.0:
+            raise ValueError("label_smoothing: a value in [0, 1)")
+        if not (gamma >= 0.0 and np.isfinite(gamma)):
+            raise ValueError("focal_gamma: a finite value >= 0")
+        if gamma != 0.0 and head != "sigmoid":
+            raise ValueError("focal_gamma is for head='sigmoid'")
+        if class_weight is None:
+            if eps == 0.0 and gamma == 0.0:
+                return None
+            cw = [1.0] * units
+        else:
+            cw = [float(v) for v in np.asarray(class_weight, np.float64).reshape(-1)]
+            if len(cw) != units or not all(v > 0.0 and np.isfinite(v) for v in cw):
+                raise ValueError(f"class_weight: None or {units} finite weights > 0 (one per unit)")
+        spec = _ffi.LossSpec(eps, gamma)
+        for u in range(16):
+            spec.class_weight[u] = cw[u] if u < units else 1.0
+        return spec
+
     def _choose_tiles(self, tiles: str) -> None:
         """Conv tiles: "pinned" = the committed MI355X table for this workload
         (jr/tiles_mi355x.json, tools/make_tile_tables.py) when there is one,
@@ -695,6 +742,10 @@ class Engine(Replica):
             if self.weight_ema is not None:
                 # the averaged weights (internal layout, padding included) and jr_ema_state
                 self.ema, self.ema_state = self._t(self.nparam), self._t(4)
+            if self.dropout is not None:
+                # the dropped features the head reads in a training step, and jr_dropout_state
+                self.feat_drop, self.drop_state = self._t(B * feat_c), self._t(8)
+                self._dropout_set(0)
             if self.opt_ex:
                 # the norm's per-block partials, jr_opt_hyper, jr_opt_step (zeroed: skipped_total
                 # counts from here) and the decay ranges of the internal layout
@@ -953,6 +1004,17 @@ class Engine(Replica):
         _ffi.check("jr_ema_set", self.lib.jr_ema_set(self.ema_state.data_ptr(), self.weight_ema,
                                                      int(self.weight_ema_warm), int(updates), self._s))
 
+    def _dropout_set(self, step: int) -> None:
+        _ffi.check("jr_dropout_set", self.lib.jr_dropout_set(self.drop_state.data_ptr(), *self.dropout_key, self.dropout,
+                                                             int(step) & 0xFFFFFFFF, self._s))
+
+    def dropout_steps(self) -> int:
+        """Training steps enqueued so far, modulo 2^32: the device counter the next mask is drawn with."""
+        if self.drop_state is None:
+            raise ValueError("no dropout: Engine(dropout=rate) keeps its state")
+        self.synchronize()
+        return int(self.drop_state.cpu()[2:3].view(torch.int32)[0]) & 0xFFFFFFFF
+
     def _need_ema(self) -> None:
         if self.ema is None:
             raise ValueError("no averaged weights: Engine(weight_ema=decay) keeps them")
@@ -1054,14 +1116,19 @@ class Engine(Replica):
             groups = [[mc] for mc in groups[0]]
         return groups
 
-    def _build_calls(self, B: int, nl: Optional[int] = None, frozen: bool = False):
+    def _build_calls(self, B: int, nl: Optional[int] = None, frozen: bool = False, training: bool = False):
         """Pre-bound Calls (jr.lanes) for forward, backward, update on nl
         lanes (default self.nlanes), with their cross-lane waits:
         (fwd, bwd, opt, keep, None).  frozen: the forward alone, every BN
-        apply and fused stem pool reading self.frozen (its own key)."""
+        apply and fused stem pool reading self.frozen (its own key).
+        training: the lists of a training step (train_step, capture); they are
+        the default lists unless dropout is on, which adds jr_dropout_fwd between
+        the pool and the head, jr_dropout_bwd behind the head's backward and
+        jr_dropout_advance at the end of the update."""
         self._ensure_tiles()
         nl = self.nlanes if nl is None else max(1, min(int(nl), self.nlanes))
-        key = (B, nl, "frozen") if frozen else (B, nl)
+        training = bool(training) and self.dropout is not None and not frozen
+        key = (B, nl, "frozen") if frozen else (B, nl, "training") if training else (B, nl)
         if key in self._calls:
             return self._calls[key]
         if B > self.batch or B <= 0:
@@ -1071,6 +1138,7 @@ class Engine(Replica):
         if frozen:
             b.stats_shift = self.frozen.data_ptr() - self.stats.data_ptr()
             b.guard = self._frozen_guard()
+        b.training = training
         self._fwd_prep(b)
         for i, n in enumerate(g.nodes):
             if n.kind != "conv":
@@ -1239,11 +1307,21 @@ class Engine(Replica):
         b.add(b.fwd, self.lib.jr_gap_fwd,
               (self.dt, self._A(g.output_buf), b.B, ob.h * ob.w, ob.c, self.feat.data_ptr(), s0),
               "gap_fwd", 0, self._a_all(g.output_buf), [("feat",)])
-        b.add(b.fwd, self.lib.jr_head_fwd,
-              (self.head_mode, self.feat.data_ptr(), self._p("dense/kernel"), self._p("dense/bias"),
-               self.labels.data_ptr(), b.B, ob.c, self.units, self.logits.data_ptr(), self.probs.data_ptr(),
-               self.loss.data_ptr(), s0),
-              "head_fwd", 0, [("feat",), ("p",), ("lab",)], [("head",)])
+        feat, fkey = self.feat.data_ptr(), ("feat",)
+        if b.training:
+            # a training step's head reads the dropped features (a new mask per step: jr.h)
+            b.add(b.fwd, self.lib.jr_dropout_fwd, (feat, self.feat_drop.data_ptr(), b.B * ob.c,
+                                                   self.drop_state.data_ptr(), s0),
+                  "dropout_fwd", 0, [("feat",), ("drop",)], [("feat_drop",)], nbytes=8 * b.B * ob.c)
+            feat, fkey = self.feat_drop.data_ptr(), ("feat_drop",)
+        args = (feat, self._p("dense/kernel"), self._p("dense/bias"), self.labels.data_ptr(), b.B, ob.c, self.units,
+                self.logits.data_ptr(), self.probs.data_ptr(), self.loss.data_ptr(), s0)
+        if self.loss_spec is not None:
+            b.add(b.fwd, self.lib.jr_head_fwd_ex, (self.head_mode, ctypes.byref(self.loss_spec)) + args,
+                  "head_fwd_ex", 0, [fkey, ("p",), ("lab",)], [("head",)])
+        else:
+            b.add(b.fwd, self.lib.jr_head_fwd, (self.head_mode,) + args,
+                  "head_fwd", 0, [fkey, ("p",), ("lab",)], [("head",)])
 
     # ---- backward
     def _bwd_slab_arena(self, b: Build) -> None:
@@ -1285,11 +1363,21 @@ class Engine(Replica):
     def _bwd_head(self, b: Build) -> None:
         g, s0 = self.g, b.S[0]
         ob = g.bufs[g.output_buf]
-        b.add(b.bwd, self.lib.jr_head_bwd,
-              (self.head_mode, self.feat.data_ptr(), self._p("dense/kernel"), self.probs.data_ptr(),
-               self.labels.data_ptr(), b.B, ob.c, self.units, self.dfeat.data_ptr(), self._gp("dense/kernel"),
-               self._gp("dense/bias"), s0),
-              "head_bwd", 0, [("feat",), ("p",), ("head",), ("lab",)], [("dfeat",), ("g", "dense")])
+        drop = b.training
+        feat, fkey = (self.feat_drop.data_ptr(), ("feat_drop",)) if drop else (self.feat.data_ptr(), ("feat",))
+        args = (feat, self._p("dense/kernel"), self.probs.data_ptr(), self.labels.data_ptr(), b.B, ob.c, self.units,
+                self.dfeat.data_ptr(), self._gp("dense/kernel"), self._gp("dense/bias"), s0)
+        if self.loss_spec is not None:
+            b.add(b.bwd, self.lib.jr_head_bwd_ex,
+                  (self.head_mode, ctypes.byref(self.loss_spec), self.logits.data_ptr()) + args,
+                  "head_bwd_ex", 0, [fkey, ("p",), ("head",), ("lab",)], [("dfeat",), ("g", "dense")])
+        else:
+            b.add(b.bwd, self.lib.jr_head_bwd, (self.head_mode,) + args,
+                  "head_bwd", 0, [fkey, ("p",), ("head",), ("lab",)], [("dfeat",), ("g", "dense")])
+        if drop:
+            # the forward's mask again, recomputed from the state (the counter advances after the update)
+            b.add(b.bwd, self.lib.jr_dropout_bwd, (self.dfeat.data_ptr(), b.B * ob.c, self.drop_state.data_ptr(), s0),
+                  "dropout_bwd", 0, [("drop",)], [("dfeat",)], nbytes=8 * b.B * ob.c)
         b.add(b.bwd, self.lib.jr_gap_bwd,
               (self.dt, self.dfeat.data_ptr(), b.B, ob.h * ob.w, ob.c, self._D(g.output_buf), s0),
               "gap_bwd", 0, [("dfeat",)], self._d_all(g.output_buf))
@@ -1610,6 +1698,9 @@ class Engine(Replica):
             # the moving averages of this step's batch statistics (one launch; jr.h)
             b.add(b.opt, L.jr_bn_moving_update, self._bn_update_args(b.B, self.bn_momentum, s0), "bn_moving", 0,
                   [("r", u.first.idx) for u in self.cunits], [("bn_moving",)], nbytes=4 * 2 * self.stats_ms)
+        if b.training:
+            # the next step's mask: the counter counts enqueued steps, a skipped one included (jr.h)
+            b.add(b.opt, L.jr_dropout_advance, (self.drop_state.data_ptr(), s0), "dropout_advance", 0, [], [("drop",)])
 
     def fence_lanes(self, stream) -> None:
         """`stream` (the gradient all-reduce's) waits for the work enqueued on
@@ -1633,18 +1724,21 @@ class Engine(Replica):
         return B
 
     # ------------------------------------------------------------------- runs
-    def forward(self, B: Optional[int] = None, bn: str = "batch") -> None:
+    def forward(self, B: Optional[int] = None, bn: str = "batch", training: bool = False) -> None:
         """bn="frozen": normalise with the statistics of freeze_bn() instead
-        of this batch's (every image's output then depends on that image alone)."""
+        of this batch's (every image's output then depends on that image alone).
+        training: the forward of a training step (train_step passes it): with
+        dropout on it drops, and backward / apply_update of that step take
+        training=True too.  Every other forward never drops."""
         frozen = self._check_frozen(bn)
-        fwd = self._build_calls(B or self.batch, frozen=frozen)[0]
+        fwd = self._build_calls(B or self.batch, frozen=frozen, training=training)[0]
         self._frozen_fwd = (B or self.batch) if frozen else None
         self.lanes.fork()
         self.lanes.run(fwd)
         self.lanes.join()
 
-    def backward(self, B: Optional[int] = None, hook=None) -> None:
-        self.lanes.run(self._build_calls(B or self.batch)[1], hook)
+    def backward(self, B: Optional[int] = None, hook=None, training: bool = False) -> None:
+        self.lanes.run(self._build_calls(B or self.batch, training=training)[1], hook)
         self.lanes.join()
 
     def _adam_alpha(self) -> float:
@@ -1690,9 +1784,9 @@ class Engine(Replica):
         skipped, total = (int(v) for v in raw[2:].view(torch.int32))
         return norm, scale, skipped, total
 
-    def apply_update(self, B: Optional[int] = None, grad_scale: float = 1.0) -> None:
+    def apply_update(self, B: Optional[int] = None, grad_scale: float = 1.0, training: bool = False) -> None:
         self._no_update_on_average("apply_update")
-        opt = self._build_calls(B or self.batch)[2]
+        opt = self._build_calls(B or self.batch, training=training)[2]
         if self.opt_ex:
             # (a skipped step still counts as a step on the host: Adam's t and beta powers,
             # and the BN moving averages and self.updates below, advance; only the device
@@ -1712,15 +1806,15 @@ class Engine(Replica):
         B = B or self.batch
         self._no_update_on_average("train_step")
         if allreduce is None:
-            self.forward(B)
-            self.backward(B)
-            self.apply_update(B)
+            self.forward(B, training=True)
+            self.backward(B, training=True)
+            self.apply_update(B, training=True)
             return
-        self.forward(B)
+        self.forward(B, training=True)
         allreduce.begin(self)
-        self.backward(B, hook=allreduce.param_ready)
+        self.backward(B, hook=allreduce.param_ready, training=True)
         scale = allreduce.finish(self)
-        self.apply_update(B, grad_scale=scale)
+        self.apply_update(B, grad_scale=scale, training=True)
 
     def capture(self, B: Optional[int] = None) -> None:
         """Capture fwd+bwd+update for batch B into a HIP graph (single GPU;
@@ -1736,7 +1830,7 @@ class Engine(Replica):
             raise ValueError("Adam steps run eagerly (the step's alpha is a host scalar)")
         if self.nlanes > 2:
             raise ValueError("HIP graph capture supports at most two lanes (more lanes run eagerly)")
-        fwd, bwd, opt, _, _ = self._build_calls(B)
+        fwd, bwd, opt, _, _ = self._build_calls(B, training=True)
         if self.opt_ex:     # the graph reads the scalars: written ahead of it, never inside it
             self._push_hyper(self.lr, 1.0)
         torch.cuda.synchronize(self.device)

@@ -165,6 +165,8 @@ class Build:
         # ... and, for JR_F32_X6H under frozen statistics, the limit of the guarded
         # BN applies and fused pools (None: the unguarded entry points)
         self.guard = None
+        # the lists of a training step with dropout on (Engine._build_calls(training=True))
+        self.training = False
 
     def add(self, lst, fn, args, name, lane, reads=(), writes=(), nbytes=0) -> None:
         c = Call(fn, args, name, lane, tuple(reads), tuple(writes), nbytes=int(nbytes))

@@ -65,6 +65,8 @@ class _Parser(argparse.ArgumentParser):
             self.error("--rmsprop needs --optimizer rmsprop")
         if ns.weight_ema_no_warm and ns.weight_ema is None:
             self.error("--weight_ema_no_warm needs --weight_ema")
+        if ns.dropout_seed is not None and ns.dropout is None:
+            self.error("--dropout_seed needs --dropout")
         return ns
 
 
@@ -161,7 +163,76 @@ def build_parser():
                         "carries both the trained weights and the average (<path>.ema, evaluate.py --weights averaged)")
     p.add_argument("--weight_ema_no_warm", action="store_true",
                    help="a fixed decay from the first step (default: min(DECAY, (1 + t) / (10 + t)) at update t)")
+    # the loss recipe and dropout (not in the reference: off by default; jr.h jr_loss_spec, jr_dropout_*).  With any
+    # of the first three the `Xent:` of the status line and the validation loss are the training objective
+    # (smoothed, weighted, focal), no longer the plain cross-entropy
+    p.add_argument("--label_smoothing", type=_smoothing_arg, default=None, metavar="E",
+                   help="smooth the labels towards 1/2 by E in [0, 1) (0.1 in the published Inception-v3 recipe); "
+                        "the `Xent:` status value is then the training objective")
+    p.add_argument("--pos_weight", type=_positive_float, default=None, metavar="W",
+                   help="weight the positive class's term of the loss by W > 0 (an imbalanced label); the `Xent:` "
+                        "status value is then the training objective")
+    p.add_argument("--focal_gamma", type=_nonnegative_float, default=None, metavar="G",
+                   help="focal exponent G >= 0 on both terms of the loss; the `Xent:` status value is then the "
+                        "training objective")
+    p.add_argument("--dropout", type=_dropout_arg, default=None, metavar="RATE",
+                   help="drop the pooled features before the dense layer at RATE in [0, 1) in training steps only "
+                        "(0.2 in the published Inception-v3 recipe); a new mask every step, drawn on the GPU")
+    p.add_argument("--dropout_seed", type=int, default=None, metavar="N",
+                   help="seed of the dropout masks (default 0; rank r draws stream r of it; with --dropout)")
     return p
+
+
+def _smoothing_arg(text):
+    return _float_arg(text, lambda v: 0.0 <= v < 1.0, "a smoothing in [0, 1)")
+
+
+def _dropout_arg(text):
+    return _float_arg(text, lambda v: 0.0 <= v < 1.0, "a rate in [0, 1)")
+
+
+LOSS_FLAGS = ("label_smoothing", "pos_weight", "focal_gamma", "dropout")
+
+
+def loss_meta(args):
+    """What --label_smoothing / --pos_weight / --focal_gamma / --dropout save as the
+    "loss" entry of the checkpoint .meta (None: none of them is given)."""
+    if all(getattr(args, f) is None for f in LOSS_FLAGS):
+        return None
+    return {"label_smoothing": args.label_smoothing or 0.0, "pos_weight": args.pos_weight,
+            "focal_gamma": args.focal_gamma or 0.0, "dropout": args.dropout,
+            "dropout_seed": (args.dropout_seed or 0) if args.dropout is not None else None}
+
+
+def loss_engine_kwargs(args, rank=0):
+    """Engine keywords of the loss and dropout flags (none without them); rank: the dropout stream."""
+    kw = {}
+    if args.label_smoothing is not None:
+        kw["label_smoothing"] = args.label_smoothing
+    if args.pos_weight is not None:
+        kw["class_weight"] = [args.pos_weight]
+    if args.focal_gamma is not None:
+        kw["focal_gamma"] = args.focal_gamma
+    if args.dropout is not None:
+        kw.update(dropout=args.dropout, dropout_seed=args.dropout_seed or 0, dropout_stream=rank)
+    return kw
+
+
+def objective_line(args):
+    """The start-up line that names the objective of the loss flags (None without them)."""
+    m = loss_meta(args)
+    if m is None:
+        return None
+    parts = ["sigmoid cross-entropy"]
+    if m["label_smoothing"]:
+        parts.append("label smoothing {:g}".format(m["label_smoothing"]))
+    if m["pos_weight"] is not None:
+        parts.append("positive weight {:g}".format(m["pos_weight"]))
+    if m["focal_gamma"]:
+        parts.append("focal gamma {:g}".format(m["focal_gamma"]))
+    if m["dropout"] is not None:
+        parts.append("dropout {:g} before the dense layer (seed {})".format(m["dropout"], m["dropout_seed"]))
+    return "Objective: " + ", ".join(parts)
 
 
 RMSPROP_DEFAULT = (0.9, 0.9, 1.0)
@@ -403,7 +474,7 @@ Use SGD: {bool(args.vanilla_sgd)}
                     conv_math=args.conv_math if args.dtype == "f32" else "bf16",
                     tiles="pinned" if args.tiles == "pinned" else "heuristic",
                     **({} if args.bn_moving is None else {"bn_moving": args.bn_moving}), **opt_engine_kwargs(args),
-                    **ema_engine_kwargs(args))
+                    **ema_engine_kwargs(args), **loss_engine_kwargs(args, rank))
     table = None
     if args.tile_table:
         table = load_tile_table(args.tile_table)
@@ -432,6 +503,10 @@ Use SGD: {bool(args.vanilla_sgd)}
     recipe = opt_recipe(args)
     if recipe or optimizer_meta(args):
         run_meta["optimizer"] = {**(recipe or {}), **optimizer_meta(args)}
+    if loss_meta(args):
+        run_meta["loss"] = loss_meta(args)
+        if rank == 0:
+            print(objective_line(args))
     # --weight_ema: validation, early stopping and the final sweep read the averaged weights
     import contextlib
     averaged = engine.averaged_weights if args.weight_ema is not None else contextlib.nullcontext
