@@ -699,6 +699,22 @@ int jr_ema_prepare(jr_ema_state* state, const jr_opt_step* step, void* stream);
 int jr_ema_update(float* shadow, const float* w, int64_t n, const jr_ema_state* state, const jr_opt_step* step,
                   void* stream);
 
+/* ---- gradient accumulation (K micro-batches per optimizer update; not in
+ *      the reference) ---------------------------------------------------------
+ *   dst[i] = first ? src[i] : dst[i] + src[i],   i in [0, n)
+ * one correctly rounded fp32 add per element, no atomics: the result does not
+ * depend on the grid.  One call serves both directions of a group of
+ * micro-batches: acc <- (first ? g : acc + g) on a micro-step that does not
+ * close the group, g <- g + acc (first = 0) on the one that does; fp32 addition
+ * commutes, so the closed gradient is bitwise ((g0 + g1) + g2) + ... in
+ * micro-batch order.  first != 0 is a copy: dst is never read, so whatever an
+ * abandoned group left there (a NaN included) is gone.
+ * Any 4-byte alignment (16-byte moves when both pointers are 16-byte aligned,
+ * single elements otherwise: the data-parallel path folds bucket sub-ranges of
+ * the flat buffers).  JR_ERR_INVALID, before any HIP call: a null or
+ * misaligned pointer, n <= 0, or [dst, dst + n) overlapping [src, src + n). */
+int jr_grad_accumulate(float* dst, const float* src, int64_t n, int first, void* stream);
+
 /* ---- bf16 filter copies (the bf16 conv path's weight operands) -------
  * From the fp32 master kernel [kh][kw][c_in][c_out] write
  *   w_hwio: bf16 [kh][kw][c_in][c_out]        (jr_conv2d_bwd_data, JR_BF16)

@@ -3,7 +3,8 @@
 // global gradient norm, the clip factor and the non-finite guard, and the five
 // updates reading (lr, weight_decay) and (scale, skipped) from device memory,
 // so a captured step replays under a changing learning rate; contracts: jr.h),
-// and the moving average of the weights with its counter in device memory.
+// the moving average of the weights with its counter in device memory, and the
+// add that accumulates K micro-batches' gradients per update.
 //
 // The updates replace the TF ApplyMomentum / ApplyGradientDescent / ApplyAdam
 // ops that .minimize adds at train.py:147-153; ApplyRMSProp
@@ -369,6 +370,39 @@ __global__ void __launch_bounds__(256) k_ema_update(float* __restrict__ shadow, 
   }
 }
 
+// ---- gradient accumulation (contract: jr.h) ----
+// k_ema_update's loop at W = 4 (W = 1: buffers that are not 16-byte aligned,
+// no tail).  FIRST: a copy -- dst is not read.
+template <int W, bool FIRST>
+__device__ __forceinline__ void accumulate_body(float* __restrict__ dst, const float* __restrict__ src, int64_t n) {
+  using V = Vec<W>;
+  const int64_t nv = W == 4 ? n >> 2 : n;
+  for (int64_t i = (int64_t)blockIdx.x * kTile + threadIdx.x; i < nv; i += (int64_t)gridDim.x * kTile) {
+    V sv = reinterpret_cast<const V*>(src)[i];
+    if constexpr (!FIRST) {
+      const V dv = reinterpret_cast<const V*>(dst)[i];
+#pragma unroll
+      for (int j = 0; j < W; ++j) sv.e[j] = __fadd_rn(dv.e[j], sv.e[j]);
+    }
+    reinterpret_cast<V*>(dst)[i] = sv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & (W - 1))) {
+    const int64_t e = nv * W + threadIdx.x;
+    dst[e] = FIRST ? src[e] : __fadd_rn(dst[e], src[e]);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_grad_accumulate(float* __restrict__ dst, const float* __restrict__ src,
+                                                         int64_t n, int first) {
+  if (aligned16(dst, src)) {   // (the host sizes the grid by the same test)
+    if (first) accumulate_body<4, true>(dst, src, n);
+    else accumulate_body<4, false>(dst, src, n);
+  } else {
+    if (first) accumulate_body<1, true>(dst, src, n);
+    else accumulate_body<1, false>(dst, src, n);
+  }
+}
+
 }  // namespace jr
 
 using namespace jr;
@@ -505,4 +539,14 @@ JR_API int jr_ema_update(float* shadow, const float* w, int64_t n, const jr_ema_
   if (n == 0) return JR_OK;
   hipLaunchKernelGGL(k_ema_update, update_grid(n >> 2), dim3(256), 0, as_stream(stream), shadow, w, n, state, step);
   return check_launch("ema_update");
+}
+
+JR_API int jr_grad_accumulate(float* dst, const float* src, int64_t n, int first, void* stream) {
+  if (!dst || !src || n <= 0) return fail(JR_ERR_INVALID, "grad_accumulate: bad arguments");
+  if (((uintptr_t)dst | (uintptr_t)src) & 3) return fail(JR_ERR_INVALID, "grad_accumulate: misaligned buffers");
+  const uintptr_t d0 = (uintptr_t)dst, s0 = (uintptr_t)src, bytes = (uintptr_t)n * 4;
+  if (d0 < s0 + bytes && s0 < d0 + bytes) return fail(JR_ERR_INVALID, "grad_accumulate: dst and src overlap");
+  hipLaunchKernelGGL(k_grad_accumulate, update_grid(aligned16(dst, src) ? n >> 2 : n), dim3(256), 0, as_stream(stream),
+                     dst, src, n, first ? 1 : 0);
+  return check_launch("grad_accumulate");
 }

@@ -307,6 +307,7 @@ _SIGS = {
     "jr_ema_set": (c_int, [c_void_p, c_float, ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
     "jr_ema_prepare": (c_int, [c_void_p, c_void_p, c_void_p]),
     "jr_ema_update": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "jr_grad_accumulate": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "jr_cast_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "jr_cast_bf16_to_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "jr_u8_to_f32_scaled": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),

@@ -31,6 +31,17 @@ Two transports, same bucket walk:
 and two payloads: fp32 (default; the sum of fp32 gradients) or bf16 (43.5 MB
 instead of 87.1 MB: each bucket cast to bf16, summed in bf16 by RCCL, cast
 back; ranks stay identical, the sum carries bf16 rounding).
+
+Gradient accumulation (Engine(accum_steps=K > 1)): only the micro-step that
+closes a group exchanges anything -- the others run the backward without the
+hook.  On the closing step (begin(fold=True)) each bucket's share of the
+group's earlier gradients is added just before the bucket is issued, on the
+issuing stream behind the fence it already takes:
+jr_grad_accumulate(grads + lo, gacc + lo, hi - lo, 0).  The fold therefore
+rides the bucket walk -- a bucket still leaves as soon as its gradients are
+final, and the backward's lanes never see it -- where one fold of the whole
+buffer would have to wait for the end of the backward and hold every bucket
+back with it.  `finish` still returns 1 / world; the engine divides by k.
 """
 from __future__ import annotations
 
@@ -187,6 +198,7 @@ class BucketAllReduce:
         self.feed = (torch.cuda.Stream(device=engine.grads.device)
                      if comm is None and getattr(engine, "stream", None) is not None else None)
         self.fences = 0                 # issue points that fenced the lanes (one per issue point with work)
+        self.fold = False               # this step closes a group of micro-batches: add engine.gacc per bucket
         # trace=True: timing events on the issuing stream right after each
         # fence (the bucket's gradients are final: its all-reduce can start)
         # and on lane 0 when the backward has been joined (finish); see
@@ -194,7 +206,9 @@ class BucketAllReduce:
         self.trace = False
         self._tev: List[Tuple[str, object]] = []
 
-    def begin(self, eng=None) -> None:
+    def begin(self, eng=None, fold: bool = False) -> None:
+        """fold: the step closes a group of accumulated micro-batches (Engine._accum_step)."""
+        self.fold = bool(fold)
         self.works = []
         self.next = 0
         self.fences = 0
@@ -275,6 +289,11 @@ class BucketAllReduce:
         self._mark("ready", st)
         while self.ready(ready_from):
             lo, hi = self.buckets[self.next]
+            if self.fold:       # g[lo:hi] += acc[lo:hi] on the issuing stream, behind the fence
+                g, acc = self.eng.grads.data_ptr() + 4 * lo, self.eng.gacc.data_ptr() + 4 * lo
+                _ffi.check("jr_grad_accumulate", _ffi.load().jr_grad_accumulate(
+                    ctypes.c_void_p(g), ctypes.c_void_p(acc), hi - lo, 0,
+                    ctypes.c_void_p(st.cuda_stream if st is not None else 0)))
             if self.comm is not None:
                 self._issue_jr(lo, hi)
             else:

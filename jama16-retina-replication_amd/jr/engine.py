@@ -34,6 +34,11 @@ that step, MI355X-native:
   train_step, capture, replay -- drop the pooled features before the dense
   layer (jr_dropout_fwd / _bwd / _advance; key, counter, threshold and scale
   in device memory, so a replay draws the next mask).  No other forward drops.
+* Optional (accum_steps=K > 1): K micro-batches per optimizer update.  A
+  micro-step that does not close its group ends with jr_grad_accumulate into
+  one more flat buffer (acc <- g, then acc <- acc + g) instead of the
+  optimizer; the closing one folds it back (g <- g + acc) ahead of today's
+  update phase, whose grad_scale becomes 1 / (k * world).
 * Optional (input_grad=True): a third call list, the data-gradient chain of
   one logit per image down to the image after a frozen forward
   (input_gradient: jr_head_logit_bwd, jr_bn_relu_bwd_frozen, the data
@@ -513,7 +518,8 @@ class Engine(Replica):
                  device_lr: bool = False, rmsprop_rho: float = 0.9, rmsprop_momentum: float = 0.9,
                  rmsprop_eps: float = 1.0, weight_ema: Optional[float] = None, weight_ema_warm: bool = True,
                  label_smoothing: float = 0.0, class_weight=None, focal_gamma: float = 0.0,
-                 dropout: Optional[float] = None, dropout_seed: int = 0, dropout_stream: int = 0):
+                 dropout: Optional[float] = None, dropout_seed: int = 0, dropout_stream: int = 0,
+                 accum_steps: int = 1):
         # the optimizer recipe with its scalars in device memory (jr.h: jr_opt_*;
         # off by default, on when any of the three is set): L2 weight decay on
         # the filters and the dense kernel, clipping of the global gradient
@@ -551,6 +557,16 @@ class Engine(Replica):
         self.dropout = None if dropout is None or not train else float(dropout)
         self.dropout_key = (int(dropout_seed) & 0xFFFFFFFF, int(dropout_stream) & 0xFFFFFFFF)
         self.feat_drop, self.drop_state = None, None
+        # accum_steps: micro-batches per optimizer update (1: every batch updates, nothing
+        # below exists).  K > 1: every train_step still runs the forward, the backward, the
+        # BN moving averages and the dropout counter, but only the K-th of a group runs the
+        # optimizer, on the sum of the group's gradients scaled by 1 / (k * world) -- K
+        # virtual data-parallel ranks, each under its own BN statistics (jr.h
+        # jr_grad_accumulate; `gacc` holds the open group's sum, _pending counts it)
+        if isinstance(accum_steps, bool) or int(accum_steps) != accum_steps or int(accum_steps) < 1:
+            raise ValueError("accum_steps: a whole number of micro-batches >= 1")
+        self.accum_steps = int(accum_steps) if train else 1
+        self.gacc, self._pending = None, 0
         # bn_moving: None, or the momentum of the moving averages of the BN
         # statistics every training step then updates (Keras: 0.99)
         if bn_moving is not None and not 0.0 <= float(bn_moving) <= 1.0:
@@ -643,7 +659,7 @@ class Engine(Replica):
             defer_wgrad = env == "1" if env in ("0", "1") else self.dt != _ffi.JR_F32
         self.defer_wgrad = bool(defer_wgrad)
         self._flush_points: List[int] = []
-        self._graphs: Dict[int, int] = {}
+        self._graphs: Dict[object, int] = {}     # batch (accum_steps > 1: (batch, phase)) -> executable
         self.bucket_hooks: List[Tuple[int, Callable]] = []
         self._alloc()
         self.load_params(init_params(self.g, seed))
@@ -746,6 +762,8 @@ class Engine(Replica):
                 # the dropped features the head reads in a training step, and jr_dropout_state
                 self.feat_drop, self.drop_state = self._t(B * feat_c), self._t(8)
                 self._dropout_set(0)
+            if self.accum_steps > 1:
+                self.gacc = self._t(self.nparam)    # the open group's gradient sum, resource ("gacc",)
             if self.opt_ex:
                 # the norm's per-block partials, jr_opt_hyper, jr_opt_step (zeroed: skipped_total
                 # counts from here) and the decay ranges of the internal layout
@@ -999,6 +1017,7 @@ class Engine(Replica):
         if self.train_mode:
             self.adam_t = 0
             self.adam_b1p, self.adam_b2p = np.float32(self.adam_b1), np.float32(self.adam_b2)
+            self._pending = 0       # an open group of micro-batches is discarded (its sum is overwritten by the next)
 
     def _ema_set(self, updates: int) -> None:
         _ffi.check("jr_ema_set", self.lib.jr_ema_set(self.ema_state.data_ptr(), self.weight_ema,
@@ -1116,7 +1135,8 @@ class Engine(Replica):
             groups = [[mc] for mc in groups[0]]
         return groups
 
-    def _build_calls(self, B: int, nl: Optional[int] = None, frozen: bool = False, training: bool = False):
+    def _build_calls(self, B: int, nl: Optional[int] = None, frozen: bool = False, training: bool = False,
+                     accum: Optional[str] = None):
         """Pre-bound Calls (jr.lanes) for forward, backward, update on nl
         lanes (default self.nlanes), with their cross-lane waits:
         (fwd, bwd, opt, keep, None).  frozen: the forward alone, every BN
@@ -1124,12 +1144,29 @@ class Engine(Replica):
         training: the lists of a training step (train_step, capture); they are
         the default lists unless dropout is on, which adds jr_dropout_fwd between
         the pool and the head, jr_dropout_bwd behind the head's backward and
-        jr_dropout_advance at the end of the update."""
+        jr_dropout_advance at the end of the update.
+        accum (accum_steps > 1 only): where the micro-batch sits in its group --
+        "open" / "inside": the update phase is jr_grad_accumulate(acc <- g, first
+        = 1 / acc <- acc + g) and what runs once per batch (the BN moving
+        averages, the dropout counter); "close": jr_grad_accumulate(g <- g +
+        acc), then the default update phase.  None: the default lists (a group
+        closed under data parallelism, where jr.dist folds per bucket)."""
+        if accum is not None and (self.gacc is None or frozen or accum not in ("open", "inside", "close")):
+            raise ValueError("accum: 'open', 'inside' or 'close', with accum_steps > 1")
         self._ensure_tiles()
         nl = self.nlanes if nl is None else max(1, min(int(nl), self.nlanes))
         training = bool(training) and self.dropout is not None and not frozen
         key = (B, nl, "frozen") if frozen else (B, nl, "training") if training else (B, nl)
+        if accum is not None:
+            key += ("accum", accum)
         if key in self._calls:
+            return self._calls[key]
+        if accum == "inside":
+            # the opening lists with first = 0: the same calls, schedule and buffers
+            fwd, bwd, opt, keep, _ = self._build_calls(B, nl, training=training, accum="open")
+            a = opt[0].args
+            opt = [dataclasses.replace(opt[0], args=a[:3] + (0,) + a[4:])] + list(opt[1:])
+            self._calls[key] = (fwd, bwd, opt, keep, None)
             return self._calls[key]
         if B > self.batch or B <= 0:
             raise ValueError(f"batch {B} outside 1..{self.batch}")
@@ -1139,6 +1176,7 @@ class Engine(Replica):
             b.stats_shift = self.frozen.data_ptr() - self.stats.data_ptr()
             b.guard = self._frozen_guard()
         b.training = training
+        b.accum = accum
         self._fwd_prep(b)
         for i, n in enumerate(g.nodes):
             if n.kind != "conv":
@@ -1674,7 +1712,23 @@ class Engine(Replica):
         L, s0, n, G = self.lib, b.S[0], self.nparam, self.grads.data_ptr()
         fn, fn_ex, state, hyper, writes, nbytes = self._opt_desc()
         greads = [("g", u.first.idx) for u in self.cunits] + [("g", "dense")]
-        if self.opt_ex:
+        ph = b.accum
+        if ph is not None:
+            # the group's sum (jr.h jr_grad_accumulate): acc <- g / acc <- acc + g on a micro-step that
+            # leaves the group open, g <- g + acc on the closing one, g <- acc when accum_flush
+            # closes a partial group.  ("inside" is "open" with first = 0: _build_calls)
+            A = self.gacc.data_ptr()
+            if ph == "open":
+                b.add(b.opt, L.jr_grad_accumulate, (A, G, n, 1, s0), "grad_accumulate", 0, greads, [("gacc",)],
+                      nbytes=8 * n)
+            else:
+                b.add(b.opt, L.jr_grad_accumulate, (G, A, n, int(ph == "flush"), s0), "grad_accumulate", 0,
+                      [("gacc",)], greads, nbytes=(8 if ph == "flush" else 12) * n)
+        # what runs once per update, and what runs once per micro-batch
+        updating, per_batch = ph in (None, "close", "flush"), ph != "flush"
+        if not updating:
+            pass        # the group stays open
+        elif self.opt_ex:
             # norm of the (reduced) raw gradient -> scale / skip of this step -> the
             # update reading lr, weight decay, scale and skip from device memory
             part, hy, st = self.opt_partials.data_ptr(), self.opt_hyper.data_ptr(), self.opt_step_dev.data_ptr()
@@ -1686,7 +1740,7 @@ class Engine(Replica):
                   self.optimizer + "_update_ex", 0, greads + [("gnorm",)], writes, nbytes=nbytes)
         else:   # (adam: apply_update binds the step's alpha in place of self.lr)
             b.add(b.opt, fn, self._by_value_args(self.lr, 1.0), self.optimizer, 0, greads, writes, nbytes=nbytes)
-        if self.ema is not None:
+        if self.ema is not None and updating:
             # the moving average of the updated weights, a pass of its own;
             # the device path hands it the step struct: a skipped step is neither averaged nor counted
             es, st = self.ema_state.data_ptr(), (self.opt_step_dev.data_ptr() if self.opt_ex else None)
@@ -1694,11 +1748,11 @@ class Engine(Replica):
             b.add(b.opt, L.jr_ema_prepare, (es, st, s0), "ema_prepare", 0, gn, [("ema",)])
             b.add(b.opt, L.jr_ema_update, (self.ema.data_ptr(), self.params.data_ptr(), n, es, st, s0), "ema_update", 0,
                   [("p",), ("ema",)] + gn, [("ema",)], nbytes=12 * n)
-        if self.bn_momentum is not None:
+        if self.bn_momentum is not None and per_batch:
             # the moving averages of this step's batch statistics (one launch; jr.h)
             b.add(b.opt, L.jr_bn_moving_update, self._bn_update_args(b.B, self.bn_momentum, s0), "bn_moving", 0,
                   [("r", u.first.idx) for u in self.cunits], [("bn_moving",)], nbytes=4 * 2 * self.stats_ms)
-        if b.training:
+        if b.training and per_batch:
             # the next step's mask: the counter counts enqueued steps, a skipped one included (jr.h)
             b.add(b.opt, L.jr_dropout_advance, (self.drop_state.data_ptr(), s0), "dropout_advance", 0, [], [("drop",)])
 
@@ -1784,27 +1838,40 @@ class Engine(Replica):
         skipped, total = (int(v) for v in raw[2:].view(torch.int32))
         return norm, scale, skipped, total
 
-    def apply_update(self, B: Optional[int] = None, grad_scale: float = 1.0, training: bool = False) -> None:
-        self._no_update_on_average("apply_update")
-        opt = self._build_calls(B or self.batch, training=training)[2]
+    def _bound(self, opt, grad_scale: float) -> list:
+        """An update list with this update's scalars: the device path writes them
+        ahead of it (_push_hyper); by value, the optimizer's call is rebound when
+        they differ from what the list holds (self.lr, 1.0)."""
         if self.opt_ex:
             # (a skipped step still counts as a step on the host: Adam's t and beta powers,
-            # and the BN moving averages and self.updates below, advance; only the device
+            # and the BN moving averages and self.updates, advance; only the device
             # write of weights and optimizer state is withheld -- jr.h)
             self._push_hyper(self._adam_alpha() if self.optimizer == "adam" else self.lr, grad_scale)
         elif grad_scale != 1.0 or self.optimizer == "adam":
             # (so Adam steps run eagerly: the scalar changes every step)
             lr = self._adam_alpha() if self.optimizer == "adam" else self.lr
-            opt = [dataclasses.replace(opt[0], args=self._by_value_args(lr, grad_scale))] + list(opt[1:])
-        self.lanes.run(opt)
+            i = next(j for j, c in enumerate(opt) if c.name == self.optimizer)
+            opt = list(opt)
+            opt[i] = dataclasses.replace(opt[i], args=self._by_value_args(lr, grad_scale))
+        return opt
+
+    def apply_update(self, B: Optional[int] = None, grad_scale: float = 1.0, training: bool = False) -> None:
+        self._no_update_on_average("apply_update")
+        opt = self._build_calls(B or self.batch, training=training)[2]
+        self.lanes.run(self._bound(opt, grad_scale))
         if self.bn_momentum is not None:
             self.updates += 1
 
     def train_step(self, B: Optional[int] = None, allreduce=None) -> None:
         """fwd + bwd (+ bucketed all-reduce) + optimizer, enqueued on the lanes;
-        everything is joined back onto self.stream before the optimizer."""
+        everything is joined back onto self.stream before the optimizer.
+        accum_steps = K > 1: the optimizer (and the all-reduce) run on every K-th
+        call only, on the group's gradient sum (_accum_step)."""
         B = B or self.batch
         self._no_update_on_average("train_step")
+        if self.accum_steps > 1:
+            self._accum_step(B, allreduce)
+            return
         if allreduce is None:
             self.forward(B, training=True)
             self.backward(B, training=True)
@@ -1816,6 +1883,78 @@ class Engine(Replica):
         scale = allreduce.finish(self)
         self.apply_update(B, grad_scale=scale, training=True)
 
+    # ---- gradient accumulation (accum_steps = K > 1)
+    def accum_pending(self) -> int:
+        """Micro-batches in the open group (0: the last train_step, replay or accum_flush closed one)."""
+        return self._pending
+
+    def _accum_phase(self) -> str:
+        k = self._pending
+        return "close" if k + 1 == self.accum_steps else "inside" if k else "open"
+
+    def _accum_step(self, B: int, allreduce) -> None:
+        """One micro-batch: forward and backward as ever; then the group's sum, and
+        on the closing one the exchange and the update with grad_scale 1 / (k *
+        world).  A micro-step that leaves the group open runs the backward
+        without the hook: nothing is exchanged.  Closing under data parallelism
+        runs the DEFAULT lists: BucketAllReduce folds `gacc` into each bucket on
+        its own stream just before it issues it (begin(fold=True))."""
+        k, ph = self._pending, self._accum_phase()
+        closing = ph == "close"
+        exchange = closing and allreduce is not None
+        fwd, bwd, opt, _, _ = self._build_calls(B, training=True, accum=None if exchange else ph)
+        self._frozen_fwd = None
+        ln = self.lanes
+        ln.fork()
+        ln.run(fwd)
+        ln.join()
+        scale = 1.0
+        if exchange:
+            allreduce.begin(self, fold=True)
+            ln.run(bwd, allreduce.param_ready)
+            ln.join()
+            scale = allreduce.finish(self)
+        else:
+            ln.run(bwd)
+            ln.join()
+        ln.run(self._bound(opt, scale / (k + 1)) if closing else opt)
+        if self.bn_momentum is not None:
+            self.updates += 1
+        self._pending = 0 if closing else k + 1
+
+    def _flush_calls(self) -> list:
+        """accum_flush's list: jr_grad_accumulate(g <- acc, first = 1), then what
+        runs once per update (the optimizer, the weight average) -- what runs
+        once per micro-batch already ran with each of them."""
+        key = ("accum", "flush")
+        if key not in self._calls:
+            b = Build(self.batch, self.lanes, 1, self.ws_lane, self.ws_bytes, {})
+            b.accum = "flush"
+            self._opt_update(b)
+            schedule(b.seq)
+            self._calls[key] = ([], [], b.opt, b.keep, None)
+        return self._calls[key][2]
+
+    def accum_flush(self, allreduce=None) -> bool:
+        """Close a partial group of k < K micro-batches (the end of an epoch):
+        g <- acc, the exchange (every bucket at once: no backward to overlap), the
+        update with grad_scale 1 / (k * world).  Nothing is pending: nothing
+        happens.  Returns whether an update ran.  Collective under data
+        parallelism: every rank holds the same k."""
+        self._no_update_on_average("accum_flush")
+        k = self._pending
+        if k == 0:
+            return False
+        opt = self._flush_calls()
+        self.lanes.run(opt[:1])
+        scale = 1.0
+        if allreduce is not None:
+            allreduce.begin(self)
+            scale = allreduce.finish(self)
+        self.lanes.run(self._bound(opt, scale / k)[1:])
+        self._pending = 0
+        return True
+
     def capture(self, B: Optional[int] = None) -> None:
         """Capture fwd+bwd+update for batch B into a HIP graph (single GPU;
         not for Adam, whose step scalar changes every step); the two lane
@@ -1823,41 +1962,52 @@ class Engine(Replica):
         branches of the graph, the producer waits its edges.  At most two
         lanes: on ROCm 7.2, cross-waits among three or more captured streams
         (waits on events recorded mid-stream) crashed hipGraphInstantiate
-        (DESIGN.md §3); more lanes run eagerly."""
+        (DESIGN.md §3); more lanes run eagerly.  accum_steps = K > 1: one graph
+        each for the micro-step that opens a group, one inside it (K > 2) and
+        the one that closes it, grad_scale 1 / K."""
         B = B or self.batch
         self._no_update_on_average("capture")
         if self.optimizer == "adam":
             raise ValueError("Adam steps run eagerly (the step's alpha is a host scalar)")
         if self.nlanes > 2:
             raise ValueError("HIP graph capture supports at most two lanes (more lanes run eagerly)")
-        fwd, bwd, opt, _, _ = self._build_calls(B, training=True)
-        if self.opt_ex:     # the graph reads the scalars: written ahead of it, never inside it
-            self._push_hyper(self.lr, 1.0)
-        torch.cuda.synchronize(self.device)
-        _ffi.check("jr_graph_begin", self.lib.jr_graph_begin(self._s))
-        ln = self.lanes
-        ln.capturing = not self.graph_precise
-        try:
-            ln.fork()
-            ln.run(fwd)
-            ln.join()
-            ln.run(bwd)
-            ln.join()
-            ln.run(opt)
-        finally:
-            ln.capturing = False
-            ex = ctypes.c_void_p()
-            _ffi.check("jr_graph_end", self.lib.jr_graph_end(self._s, ctypes.byref(ex)))
-        self._graphs[B] = ex.value
+        K = self.accum_steps
+        for ph in ([None] if K == 1 else ["open"] + ["inside"] * (K > 2) + ["close"]):
+            fwd, bwd, opt, _, _ = self._build_calls(B, training=True, accum=ph)
+            if ph in (None, "close"):
+                # the graph reads the device scalars: written ahead of it, never inside it
+                # (by value: the group's 1 / K is bound into the captured call)
+                opt = self._bound(opt, 1.0 / K)
+            torch.cuda.synchronize(self.device)
+            _ffi.check("jr_graph_begin", self.lib.jr_graph_begin(self._s))
+            ln = self.lanes
+            ln.capturing = not self.graph_precise
+            try:
+                ln.fork()
+                ln.run(fwd)
+                ln.join()
+                ln.run(bwd)
+                ln.join()
+                ln.run(opt)
+            finally:
+                ln.capturing = False
+                ex = ctypes.c_void_p()
+                _ffi.check("jr_graph_end", self.lib.jr_graph_end(self._s, ctypes.byref(ex)))
+            self._graphs[B if ph is None else (B, ph)] = ex.value
 
     def replay(self, B: Optional[int] = None) -> None:
         B = B or self.batch
         self._no_update_on_average("replay")
-        if self.opt_ex:     # a captured step is single-GPU: grad_scale 1, whatever an eager apply_update left
-            self._push_hyper(self.lr, 1.0)
-        _ffi.check("jr_graph_launch", self.lib.jr_graph_launch(ctypes.c_void_p(self._graphs[B]), self._s))
+        K = self.accum_steps
+        ph = self._accum_phase() if K > 1 else None     # (choosing the graph is the only host work)
+        if self.opt_ex:     # a captured step is single-GPU: grad_scale 1 / K, whatever an eager update left
+            self._push_hyper(self.lr, 1.0 / K)
+        _ffi.check("jr_graph_launch",
+                   self.lib.jr_graph_launch(ctypes.c_void_p(self._graphs[B if ph is None else (B, ph)]), self._s))
         if self.bn_momentum is not None:
             self.updates += 1
+        if K > 1:
+            self._pending = 0 if ph == "close" else self._pending + 1
 
     def synchronize(self) -> None:
         """Wait for every lane, then jr_device_check: a device-side failure

@@ -167,6 +167,9 @@ class Build:
         self.guard = None
         # the lists of a training step with dropout on (Engine._build_calls(training=True))
         self.training = False
+        # gradient accumulation (Engine(accum_steps=K > 1)): the update phase of a micro-batch that
+        # opens, continues ("inside") or closes its group, or of accum_flush; None: the default one
+        self.accum = None
 
     def add(self, lst, fn, args, name, lane, reads=(), writes=(), nbytes=0) -> None:
         c = Call(fn, args, name, lane, tuple(reads), tuple(writes), nbytes=int(nbytes))

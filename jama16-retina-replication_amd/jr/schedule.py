@@ -8,7 +8,7 @@ writes it to device memory ahead of the step (jr_opt_set_hyper).
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -40,3 +40,16 @@ def learning_rate(step: int, base: float, decay: Optional[Tuple[float, int]] = N
     if step + 1 < warmup:
         lr = f(lr * f(f(step + 1) / f(warmup)))
     return lr
+
+
+def accum_groups(batches: int, accum_steps: int) -> Tuple[List[int], int]:
+    """How an epoch of `batches` micro-batches falls into optimizer updates of
+    `accum_steps` micro-batches each: (the group sizes in order, their number).
+    Every group is full but the last, which holds the remainder and is closed
+    at the end of the epoch (Engine.accum_flush); the number of updates,
+    ceil(batches / accum_steps), is the epoch the schedule counts in."""
+    batches, k = int(batches), int(accum_steps)
+    if batches < 0 or k < 1:
+        raise ValueError("accum_groups: batches >= 0 and accum_steps >= 1")
+    sizes = [k] * (batches // k) + ([batches % k] if batches % k else [])
+    return sizes, len(sizes)

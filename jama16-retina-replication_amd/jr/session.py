@@ -98,5 +98,16 @@ class Session:
         B = self.engine.set_batch(images, labels, augment=augment, warp=warp)
         step = self.global_step
         self.engine.train_step(B, allreduce=getattr(self, "allreduce", None))
-        self.global_step += 1
+        # global_step counts optimizer updates: with Engine(accum_steps=K > 1) a batch that
+        # leaves its group open is no step (the loss and predictions are this batch's own)
+        if not getattr(self.engine, "accum_pending", int)():
+            self.global_step += 1
         return step, self.engine.loss_value(), self.engine.predictions(B)
+
+    def accum_flush(self) -> bool:
+        """Close a partial group of accumulated micro-batches (Engine.accum_flush;
+        the end of an epoch): one more step when anything was pending."""
+        flush = getattr(self.engine, "accum_flush", None)
+        done = bool(flush(allreduce=getattr(self, "allreduce", None))) if flush is not None else False
+        self.global_step += int(done)
+        return done

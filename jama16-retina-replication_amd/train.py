@@ -180,7 +180,38 @@ def build_parser():
                         "(0.2 in the published Inception-v3 recipe); a new mask every step, drawn on the GPU")
     p.add_argument("--dropout_seed", type=int, default=None, metavar="N",
                    help="seed of the dropout masks (default 0; rank r draws stream r of it; with --dropout)")
+    # gradient accumulation (not in the reference: off by default; jr.h jr_grad_accumulate)
+    p.add_argument("--accum_steps", type=_accum_arg, default=None, metavar="K",
+                   help="accumulate K batches of {0} per optimizer update ({0} * K images per GPU and update, every "
+                        "batch under its own BN statistics; default 1): --lr_decay epochs, --lr_warmup and the "
+                        "`Step:` of the status line then count updates, and a partial group at the end of an epoch "
+                        "is closed there".format(TRAIN_BATCH_SIZE))
     return p
+
+
+def _accum_arg(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected a count >= 1, got {text!r}")
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"expected a count >= 1, got {text!r}")
+    return v
+
+
+def accum_meta(args):
+    """What --accum_steps adds to the checkpoint .meta and to the Engine's keywords (nothing without it)."""
+    return {} if args.accum_steps is None else {"accum_steps": args.accum_steps}
+
+
+def accum_line(args, world, batches):
+    """The start-up line of --accum_steps (None without it); batches: per rank and epoch."""
+    if args.accum_steps is None:
+        return None
+    from jr.schedule import accum_groups
+    return ("Gradient accumulation: {0} batches of {1} per update, {2} images per update, {3} updates per epoch"
+            .format(args.accum_steps, TRAIN_BATCH_SIZE, TRAIN_BATCH_SIZE * args.accum_steps * world,
+                    accum_groups(batches, args.accum_steps)[1]))
 
 
 def _smoothing_arg(text):
@@ -474,7 +505,8 @@ Use SGD: {bool(args.vanilla_sgd)}
                     conv_math=args.conv_math if args.dtype == "f32" else "bf16",
                     tiles="pinned" if args.tiles == "pinned" else "heuristic",
                     **({} if args.bn_moving is None else {"bn_moving": args.bn_moving}), **opt_engine_kwargs(args),
-                    **ema_engine_kwargs(args), **loss_engine_kwargs(args, rank))
+                    **ema_engine_kwargs(args), **loss_engine_kwargs(args, rank),
+                    **accum_meta(args))
     table = None
     if args.tile_table:
         table = load_tile_table(args.tile_table)
@@ -507,6 +539,7 @@ Use SGD: {bool(args.vanilla_sgd)}
         run_meta["loss"] = loss_meta(args)
         if rank == 0:
             print(objective_line(args))
+    run_meta.update(accum_meta(args))
     # --weight_ema: validation, early stopping and the final sweep read the averaged weights
     import contextlib
     averaged = engine.averaged_weights if args.weight_ema is not None else contextlib.nullcontext
@@ -565,10 +598,27 @@ Use SGD: {bool(args.vanilla_sgd)}
     if dist:   # every rank runs the same number of steps (matching collectives)
         steps_per_epoch = -(-train_dataset.num_records() // TRAIN_BATCH_SIZE) // world
     # the schedule counts optimizer steps; an epoch of --lr_decay is this many of them
-    # (every rank computes the same value from the same integers: jr.schedule)
-    sched_epoch = -(-train_dataset.num_records() // TRAIN_BATCH_SIZE) // world if device_opt else None
-    if device_opt and args.max_steps_per_epoch is not None:
-        sched_epoch = min(sched_epoch, args.max_steps_per_epoch)
+    # (every rank computes the same value from the same integers: jr.schedule).  --accum_steps K:
+    # an update takes K batches (--max_steps_per_epoch still counts batches), ceil(batches / K) per epoch
+    sched_epoch = None
+    if device_opt or args.accum_steps is not None:
+        from jr.schedule import accum_groups
+        epoch_batches = -(-train_dataset.num_records() // TRAIN_BATCH_SIZE) // world
+        if args.max_steps_per_epoch is not None:
+            epoch_batches = min(epoch_batches, args.max_steps_per_epoch)
+        if device_opt:
+            sched_epoch = accum_groups(epoch_batches, args.accum_steps or 1)[1]
+        if rank == 0 and args.accum_steps is not None:
+            print(accum_line(args, world, epoch_batches))
+
+    def note_update():
+        """After an update: the device's norm, clip and skip of it (16 bytes, after a synchronise)."""
+        nonlocal clipped, skipped
+        norm, _, skip, _ = engine.opt_step()
+        norms.append(norm)
+        skipped += skip
+        # (the kernel's own decision: fp32 norm against fp32 clip_norm)
+        clipped += int(not skip and args.clip_norm is not None and np.float32(norm) > np.float32(args.clip_norm))
     for epoch in range(args.num_epochs):
         sess.reset("brier")
         batch_num = 0
@@ -593,19 +643,18 @@ Use SGD: {bool(args.vanilla_sgd)}
                                                              augment.draw(aug_spec, aug_rng, len(images)), warp)
                 else:
                     i_global, xent, probs = sess.train_batch(images, labels)
-                if device_opt:      # train_batch synchronised for the loss: 16 more bytes
-                    norm, _, skip, _ = engine.opt_step()
-                    norms.append(norm)
-                    skipped += skip
-                    # (the kernel's own decision: fp32 norm against fp32 clip_norm)
-                    clipped += int(not skip and args.clip_norm is not None
-                                   and np.float32(norm) > np.float32(args.clip_norm))
+                if device_opt and engine.accum_pending() == 0:      # (read after updates only)
+                    note_update()
                 sess.update(labels, probs, "brier")
                 if rank == 0:
                     print(status_line(epoch, args.num_epochs, batch_num, xent, i_global), end="\r")
                 batch_num += 1
         finally:
             lib.dataset.close_iterator(it)
+        # --accum_steps: a partial group is closed here, so validation, early stopping, checkpoints
+        # and the replica check never see an open one (every rank ran the same number of batches)
+        if sess.accum_flush() and device_opt:
+            note_update()
         sess.sync_metrics("brier")
         check_replicas(epoch)
         train_brier = sess.value("brier")
