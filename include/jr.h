@@ -896,8 +896,54 @@ int jr_image_u8_warp_augment_nhwc(const uint8_t* src, void* dst, int dtype, int3
                                   int32_t c, int32_t dst_stride, const jr_augment_param* params,
                                   const jr_warp_param* warps, void* ws, size_t ws_bytes, void* stream);
 /* acc[0] += sum (p - y)^2, acc[1] += n   (tf.metrics.mean_squared_error,
- * train.py:175-177) */
+ * train.py:175-177).  One block of 256 threads, in this order:
+ *   d_i = (double)p[i] - (double)y[i]        (fp32 widened exactly; one fp64 subtract)
+ *   q_i = d_i * d_i                          (one fp64 multiply, no FMA with the sum)
+ *   s_t = ((0.0 + q_t) + q_{t+256}) + ...    (thread t: i = t, t + 256, ..., ascending; fp64 adds)
+ *   r   = s;  for o = 128, 64, ..., 1:  r[t] = r[t] + r[t + o]  for every t < o
+ *   acc[0] = acc[0] + r[0];  acc[1] = acc[1] + (double)n           (fp64)
+ * Nothing runs in fp32.  n == 0 does nothing. */
 int jr_brier_accumulate(const float* probs, const float* labels, int32_t n, double* acc, void* stream);
+
+/* ---- streaming metrics and the step log in device memory ---------------
+ * (jr/engine.py metrics_* and step_log_*; tests/metrics_ref.py restates the
+ * three kernels in numpy).  All state is the caller's device memory; no call
+ * synchronises the host, none uses an atomic, and a launch binds nothing but
+ * pointers and element counts: every call may be captured into a graph.
+ *
+ * jr_metrics_accumulate: probs and labels are n fp32 values (batch * units,
+ * flattened); thr holds T fp32 thresholds; counts is uint32 [4][T], rows tp,
+ * fp, fn, tn; brier is double[2].  which bit 0: update counts; bit 1: update
+ * brier.  Per sample and threshold, positive iff p > thr[t] as an fp32
+ * comparison (a NaN p is negative), the label true iff y != 0 (0.5 and NaN
+ * true, -0.0 false).  One thread owns one threshold (ceil(T / 256) blocks of
+ * 256 threads), walks the samples through LDS in chunks of JR_METRICS_CHUNK
+ * and adds its four counts by a plain read, add and store: the result does
+ * not depend on the grid.  brier is jr_brier_accumulate(probs, labels, n,
+ * brier), bit for bit (one shared device function, run by block 0).
+ * JR_ERR_INVALID, before any HIP call: a null pointer that `which` needs
+ * (probs and labels always; thr and counts for bit 0; brier, 8-byte aligned,
+ * for bit 1), n <= 0, T outside 1..1024, which outside 1..3. */
+#define JR_METRICS_CHUNK 1024
+int jr_metrics_accumulate(const float* probs, const float* labels, int32_t n, const float* thr, int32_t T,
+                          uint32_t* counts, double* brier, int32_t which, void* stream);
+/* counts[0 .. 4 T) = 0 and brier[0 .. 2) = 0 in stream order (one memset node
+ * each: capturable, as jr_absmax_reset).  Either pointer may be NULL;
+ * JR_ERR_INVALID for counts with T outside 1..1024. */
+int jr_metrics_reset(uint32_t* counts, int32_t T, double* brier, void* stream);
+/* One record per training step, in a ring the host reads once in a while.
+ * One thread:
+ *   slot = *cursor % capacity
+ *   ring[slot] = { *loss, step ? step->grad_norm : 0, step ? step->scale : 0, flags }
+ *   *cursor += 1
+ * flags bit 0: an update ran (step != NULL); bit 1: step->skipped != 0.
+ * step: this step's jr_opt_step, or NULL -- the by-value optimizer path, and
+ * a micro-batch that leaves its accumulation group open.
+ * JR_ERR_INVALID: a null ring, cursor or loss, capacity == 0, a pointer that
+ * is not 4-byte aligned. */
+typedef struct jr_step_rec { float loss, grad_norm, scale; uint32_t flags; } jr_step_rec; /* DEVICE memory */
+int jr_step_log_append(jr_step_rec* ring, uint32_t capacity, uint32_t* cursor, const float* loss,
+                       const jr_opt_step* step, void* stream);
 
 /* ---- attribution: per-image input gradients under frozen BN ------------
  * (jr/attribution.py; not in the reference).  Every multiply and add named

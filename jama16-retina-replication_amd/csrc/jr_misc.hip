@@ -2,7 +2,8 @@
 //
 // NOTE: hipcc contracts a*b+c into an FMA by default (-ffp-contract=fast);
 // this file is compiled with -ffp-contract=off (Makefile): k_brier's fp64
-// s += d * d rounds the square and the sum each on its own.
+// s += d * d rounds the square and the sum each on its own (jr_brier.h).
+#include "jr_brier.h"
 #include "jr_common.h"
 
 namespace jr {
@@ -43,17 +44,8 @@ __global__ void k_image_u8(const uint8_t* __restrict__ s, T* d, int64_t pixels, 
 
 __global__ void k_brier(const float* __restrict__ p, const float* __restrict__ y, int n, double* acc) {
   __shared__ double red[256];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (int i = t; i < n; i += 256) {
-    const double d = (double)p[i] - (double)y[i];
-    s += d * d;
-  }
-  const double sum = block_sum256(s, red);
-  if (t == 0) {
-    acc[0] += sum;
-    acc[1] += (double)n;
-  }
+  const double sum = brier_sum256(p, y, n, red);
+  if (threadIdx.x == 0) brier_add(acc, sum, n);
 }
 
 }  // namespace jr

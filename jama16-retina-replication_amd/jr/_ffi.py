@@ -144,6 +144,14 @@ class DropoutState(Structure):
                 ("scale", c_float), ("pad", ctypes.c_uint32 * 3)]
 
 
+class StepRec(Structure):
+    """include/jr.h jr_step_rec: one record of the step log (jr_step_log_append writes them)."""
+    _fields_ = [("loss", c_float), ("grad_norm", c_float), ("scale", c_float), ("flags", ctypes.c_uint32)]
+
+
+METRICS_CHUNK = 1024    # include/jr.h JR_METRICS_CHUNK: samples per LDS chunk of jr_metrics_accumulate
+
+
 class PoolDesc(Structure):
     _fields_ = [(n, c_int32) for n in (
         "n", "h", "w", "c", "ho", "wo", "x_c_off", "x_c_stride", "y_c_off", "y_c_stride")]
@@ -318,6 +326,10 @@ _SIGS = {
     "jr_image_u8_warp_augment_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int32, c_int32, c_int32, c_int32, c_int32,
                                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "jr_brier_accumulate": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "jr_metrics_accumulate": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
+                                      c_void_p]),
+    "jr_metrics_reset": (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
+    "jr_step_log_append": (c_int, [c_void_p, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jr_crc32c": (ctypes.c_uint32, [c_void_p, c_size_t, ctypes.c_uint32]),
     "jr_masked_crc32c": (ctypes.c_uint32, [c_void_p, c_size_t]),
     "jr_tfrecord_index": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

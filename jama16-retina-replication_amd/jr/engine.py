@@ -39,6 +39,12 @@ that step, MI355X-native:
   one more flat buffer (acc <- g, then acc <- acc + g) instead of the
   optimizer; the closing one folds it back (g <- g + acc) ahead of today's
   update phase, whose grad_scale becomes 1 / (k * world).
+* Optional (metrics_init / step_log_enable / set_batch(staged=True); DESIGN.md
+  §15): the streaming metrics and a ring of per-step records live in device
+  memory (jr_metrics_accumulate, jr_step_log_append, enqueued on self.stream
+  BEHIND the step's call lists, never inside them), and uint8 batches arrive
+  through two pinned slots on a feed stream, so a loop needs the host only
+  once in a while.
 * Optional (input_grad=True): a third call list, the data-gradient chain of
   one logit per image down to the image after a frozen forward
   (input_gradient: jr_head_logit_bwd, jr_bn_relu_bwd_frozen, the data
@@ -661,6 +667,10 @@ class Engine(Replica):
         self._flush_points: List[int] = []
         self._graphs: Dict[object, int] = {}     # batch (accum_steps > 1: (batch, phase)) -> executable
         self.bucket_hooks: List[Tuple[int, Callable]] = []
+        # opt-in, nothing exists until asked for: the device metrics
+        # (metrics_init), the step log (step_log_enable), the staged input feed
+        # (set_batch(staged=True))
+        self._metrics, self._log, self._feed = None, None, None
         self._alloc()
         self.load_params(init_params(self.g, seed))
         self._choose_tiles("autotune" if autotune else tiles)
@@ -1764,18 +1774,113 @@ class Engine(Replica):
         self.lanes.fence(stream)
 
     # ------------------------------------------------------------------- data
-    def set_batch(self, images, labels=None, n: Optional[int] = None, augment=None, warp=None) -> int:
+    def set_batch(self, images, labels=None, n: Optional[int] = None, augment=None, warp=None,
+                  staged: bool = False) -> int:
         """Copy a batch (NHWC float32, or uint8 to be scaled by 1/255) into the
         input buffer.  Returns the batch size.  augment, warp: jr.augment
         tables (one jr_augment_param / jr_warp_param per image) -- the uint8
         batch then goes through jr_image_u8_augment_nhwc or, with a warp,
-        jr_image_u8_warp_augment_nhwc (None, None: no augmentation)."""
+        jr_image_u8_warp_augment_nhwc (None, None: no augmentation).
+        staged: a uint8 host batch goes through the two-slot pinned feed
+        (_upload_staged: the copy runs on a stream of its own and the host never
+        waits for the step it feeds); anything else takes the path above."""
         B = int(images.shape[0]) if n is None else n
         self._check_images(images, B)
         self._frozen_fwd = None
+        if staged and not isinstance(images, torch.Tensor) and np.asarray(images).dtype == np.uint8:
+            self._upload_staged(np.asarray(images), labels, B, augment, warp)
+            return B
         with torch.cuda.stream(self.stream):
             self._upload(images, labels, B, augment, warp)
         return B
+
+    # ---- the staged input feed (DESIGN.md §15)
+    def _feed_init(self) -> dict:
+        """Two slots, each one pinned host buffer and one device staging tensor
+        of the same layout: labels, the jr_augment_param and jr_warp_param
+        tables (sized for the planned batch, 256-byte aligned), then the uint8
+        pixels -- so one copy of the used prefix moves a whole batch."""
+        from . import augment as _augment
+        ib = self.g.bufs[self.g.input_buf]
+        al = lambda v: (v + 255) // 256 * 256   # noqa: E731
+        off_y = 0
+        off_a = al(4 * self.batch * self.units)
+        off_w = off_a + al(self.batch * _augment.PARAM_DTYPE.itemsize)
+        off_x = off_w + al(self.batch * _augment.WARP_DTYPE.itemsize)
+        nbytes = off_x + self.batch * ib.h * ib.w * ib.c
+        if self._aug_ws is None:    # the workspace of the augmenting kernels (the tables live in the slots)
+            self._aug_ws = torch.empty(int(self.lib.jr_augment_workspace_size(self.batch, ib.h, ib.w)),
+                                       dtype=torch.uint8, device=self.device)
+            self._aug_tab = torch.empty(self.batch * _augment.PARAM_DTYPE.itemsize, dtype=torch.uint8,
+                                        device=self.device)
+            self._warp_tab = torch.empty(self.batch * _augment.WARP_DTYPE.itemsize, dtype=torch.uint8,
+                                         device=self.device)
+        pin = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._feed = {
+            "off": (off_y, off_a, off_w, off_x),
+            "pin": pin, "host": [p.numpy() for p in pin],
+            "dev": [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)],
+            "stream": torch.cuda.Stream(device=self.device),
+            "copied": [torch.cuda.Event() for _ in range(2)],
+            # recorded on self.stream after the step that read the slot; waited for before its refill
+            "consumed": [torch.cuda.Event() for _ in range(2)],
+            "busy": [False, False], "last": None,
+        }
+        return self._feed
+
+    def _upload_staged(self, images: np.ndarray, labels, B: int, augment, warp) -> None:
+        """_upload for a uint8 host batch without a pageable copy and without a
+        host wait for the step it feeds: fill the free slot's pinned buffer,
+        one copy on the feed stream, self.stream waits for that copy's event,
+        then the unchanged conversion kernel (and the label copy) on
+        self.stream.  A slot is refilled only after the event recorded behind
+        the step that consumed it: at most two steps are in flight."""
+        from . import augment as _augment
+        f = self._feed or self._feed_init()
+        ib = self.g.bufs[self.g.input_buf]
+        if f["last"] is not None:   # what was enqueued since the last staged batch consumed its slot
+            f["consumed"][f["last"]].record(self.stream)
+            f["busy"][f["last"]] = True
+        s = 0 if f["last"] is None else 1 - f["last"]
+        if f["busy"][s]:
+            f["consumed"][s].synchronize()
+            f["busy"][s] = False
+        off_y, off_a, off_w, off_x = f["off"]
+        host, dev = f["host"][s], f["dev"][s]
+        npx = B * ib.h * ib.w * ib.c
+        host[off_x:off_x + npx] = images.reshape(-1)
+        if labels is not None:
+            y = np.asarray(labels, np.float32).reshape(-1)
+            if y.size != B * self.units:
+                raise ValueError("labels must have batch*units elements")
+            host[off_y:off_y + 4 * y.size] = y.view(np.uint8)
+        tab = wtab = None
+        if augment is not None or warp is not None:
+            tab = _augment.identity(B) if augment is None else _augment.as_table(augment, B)
+            host[off_a:off_a + tab.nbytes] = np.ascontiguousarray(tab).view(np.uint8).reshape(-1)
+            if warp is not None:
+                wtab = _augment.as_warp_table(warp, B)
+                host[off_w:off_w + wtab.nbytes] = np.ascontiguousarray(wtab).view(np.uint8).reshape(-1)
+        with torch.cuda.stream(f["stream"]):
+            dev[:off_x + npx].copy_(f["pin"][s][:off_x + npx], non_blocking=True)
+        f["copied"][s].record(f["stream"])
+        self.stream.wait_event(f["copied"][s])
+        dst, base = self.acts[self.g.input_buf], dev.data_ptr()
+        if tab is None:
+            _ffi.check("jr_image_u8_to_nhwc", self.lib.jr_image_u8_to_nhwc(
+                base + off_x, dst.data_ptr(), self.dt, B * ib.h * ib.w, ib.c, self.in_stride, self._s))
+        elif wtab is None:
+            _ffi.check("jr_image_u8_augment_nhwc", self.lib.jr_image_u8_augment_nhwc(
+                base + off_x, dst.data_ptr(), self.dt, B, ib.h, ib.w, ib.c, self.in_stride,
+                base + off_a, self._aug_ws.data_ptr(), self._aug_ws.numel(), self._s))
+        else:
+            _ffi.check("jr_image_u8_warp_augment_nhwc", self.lib.jr_image_u8_warp_augment_nhwc(
+                base + off_x, dst.data_ptr(), self.dt, B, ib.h, ib.w, ib.c, self.in_stride,
+                base + off_a, base + off_w, self._aug_ws.data_ptr(), self._aug_ws.numel(), self._s))
+        if labels is not None:
+            with torch.cuda.stream(self.stream):
+                self.labels[:B * self.units].copy_(dev[off_y:off_y + 4 * B * self.units].view(torch.float32))
+        f["last"] = s
 
     # ------------------------------------------------------------------- runs
     def forward(self, B: Optional[int] = None, bn: str = "batch", training: bool = False) -> None:
@@ -1876,12 +1981,14 @@ class Engine(Replica):
             self.forward(B, training=True)
             self.backward(B, training=True)
             self.apply_update(B, training=True)
+            self._log_append(True)
             return
         self.forward(B, training=True)
         allreduce.begin(self)
         self.backward(B, hook=allreduce.param_ready, training=True)
         scale = allreduce.finish(self)
         self.apply_update(B, grad_scale=scale, training=True)
+        self._log_append(True)
 
     # ---- gradient accumulation (accum_steps = K > 1)
     def accum_pending(self) -> int:
@@ -1921,6 +2028,7 @@ class Engine(Replica):
         if self.bn_momentum is not None:
             self.updates += 1
         self._pending = 0 if closing else k + 1
+        self._log_append(closing)
 
     def _flush_calls(self) -> list:
         """accum_flush's list: jr_grad_accumulate(g <- acc, first = 1), then what
@@ -1953,7 +2061,87 @@ class Engine(Replica):
             scale = allreduce.finish(self)
         self.lanes.run(self._bound(opt, scale / k)[1:])
         self._pending = 0
+        self._log_append(True)      # (the loss is the last micro-batch's: no forward ran here)
         return True
+
+    # ---- device metrics (jr.h jr_metrics_*)
+    def metrics_init(self, thresholds) -> None:
+        """Device state of the streaming metrics: the fp32 threshold table, the
+        uint32 [4][T] counts (tp, fp, fn, tn) and the Brier double[2], zeroed."""
+        thr = np.ascontiguousarray(np.asarray(thresholds, np.float32).reshape(-1))
+        if not 1 <= thr.size <= 1024:
+            raise ValueError("metrics_init: 1..1024 thresholds")
+        self._metrics = {"T": int(thr.size), "thr": self._after_fill(torch.from_numpy(thr).to(self.device)),
+                         "counts": self._t(4 * thr.size, torch.int32), "brier": self._t(2, torch.float64)}
+
+    def _need_metrics(self) -> dict:
+        if self._metrics is None:
+            raise ValueError("the device metrics are off: call metrics_init(thresholds) first")
+        return self._metrics
+
+    def metrics_update(self, B: Optional[int] = None, counts: bool = True, brier: bool = True) -> None:
+        """Enqueue jr_metrics_accumulate over the probabilities and labels of the
+        forward (or step) enqueued last, on self.stream behind it: no host wait."""
+        m, which = self._need_metrics(), int(bool(counts)) | 2 * int(bool(brier))
+        if not which:
+            return
+        _ffi.check("jr_metrics_accumulate", self.lib.jr_metrics_accumulate(
+            self.probs.data_ptr(), self.labels.data_ptr(), (B or self.batch) * self.units, m["thr"].data_ptr(), m["T"],
+            m["counts"].data_ptr(), m["brier"].data_ptr(), which, self._s))
+
+    def metrics_reset(self) -> None:
+        m = self._need_metrics()
+        _ffi.check("jr_metrics_reset", self.lib.jr_metrics_reset(m["counts"].data_ptr(), m["T"], m["brier"].data_ptr(),
+                                                                 self._s))
+
+    def metrics_read(self) -> Tuple[np.ndarray, float, float]:
+        """(uint32 [4, T] counts, the Brier sum, the sample count) after a synchronise."""
+        m = self._need_metrics()
+        self.synchronize()
+        counts = m["counts"].cpu().numpy().view(np.uint32).reshape(4, m["T"])
+        s, n = (float(v) for v in m["brier"].cpu().numpy())
+        return counts, s, n
+
+    # ---- the step log (jr.h jr_step_log_append; DESIGN.md §15)
+    STEP_REC = np.dtype([("loss", "<f4"), ("grad_norm", "<f4"), ("scale", "<f4"), ("flags", "<u4")])
+
+    def step_log_enable(self, capacity: int) -> None:
+        """From here on train_step (each micro-batch of an accumulation group) and
+        accum_flush append one jr_step_rec to a device ring of `capacity` records:
+        the loss, and on the device optimizer path the update's grad_norm, scale
+        and skip flag.  step_log_read() fetches them.  A device failure
+        (jr_device_check) of a logged step shows at the next synchronise, up to
+        `capacity` steps late."""
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("step_log_enable: capacity >= 1")
+        self._log = {"cap": capacity, "ring": self._t(4 * capacity, torch.int32), "cursor": self._t(1, torch.int32),
+                     "appended": 0, "read": 0}
+
+    def _log_append(self, updated: bool) -> None:
+        lg = self._log
+        if lg is None:
+            return
+        if lg["appended"] - lg["read"] >= lg["cap"]:
+            raise RuntimeError(f"step log full: {lg['cap']} records unread (call step_log_read() at least every "
+                               f"{lg['cap']} steps, or enable a larger ring)")
+        step = self.opt_step_dev.data_ptr() if (self.opt_ex and updated) else None
+        _ffi.check("jr_step_log_append", self.lib.jr_step_log_append(
+            lg["ring"].data_ptr(), lg["cap"], lg["cursor"].data_ptr(), self.loss.data_ptr(), step, self._s))
+        lg["appended"] += 1
+
+    def step_log_read(self) -> np.ndarray:
+        """The records appended since the last read, oldest first, as a STEP_REC
+        array (flags bit 0: an update ran and grad_norm / scale are its own; bit 1:
+        the non-finite guard skipped it).  One synchronise."""
+        lg = self._log
+        if lg is None:
+            raise ValueError("the step log is off: call step_log_enable(capacity) first")
+        self.synchronize()
+        ring = lg["ring"].cpu().numpy().view(self.STEP_REC)
+        idx = np.arange(lg["read"], lg["appended"]) % lg["cap"]
+        lg["read"] = lg["appended"]
+        return ring[idx].copy()
 
     def capture(self, B: Optional[int] = None) -> None:
         """Capture fwd+bwd+update for batch B into a HIP graph (single GPU;
@@ -2012,7 +2200,11 @@ class Engine(Replica):
     def synchronize(self) -> None:
         """Wait for every lane, then jr_device_check: a device-side failure
         of any launch since the last check (a stream-K hand-off count word not
-        left zero) raises JRError here instead of leaving wrong numbers."""
+        left zero) raises JRError here instead of leaving wrong numbers.
+        A loop that runs ahead (device metrics, the step log, the staged feed)
+        synchronises once in N steps, so a failure is reported up to N steps
+        late -- but always before anything read after a synchronise is used:
+        metrics_read, step_log_read, params_numpy (a checkpoint) all end here."""
         for st in self.lane_streams:
             st.synchronize()
         _ffi.device_check()

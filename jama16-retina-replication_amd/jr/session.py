@@ -16,7 +16,8 @@ from lib import metrics as M
 
 
 class Session:
-    def __init__(self, engine, thresholds=None, num_thresholds: int = 200, kepsilon: float = 1e-7):
+    def __init__(self, engine, thresholds=None, num_thresholds: int = 200, kepsilon: float = 1e-7,
+                 device_metrics: bool = False):
         self.engine = engine
         if thresholds is None:
             thresholds = M.generate_thresholds(num_thresholds, kepsilon) + [0.5]
@@ -32,6 +33,13 @@ class Session:
             "auc": M.create_reset_metric(M.auc, scope="auc"),
         }
         self.global_step = 0
+        # device_metrics: the streaming states live on the GPU while a pass runs (Engine.metrics_*:
+        # this session's thresholds followed by the auc state's own), batches arrive through the
+        # engine's staged feed, and train_batch / predict_enqueue return without waiting;
+        # pull_metrics() brings the sums into the host states above once per pass
+        self.device_metrics = bool(device_metrics)
+        if self.device_metrics:
+            engine.metrics_init(self.thresholds + list(self.metrics["auc"][0].__self__.thresholds))
         # data-parallel ranks: reduce(vec float64) -> elementwise sum over ranks;
         # rank: only rank 0 prints the reference's per-pass lines
         self.reduce = None
@@ -95,6 +103,8 @@ class Session:
     def train_batch(self, images, labels, augment=None, warp=None) -> tuple:
         """train.py:231-232: one step; returns (global_step, xent, probs).
         augment, warp: jr.augment tables for this (uint8) batch, or None."""
+        if self.device_metrics:
+            return self._train_enqueue(images, labels, augment, warp)
         B = self.engine.set_batch(images, labels, augment=augment, warp=warp)
         step = self.global_step
         self.engine.train_step(B, allreduce=getattr(self, "allreduce", None))
@@ -111,3 +121,53 @@ class Session:
         done = bool(flush(allreduce=getattr(self, "allreduce", None))) if flush is not None else False
         self.global_step += int(done)
         return done
+
+    # ---------------------------------------------- device metrics (opt-in)
+    def _train_enqueue(self, images, labels, augment, warp) -> tuple:
+        """train_batch with device_metrics: the staged feed, the step, the Brier
+        sums of its probabilities -- all enqueued, nothing waited for.  The loss
+        is in the engine's step log (Engine.step_log_enable), the probabilities
+        stay on the device: (global_step, None, None)."""
+        B = self.engine.set_batch(images, labels, augment=augment, warp=warp, staged=True)
+        step = self.global_step
+        self.engine.train_step(B, allreduce=getattr(self, "allreduce", None))
+        self.engine.metrics_update(B, counts=False, brier=True)
+        if not self.engine.accum_pending():
+            self.global_step += 1
+        return step, None, None
+
+    def predict_enqueue(self, images, labels) -> None:
+        """predict() without the wait: the forward, then the counts and the Brier
+        sums of its probabilities against `labels` on the device."""
+        self._need_device_metrics()
+        B = self.engine.set_batch(images, labels, staged=True)
+        self.engine.forward(B)
+        self.engine.metrics_update(B, counts=True, brier=True)
+
+    def metrics_reset(self) -> None:
+        """Zero the device counts and Brier sums (in stream order)."""
+        self._need_device_metrics()
+        self.engine.metrics_reset()
+
+    def pull_metrics(self, *names) -> None:
+        """Read the device state (one synchronise) into the lib.metrics states of
+        `names` (all six when none is given): `acc` of tp / fp / fn / tn and of
+        auc from the counts, `total` and `count` of brier from the sums -- each
+        rounded to float32 once, where the host path adds float32 batch by batch.
+        value(), sync_metrics(), confusion_matrix(), specificities() then work
+        as after a host pass."""
+        self._need_device_metrics()
+        counts, total, n = self.engine.metrics_read()
+        T = len(self.thresholds)
+        for name in names or self.metrics:
+            state = self.metrics[name][0].__self__
+            if name == "brier":
+                state.total, state.count = np.float32(total), np.float32(n)
+            elif name == "auc":
+                state.acc = counts[:, T:].astype(np.float32)
+            else:
+                state.acc = counts[state.ROW, :T].astype(np.float32)
+
+    def _need_device_metrics(self) -> None:
+        if not self.device_metrics:
+            raise ValueError("this session keeps its metrics on the host: Session(..., device_metrics=True)")

@@ -13,7 +13,10 @@ keeps its arguments and outputs:
   * feed_dict_fn(**feed_dict_args), if given, supplies each batch as
     {"x": images, "y": labels} (evaluate.py:114-118 feed_images); raising
     StopIteration ends the pass (the OutOfRangeError of the reference).
-`sess` is a jr.session.Session (engine + metric states).
+`sess` is a jr.session.Session (engine + metric states).  With
+Session(device_metrics=True) the default path keeps the streaming states on
+the GPU for the pass (predict_enqueue per batch, one pull_metrics at the end);
+custom_tensors always take the host path.
 """
 from __future__ import annotations
 
@@ -37,8 +40,17 @@ def perform_test(sess, init_op, summary_writer=None, epoch=None,
     if len(custom_tensors) == 0:
         sess.reset("tp", "fp", "fn", "tn", "brier", "auc")
 
+    # a session that keeps its metrics on the device (Session(device_metrics=True)): every
+    # batch is enqueued, the sums come back once, and the report below reads them as ever
+    on_device = len(custom_tensors) == 0 and getattr(sess, "device_metrics", False)
+    if on_device:
+        sess.metrics_reset()
+        for images, labels in _batches(init_op, feed_dict_fn, feed_dict_args):
+            sess.predict_enqueue(images, labels)
+        sess.pull_metrics("tp", "fp", "fn", "tn", "brier", "auc")
+
     batch_results = []
-    for images, labels in _batches(init_op, feed_dict_fn, feed_dict_args):
+    for images, labels in ([] if on_device else _batches(init_op, feed_dict_fn, feed_dict_args)):
         probs = sess.predict(images, labels)
         if len(custom_tensors) == 0:
             sess.update(labels, probs, "tp", "fp", "fn", "tn", "brier", "auc")

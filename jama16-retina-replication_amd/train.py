@@ -186,7 +186,21 @@ def build_parser():
                         "batch under its own BN statistics; default 1): --lr_decay epochs, --lr_warmup and the "
                         "`Step:` of the status line then count updates, and a partial group at the end of an epoch "
                         "is closed there".format(TRAIN_BATCH_SIZE))
+    p.add_argument("--status_every", type=_status_arg, default=1, metavar="N",
+                   help="print the status line every N batches (default 1: after every batch, which waits for "
+                        "it).  N > 1 keeps the loss, the gradient norm and the Brier and threshold counts of "
+                        "training, validation and the final sweep on the GPU, feeds batches through pinned "
+                        "staging buffers and reads the step log once per N batches, so the GPU is not left idle "
+                        "once per step; the end-of-epoch lines, summaries, checkpoints and the operating-point "
+                        "CSV keep their meaning")
     return p
+
+
+def _status_arg(text):
+    n = int(text)
+    if n < 1:
+        raise argparse.ArgumentTypeError("--status_every: a whole number of batches >= 1")
+    return n
 
 
 def _accum_arg(text):
@@ -519,8 +533,13 @@ Use SGD: {bool(args.vanilla_sgd)}
         table = box[0]
     if table is not None:
         engine.set_tile_table(table)
-    sess = Session(engine, thresholds, NUM_THRESHOLDS, KEPSILON)
+    # --status_every N > 1: the loop that runs ahead of the host (jr.session device_metrics, the
+    # engine's step log with room for N batches and the flush of a partial accumulation group)
+    run_ahead = args.status_every > 1
+    sess = Session(engine, thresholds, NUM_THRESHOLDS, KEPSILON, **({"device_metrics": True} if run_ahead else {}))
     sess.rank = rank
+    if run_ahead:
+        engine.step_log_enable(args.status_every + 1)
     # one parameter table per training batch, each rank from its own stream
     aug_spec = augment_spec(args)
     aug_rng = np.random.Generator(np.random.PCG64([args.augment_seed, rank])) if aug_spec else None
@@ -540,6 +559,8 @@ Use SGD: {bool(args.vanilla_sgd)}
         if rank == 0:
             print(objective_line(args))
     run_meta.update(accum_meta(args))
+    if run_ahead:
+        run_meta["status_every"] = args.status_every
     # --weight_ema: validation, early stopping and the final sweep read the averaged weights
     import contextlib
     averaged = engine.averaged_weights if args.weight_ema is not None else contextlib.nullcontext
@@ -611,16 +632,31 @@ Use SGD: {bool(args.vanilla_sgd)}
         if rank == 0 and args.accum_steps is not None:
             print(accum_line(args, world, epoch_batches))
 
-    def note_update():
-        """After an update: the device's norm, clip and skip of it (16 bytes, after a synchronise)."""
+    def note_update(rec=None):
+        """After an update: the device's norm, clip and skip of it (16 bytes, after a synchronise;
+        --status_every N > 1: the step log's record of it)."""
         nonlocal clipped, skipped
-        norm, _, skip, _ = engine.opt_step()
+        if rec is None:
+            norm, _, skip, _ = engine.opt_step()
+        else:
+            norm, skip = float(rec["grad_norm"]), int(rec["flags"]) >> 1 & 1
         norms.append(norm)
         skipped += skip
         # (the kernel's own decision: fp32 norm against fp32 clip_norm)
         clipped += int(not skip and args.clip_norm is not None and np.float32(norm) > np.float32(args.clip_norm))
+
+    def drain_log():
+        """--status_every N > 1: the records since the last read (one synchronise); the updates among
+        them are noted as the default loop notes them.  Returns the newest record's loss."""
+        recs = engine.step_log_read()
+        if device_opt:
+            for rec in recs[(recs["flags"] & 1) != 0]:
+                note_update(rec)
+        return float(recs["loss"][-1]) if len(recs) else None
     for epoch in range(args.num_epochs):
         sess.reset("brier")
+        if run_ahead:
+            sess.metrics_reset()
         batch_num = 0
         step_lr, norms, clipped, skipped = None, [], 0, 0
         it = iter(train_dataset)
@@ -643,6 +679,14 @@ Use SGD: {bool(args.vanilla_sgd)}
                                                              augment.draw(aug_spec, aug_rng, len(images)), warp)
                 else:
                     i_global, xent, probs = sess.train_batch(images, labels)
+                if run_ahead:
+                    # nothing of this batch is on the host yet: every N-th batch reads the log
+                    if batch_num % args.status_every == args.status_every - 1:
+                        xent = drain_log()
+                        if rank == 0:
+                            print(status_line(epoch, args.num_epochs, batch_num, xent, i_global), end="\r")
+                    batch_num += 1
+                    continue
                 if device_opt and engine.accum_pending() == 0:      # (read after updates only)
                     note_update()
                 sess.update(labels, probs, "brier")
@@ -653,7 +697,11 @@ Use SGD: {bool(args.vanilla_sgd)}
             lib.dataset.close_iterator(it)
         # --accum_steps: a partial group is closed here, so validation, early stopping, checkpoints
         # and the replica check never see an open one (every rank ran the same number of batches)
-        if sess.accum_flush() and device_opt:
+        if run_ahead:
+            sess.accum_flush()
+            drain_log()
+            sess.pull_metrics("brier")
+        elif sess.accum_flush() and device_opt:
             note_update()
         sess.sync_metrics("brier")
         check_replicas(epoch)
@@ -704,12 +752,19 @@ Use SGD: {bool(args.vanilla_sgd)}
             if ema is not None:
                 engine.load_ema(ema[0], ema[1]["updates"])
     sess.reset("tp", "fp", "fn", "tn")
+    if run_ahead:
+        sess.metrics_reset()
     it = iter(train_dataset)
     try:
         with averaged():
             for images, labels in it:
+                if run_ahead:
+                    sess.predict_enqueue(images, labels)
+                    continue
                 probs = sess.predict(images, labels)
                 sess.update(labels, probs, "tp", "fp", "fn", "tn")
+            if run_ahead:
+                sess.pull_metrics("tp", "fp", "fn", "tn")
     finally:
         lib.dataset.close_iterator(it)
     sess.sync_metrics("tp", "fp", "fn", "tn")
