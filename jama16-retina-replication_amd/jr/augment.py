@@ -134,6 +134,14 @@ def as_warp_table(warp, n: int) -> np.ndarray:
     return a
 
 
+def batch_tables(n: int, augment=None, warp=None) -> tuple:
+    """(colour table, warp table or None) of a batch of n as an upload takes them, validated;
+    (None, None) without either.  A warp alone goes with the identity colour table."""
+    if augment is None and warp is None:
+        return None, None
+    return identity(n) if augment is None else as_table(augment, n), None if warp is None else as_warp_table(warp, n)
+
+
 def warp_matrix(h: int, w: int, degrees: float = 0.0, zoom: float = 1.0, dx: float = 0.0, dy: float = 0.0) -> np.ndarray:
     """float32[6] matrix of a rotation by `degrees` and a magnification by
     `zoom` about the image centre c = ((w-1)/2, (h-1)/2), the content then

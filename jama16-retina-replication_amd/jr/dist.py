@@ -207,7 +207,7 @@ class BucketAllReduce:
         self._tev: List[Tuple[str, object]] = []
 
     def begin(self, eng=None, fold: bool = False) -> None:
-        """fold: the step closes a group of accumulated micro-batches (Engine._accum_step)."""
+        """fold: the step closes a group of accumulated micro-batches (Engine.train_step)."""
         self.fold = bool(fold)
         self.works = []
         self.next = 0

@@ -16,7 +16,10 @@ that step, MI355X-native:
   own BN, beta and output slice.
 * Calls are pre-bound (ctypes function + argument tuple) into call lists, so a
   step is a flat loop of C calls on one HIP stream, and the whole step can be
-  captured into a HIP graph (jr_graph_*) and replayed.
+  captured into a HIP graph (jr_graph_*) and replayed.  One routine enqueues
+  a step's lists in order (Engine._enqueue_step, its tail _finish_update) for
+  train_step, every micro-batch of an accumulation group and capture; one
+  settles the host's books after it (Engine._settle).
 * Optional (bn_moving=momentum): one more launch per step keeps Keras-style
   moving averages of every BN layer's batch statistics (jr_bn_moving_update);
   freeze_bn() + forward(bn="frozen") then normalise with fixed statistics, so
@@ -44,7 +47,8 @@ that step, MI355X-native:
   memory (jr_metrics_accumulate, jr_step_log_append, enqueued on self.stream
   BEHIND the step's call lists, never inside them), and uint8 batches arrive
   through two pinned slots on a feed stream, so a loop needs the host only
-  once in a while.
+  once in a while (their state: jr.runahead; staged or not, one routine
+  launches the conversion kernel: Replica._u8_to_input).
 * Optional (input_grad=True): a third call list, the data-gradient chain of
   one logit per image down to the image after a frozen forward
   (input_gradient: jr_head_logit_bwd, jr_bn_relu_bwd_frozen, the data
@@ -70,10 +74,12 @@ import numpy as np
 import torch
 
 from . import _ffi
+from . import augment as _augment
 from .inception import BN_EPS, Graph, PoolNode, build_inception_v3
 from .init import init_params
 from .lanes import Build, Call, Lanes, node_lanes, schedule
 from .plan import ConvUnit, bn_batch_groups, bn_moving_segments, build_plan, decay_ranges
+from .runahead import STEP_REC, Feed, Metrics, StepLog
 
 DTYPES = {"f32": _ffi.JR_F32, "bf16": _ffi.JR_BF16}
 
@@ -320,54 +326,61 @@ class Replica:
         """A batch (NHWC float32, or uint8 to be scaled by 1/255; a host array
         or a device tensor) into the first member's input buffer and the
         labels, on self.stream.  augment / warp: jr.augment tables (one
-        jr_augment_param / jr_warp_param per image) for a uint8 batch --
-        augment alone goes through jr_image_u8_augment_nhwc, a warp through
-        jr_image_u8_warp_augment_nhwc (with the identity colour table when
-        augment is None)."""
+        jr_augment_param / jr_warp_param per image) for a uint8 batch, which
+        _u8_to_input converts from this upload's own device copies."""
         ib = self.g.bufs[self.g.input_buf]
-        x, pixels, dst = torch.as_tensor(images), B * ib.h * ib.w, self.acts[self.g.input_buf]
-        if augment is not None or warp is not None:
-            if x.dtype != torch.uint8:
-                raise ValueError("augment / warp need a uint8 batch (float batches are not augmented)")
-            from . import augment as _augment
-            tab = _augment.identity(B) if augment is None else _augment.as_table(augment, B)
-            wtab = None if warp is None else _augment.as_warp_table(warp, B)
-            if self._aug_ws is None:   # once: sized for the planned batch
-                nbytes = int(self.lib.jr_augment_workspace_size(self.batch, ib.h, ib.w))
-                self._aug_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                self._aug_tab = torch.empty(self.batch * tab.dtype.itemsize, dtype=torch.uint8, device=self.device)
-                self._warp_tab = torch.empty(self.batch * _augment.WARP_DTYPE.itemsize, dtype=torch.uint8,
-                                             device=self.device)
-            self._aug_tab[:tab.nbytes].copy_(torch.from_numpy(tab.view(np.uint8)), non_blocking=True)
+        x, pixels = torch.as_tensor(images), B * ib.h * ib.w
+        tab, wtab = _augment.batch_tables(B, augment, warp)
+        if x.dtype == torch.uint8:
+            if tab is not None:     # device copies of the host tables
+                self._aug_buffers()
+                self._aug_tab[:tab.nbytes].copy_(torch.from_numpy(tab.view(np.uint8)), non_blocking=True)
+                if wtab is not None:
+                    self._warp_tab[:wtab.nbytes].copy_(torch.from_numpy(wtab.view(np.uint8)), non_blocking=True)
             xd = x.to(self.device, non_blocking=True).reshape(-1)
-            if wtab is None:
-                _ffi.check("jr_image_u8_augment_nhwc", self.lib.jr_image_u8_augment_nhwc(
-                    xd.data_ptr(), dst.data_ptr(), self.dt, B, ib.h, ib.w, ib.c, self.in_stride,
-                    self._aug_tab.data_ptr(), self._aug_ws.data_ptr(), self._aug_ws.numel(), self._s))
-            else:
-                self._warp_tab[:wtab.nbytes].copy_(torch.from_numpy(wtab.view(np.uint8)), non_blocking=True)
-                _ffi.check("jr_image_u8_warp_augment_nhwc", self.lib.jr_image_u8_warp_augment_nhwc(
-                    xd.data_ptr(), dst.data_ptr(), self.dt, B, ib.h, ib.w, ib.c, self.in_stride,
-                    self._aug_tab.data_ptr(), self._warp_tab.data_ptr(), self._aug_ws.data_ptr(),
-                    self._aug_ws.numel(), self._s))
+            self._u8_to_input(xd.data_ptr(), B, None if tab is None else self._aug_tab.data_ptr(),
+                              None if wtab is None else self._warp_tab.data_ptr())
             self._keep_u8 = xd
-        elif x.dtype == torch.uint8:
-            xd = x.to(self.device, non_blocking=True).reshape(-1)
-            _ffi.check("jr_image_u8_to_nhwc", self.lib.jr_image_u8_to_nhwc(
-                xd.data_ptr(), dst.data_ptr(), self.dt, pixels, ib.c, self.in_stride, self._s))
-            self._keep_u8 = xd
+        elif tab is not None:
+            raise ValueError("augment / warp need a uint8 batch (float batches are not augmented)")
         else:
-            v = dst[:pixels * self.in_stride].view(pixels, self.in_stride)
+            v = self.acts[self.g.input_buf][:pixels * self.in_stride].view(pixels, self.in_stride)
             v[:, ib.c:].zero_()
             v[:, :ib.c].copy_(x.to(torch.float32).reshape(pixels, ib.c).to(self.device, non_blocking=True))
-        self._set_labels(labels, B)
-
-    def _set_labels(self, labels, B: int) -> None:
         if labels is not None:
             y = torch.as_tensor(labels, dtype=torch.float32).reshape(-1)
-            if y.numel() != B * self.units:
-                raise ValueError("labels must have batch*units elements")
+            self._check_labels(y, B)
             self.labels[:y.numel()].copy_(y, non_blocking=True)
+
+    def _aug_buffers(self) -> torch.Tensor:
+        """The augmenting kernels' workspace (returned) and _upload's device tables: at first use, for
+        the planned batch."""
+        if self._aug_ws is None:
+            ib = self.g.bufs[self.g.input_buf]
+            self._aug_ws, self._aug_tab, self._warp_tab = (
+                torch.empty(int(n), dtype=torch.uint8, device=self.device)
+                for n in (self.lib.jr_augment_workspace_size(self.batch, ib.h, ib.w),
+                          self.batch * _augment.PARAM_DTYPE.itemsize, self.batch * _augment.WARP_DTYPE.itemsize))
+        return self._aug_ws
+
+    def _u8_to_input(self, x: int, B: int, tab: Optional[int] = None, wtab: Optional[int] = None) -> None:
+        """uint8 pixels at device address x -> the first member's input buffer (times 1/255), on
+        self.stream: plain, through the colour table at device address tab, or the warp table at wtab too."""
+        ib, dst = self.g.bufs[self.g.input_buf], self.acts[self.g.input_buf].data_ptr()
+        if tab is None:
+            name, args = "jr_image_u8_to_nhwc", (x, dst, self.dt, B * ib.h * ib.w, ib.c, self.in_stride)
+        else:
+            ws = self._aug_buffers()
+            args = (x, dst, self.dt, B, ib.h, ib.w, ib.c, self.in_stride, tab)
+            if wtab is None:
+                name, args = "jr_image_u8_augment_nhwc", args + (ws.data_ptr(), ws.numel())
+            else:
+                name, args = "jr_image_u8_warp_augment_nhwc", args + (wtab, ws.data_ptr(), ws.numel())
+        _ffi.check(name, getattr(self.lib, name)(*args, self._s))
+
+    def _check_labels(self, y, B: int) -> None:
+        if len(y) != B * self.units:
+            raise ValueError("labels must have batch*units elements")
 
     def _check_images(self, images, B: int) -> None:
         ib = self.g.bufs[self.g.input_buf]
@@ -1779,8 +1792,8 @@ class Engine(Replica):
         """Copy a batch (NHWC float32, or uint8 to be scaled by 1/255) into the
         input buffer.  Returns the batch size.  augment, warp: jr.augment
         tables (one jr_augment_param / jr_warp_param per image) -- the uint8
-        batch then goes through jr_image_u8_augment_nhwc or, with a warp,
-        jr_image_u8_warp_augment_nhwc (None, None: no augmentation).
+        batch then goes through the augmenting conversion kernel or, with a
+        warp, the warping one (None, None: no augmentation; _u8_to_input).
         staged: a uint8 host batch goes through the two-slot pinned feed
         (_upload_staged: the copy runs on a stream of its own and the host never
         waits for the step it feeds); anything else takes the path above."""
@@ -1789,104 +1802,37 @@ class Engine(Replica):
         self._frozen_fwd = None
         if staged and not isinstance(images, torch.Tensor) and np.asarray(images).dtype == np.uint8:
             self._upload_staged(np.asarray(images), labels, B, augment, warp)
-            return B
-        with torch.cuda.stream(self.stream):
-            self._upload(images, labels, B, augment, warp)
+        else:
+            with torch.cuda.stream(self.stream):
+                self._upload(images, labels, B, augment, warp)
         return B
 
     # ---- the staged input feed
-    def _feed_init(self) -> dict:
-        """Two slots, each one pinned host buffer and one device staging tensor
-        of the same layout: labels, the jr_augment_param and jr_warp_param
-        tables (sized for the planned batch, 256-byte aligned), then the uint8
-        pixels -- so one copy of the used prefix moves a whole batch."""
-        from . import augment as _augment
-        ib = self.g.bufs[self.g.input_buf]
-        al = lambda v: (v + 255) // 256 * 256   # noqa: E731
-        off_y = 0
-        off_a = al(4 * self.batch * self.units)
-        off_w = off_a + al(self.batch * _augment.PARAM_DTYPE.itemsize)
-        off_x = off_w + al(self.batch * _augment.WARP_DTYPE.itemsize)
-        nbytes = off_x + self.batch * ib.h * ib.w * ib.c
-        if self._aug_ws is None:    # the workspace of the augmenting kernels (the tables live in the slots)
-            self._aug_ws = torch.empty(int(self.lib.jr_augment_workspace_size(self.batch, ib.h, ib.w)),
-                                       dtype=torch.uint8, device=self.device)
-            self._aug_tab = torch.empty(self.batch * _augment.PARAM_DTYPE.itemsize, dtype=torch.uint8,
-                                        device=self.device)
-            self._warp_tab = torch.empty(self.batch * _augment.WARP_DTYPE.itemsize, dtype=torch.uint8,
-                                         device=self.device)
-        pin = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self._feed = {
-            "off": (off_y, off_a, off_w, off_x),
-            "pin": pin, "host": [p.numpy() for p in pin],
-            "dev": [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)],
-            "stream": torch.cuda.Stream(device=self.device),
-            "copied": [torch.cuda.Event() for _ in range(2)],
-            # recorded on self.stream after the step that read the slot; waited for before its refill
-            "consumed": [torch.cuda.Event() for _ in range(2)],
-            "busy": [False, False], "last": None,
-        }
-        return self._feed
-
     def _upload_staged(self, images: np.ndarray, labels, B: int, augment, warp) -> None:
         """_upload for a uint8 host batch without a pageable copy and without a
-        host wait for the step it feeds: fill the free slot's pinned buffer,
-        one copy on the feed stream, self.stream waits for that copy's event,
-        then the unchanged conversion kernel (and the label copy) on
-        self.stream.  A slot is refilled only after the event recorded behind
-        the step that consumed it: at most two steps are in flight."""
-        from . import augment as _augment
-        f = self._feed or self._feed_init()
+        host wait for the step it feeds: the batch goes through the free slot
+        of the feed (jr.runahead.Feed.load, built here at first use), then the
+        unchanged conversion kernel (_u8_to_input) reads pixels and tables
+        inside the slot, and the labels are copied out of it, on self.stream."""
         ib = self.g.bufs[self.g.input_buf]
-        if f["last"] is not None:   # what was enqueued since the last staged batch consumed its slot
-            f["consumed"][f["last"]].record(self.stream)
-            f["busy"][f["last"]] = True
-        s = 0 if f["last"] is None else 1 - f["last"]
-        if f["busy"][s]:
-            f["consumed"][s].synchronize()
-            f["busy"][s] = False
-        off_y, off_a, off_w, off_x = f["off"]
-        host, dev = f["host"][s], f["dev"][s]
-        npx = B * ib.h * ib.w * ib.c
-        host[off_x:off_x + npx] = images.reshape(-1)
-        if labels is not None:
-            y = np.asarray(labels, np.float32).reshape(-1)
-            if y.size != B * self.units:
-                raise ValueError("labels must have batch*units elements")
-            host[off_y:off_y + 4 * y.size] = y.view(np.uint8)
-        tab = wtab = None
-        if augment is not None or warp is not None:
-            tab = _augment.identity(B) if augment is None else _augment.as_table(augment, B)
-            host[off_a:off_a + tab.nbytes] = np.ascontiguousarray(tab).view(np.uint8).reshape(-1)
-            if warp is not None:
-                wtab = _augment.as_warp_table(warp, B)
-                host[off_w:off_w + wtab.nbytes] = np.ascontiguousarray(wtab).view(np.uint8).reshape(-1)
-        with torch.cuda.stream(f["stream"]):
-            dev[:off_x + npx].copy_(f["pin"][s][:off_x + npx], non_blocking=True)
-        f["copied"][s].record(f["stream"])
-        self.stream.wait_event(f["copied"][s])
-        dst, base = self.acts[self.g.input_buf], dev.data_ptr()
-        if tab is None:
-            _ffi.check("jr_image_u8_to_nhwc", self.lib.jr_image_u8_to_nhwc(
-                base + off_x, dst.data_ptr(), self.dt, B * ib.h * ib.w, ib.c, self.in_stride, self._s))
-        elif wtab is None:
-            _ffi.check("jr_image_u8_augment_nhwc", self.lib.jr_image_u8_augment_nhwc(
-                base + off_x, dst.data_ptr(), self.dt, B, ib.h, ib.w, ib.c, self.in_stride,
-                base + off_a, self._aug_ws.data_ptr(), self._aug_ws.numel(), self._s))
-        else:
-            _ffi.check("jr_image_u8_warp_augment_nhwc", self.lib.jr_image_u8_warp_augment_nhwc(
-                base + off_x, dst.data_ptr(), self.dt, B, ib.h, ib.w, ib.c, self.in_stride,
-                base + off_a, base + off_w, self._aug_ws.data_ptr(), self._aug_ws.numel(), self._s))
-        if labels is not None:
+        tab, wtab = _augment.batch_tables(B, augment, warp)
+        y = None if labels is None else np.asarray(labels, np.float32).reshape(-1)
+        if y is not None:
+            self._check_labels(y, B)
+        f = self._feed = self._feed or Feed(self.device, self.batch, self.units, ib.h * ib.w * ib.c)
+        dev = f.load(self.stream, images, y, tab, wtab)
+        base = dev.data_ptr()
+        self._u8_to_input(base + f.off_x, B, None if tab is None else base + f.off_a,
+                          None if wtab is None else base + f.off_w)
+        if y is not None:
             with torch.cuda.stream(self.stream):
-                self.labels[:B * self.units].copy_(dev[off_y:off_y + 4 * B * self.units].view(torch.float32))
-        f["last"] = s
+                self.labels[:y.size].copy_(dev[f.off_y:f.off_y + 4 * y.size].view(torch.float32))
 
     # ------------------------------------------------------------------- runs
     def forward(self, B: Optional[int] = None, bn: str = "batch", training: bool = False) -> None:
         """bn="frozen": normalise with the statistics of freeze_bn() instead
         of this batch's (every image's output then depends on that image alone).
-        training: the forward of a training step (train_step passes it): with
+        training: the forward of a training step (train_step's lists): with
         dropout on it drops, and backward / apply_update of that step take
         training=True too.  Every other forward never drops."""
         frozen = self._check_frozen(bn)
@@ -1964,71 +1910,76 @@ class Engine(Replica):
         self._no_update_on_average("apply_update")
         opt = self._build_calls(B or self.batch, training=training)[2]
         self.lanes.run(self._bound(opt, grad_scale))
-        if self.bn_momentum is not None:
+        self._settle()
+
+    # ---- the step driver: one routine enqueues a step, one settles the host's books after it
+    def _enqueue_step(self, lists, allreduce=None, fold: bool = False, denom: Optional[int] = None) -> None:
+        """A step's call lists (_build_calls) on the lanes: fork, forward, join,
+        [allreduce.begin], backward [with the bucket hook], join -- every lane
+        back on self.stream -- then _finish_update.  Without `allreduce` (a
+        micro-step that leaves its group open, a capture) nothing is exchanged."""
+        fwd, bwd, opt = lists[:3]
+        ln = self.lanes
+        ln.fork()
+        ln.run(fwd)
+        ln.join()
+        if allreduce is None:
+            ln.run(bwd)
+        else:
+            allreduce.begin(self, fold=True) if fold else allreduce.begin(self)
+            ln.run(bwd, allreduce.param_ready)
+        ln.join()
+        self._finish_update(opt, allreduce, denom)
+
+    def _finish_update(self, opt, allreduce, denom: Optional[int]) -> None:
+        """The tail that closes an update: [allreduce.finish -> the exchange's
+        scale], then the update list with grad_scale = scale / denom bound
+        (_bound: after finish() has returned the scale).  denom None: the list
+        as it stands -- a group stays open, or a capture, whose scalars were
+        bound before jr_graph_begin, never inside it."""
+        scale = 1.0 if allreduce is None else allreduce.finish(self)
+        self.lanes.run(opt if denom is None else self._bound(opt, scale / denom))
+
+    def _settle(self, batch: bool = True, closed: Optional[bool] = None, log: bool = False) -> None:
+        """The host's books after what a step enqueued -- the one place where
+        `updates`, `_pending` and the step log move.  batch: a micro-batch ran
+        (and with bn_moving its jr_bn_moving_update); closed: whether it closed
+        its group (None: no group is touched -- apply_update on its own); log:
+        one record, of an update when the group closed."""
+        if batch and self.bn_momentum is not None:
             self.updates += 1
+        if closed is not None:
+            self._pending = 0 if closed else self._pending + 1
+        if log:
+            self._log_append(bool(closed))
 
     def train_step(self, B: Optional[int] = None, allreduce=None) -> None:
-        """fwd + bwd (+ bucketed all-reduce) + optimizer, enqueued on the lanes;
-        everything is joined back onto self.stream before the optimizer.
-        accum_steps = K > 1: the optimizer (and the all-reduce) run on every K-th
-        call only, on the group's gradient sum (_accum_step)."""
+        """fwd + bwd (+ bucketed all-reduce) + optimizer, enqueued on the lanes
+        (_enqueue_step).  accum_steps = K > 1: one micro-batch -- forward and
+        backward as ever, then the group's sum; the exchange and the optimizer
+        run on the K-th call only, with grad_scale 1 / (k * world).  Closing
+        under data parallelism runs the DEFAULT lists: BucketAllReduce folds
+        `gacc` into each bucket on its own stream just before it issues it
+        (begin(fold=True))."""
         B = B or self.batch
         self._no_update_on_average("train_step")
-        if self.accum_steps > 1:
-            self._accum_step(B, allreduce)
-            return
-        if allreduce is None:
-            self.forward(B, training=True)
-            self.backward(B, training=True)
-            self.apply_update(B, training=True)
-            self._log_append(True)
-            return
-        self.forward(B, training=True)
-        allreduce.begin(self)
-        self.backward(B, hook=allreduce.param_ready, training=True)
-        scale = allreduce.finish(self)
-        self.apply_update(B, grad_scale=scale, training=True)
-        self._log_append(True)
+        ph = self._accum_phase()
+        closing = ph in (None, "close")
+        exchange = allreduce if closing else None
+        lists = self._build_calls(B, training=True, accum=None if exchange is not None else ph)
+        self._frozen_fwd = None
+        self._enqueue_step(lists, exchange, fold=ph is not None, denom=self._pending + 1 if closing else None)
+        self._settle(closed=closing, log=True)
 
     # ---- gradient accumulation (accum_steps = K > 1; DESIGN.md §14)
     def accum_pending(self) -> int:
         """Micro-batches in the open group (0: the last train_step, replay or accum_flush closed one)."""
         return self._pending
 
-    def _accum_phase(self) -> str:
-        k = self._pending
-        return "close" if k + 1 == self.accum_steps else "inside" if k else "open"
-
-    def _accum_step(self, B: int, allreduce) -> None:
-        """One micro-batch: forward and backward as ever; then the group's sum, and
-        on the closing one the exchange and the update with grad_scale 1 / (k *
-        world).  A micro-step that leaves the group open runs the backward
-        without the hook: nothing is exchanged.  Closing under data parallelism
-        runs the DEFAULT lists: BucketAllReduce folds `gacc` into each bucket on
-        its own stream just before it issues it (begin(fold=True))."""
-        k, ph = self._pending, self._accum_phase()
-        closing = ph == "close"
-        exchange = closing and allreduce is not None
-        fwd, bwd, opt, _, _ = self._build_calls(B, training=True, accum=None if exchange else ph)
-        self._frozen_fwd = None
-        ln = self.lanes
-        ln.fork()
-        ln.run(fwd)
-        ln.join()
-        scale = 1.0
-        if exchange:
-            allreduce.begin(self, fold=True)
-            ln.run(bwd, allreduce.param_ready)
-            ln.join()
-            scale = allreduce.finish(self)
-        else:
-            ln.run(bwd)
-            ln.join()
-        ln.run(self._bound(opt, scale / (k + 1)) if closing else opt)
-        if self.bn_momentum is not None:
-            self.updates += 1
-        self._pending = 0 if closing else k + 1
-        self._log_append(closing)
+    def _accum_phase(self) -> Optional[str]:
+        """Where the next micro-batch sits in its group (_build_calls' accum); None: accum_steps = 1."""
+        k, K = self._pending, self.accum_steps
+        return None if K == 1 else "close" if k + 1 == K else "inside" if k else "open"
 
     def _flush_calls(self) -> list:
         """accum_flush's list: jr_grad_accumulate(g <- acc, first = 1), then what
@@ -2046,35 +1997,28 @@ class Engine(Replica):
     def accum_flush(self, allreduce=None) -> bool:
         """Close a partial group of k < K micro-batches (the end of an epoch):
         g <- acc, the exchange (every bucket at once: no backward to overlap), the
-        update with grad_scale 1 / (k * world).  Nothing is pending: nothing
-        happens.  Returns whether an update ran.  Collective under data
-        parallelism: every rank holds the same k."""
+        update with grad_scale 1 / (k * world) (_finish_update).  Nothing is
+        pending: nothing happens.  Returns whether an update ran.  Collective
+        under data parallelism: every rank holds the same k."""
         self._no_update_on_average("accum_flush")
         k = self._pending
         if k == 0:
             return False
         opt = self._flush_calls()
         self.lanes.run(opt[:1])
-        scale = 1.0
         if allreduce is not None:
             allreduce.begin(self)
-            scale = allreduce.finish(self)
-        self.lanes.run(self._bound(opt, scale / k)[1:])
-        self._pending = 0
-        self._log_append(True)      # (the loss is the last micro-batch's: no forward ran here)
+        self._finish_update(opt[1:], allreduce, k)
+        self._settle(batch=False, closed=True, log=True)    # (the loss is the last micro-batch's: no forward ran here)
         return True
 
-    # ---- device metrics (jr.h jr_metrics_*; DESIGN.md §15)
+    # ---- device metrics (jr.h jr_metrics_*; DESIGN.md §15; state: jr.runahead.Metrics)
     def metrics_init(self, thresholds) -> None:
         """Device state of the streaming metrics: the fp32 threshold table, the
         uint32 [4][T] counts (tp, fp, fn, tn) and the Brier double[2], zeroed."""
-        thr = np.ascontiguousarray(np.asarray(thresholds, np.float32).reshape(-1))
-        if not 1 <= thr.size <= 1024:
-            raise ValueError("metrics_init: 1..1024 thresholds")
-        self._metrics = {"T": int(thr.size), "thr": self._after_fill(torch.from_numpy(thr).to(self.device)),
-                         "counts": self._t(4 * thr.size, torch.int32), "brier": self._t(2, torch.float64)}
+        self._metrics = Metrics(self, thresholds)
 
-    def _need_metrics(self) -> dict:
+    def _need_metrics(self) -> Metrics:
         if self._metrics is None:
             raise ValueError("the device metrics are off: call metrics_init(thresholds) first")
         return self._metrics
@@ -2082,28 +2026,20 @@ class Engine(Replica):
     def metrics_update(self, B: Optional[int] = None, counts: bool = True, brier: bool = True) -> None:
         """Enqueue jr_metrics_accumulate over the probabilities and labels of the
         forward (or step) enqueued last, on self.stream behind it: no host wait."""
-        m, which = self._need_metrics(), int(bool(counts)) | 2 * int(bool(brier))
-        if not which:
-            return
-        _ffi.check("jr_metrics_accumulate", self.lib.jr_metrics_accumulate(
-            self.probs.data_ptr(), self.labels.data_ptr(), (B or self.batch) * self.units, m["thr"].data_ptr(), m["T"],
-            m["counts"].data_ptr(), m["brier"].data_ptr(), which, self._s))
+        self._need_metrics().accumulate(self.probs.data_ptr(), self.labels.data_ptr(), (B or self.batch) * self.units,
+                                        counts, brier, self._s)
 
     def metrics_reset(self) -> None:
-        m = self._need_metrics()
-        _ffi.check("jr_metrics_reset", self.lib.jr_metrics_reset(m["counts"].data_ptr(), m["T"], m["brier"].data_ptr(),
-                                                                 self._s))
+        self._need_metrics().reset(self._s)
 
     def metrics_read(self) -> Tuple[np.ndarray, float, float]:
         """(uint32 [4, T] counts, the Brier sum, the sample count) after a synchronise."""
         m = self._need_metrics()
         self.synchronize()
-        counts = m["counts"].cpu().numpy().view(np.uint32).reshape(4, m["T"])
-        s, n = (float(v) for v in m["brier"].cpu().numpy())
-        return counts, s, n
+        return m.read()
 
-    # ---- the step log (jr.h jr_step_log_append; DESIGN.md §15)
-    STEP_REC = np.dtype([("loss", "<f4"), ("grad_norm", "<f4"), ("scale", "<f4"), ("flags", "<u4")])
+    # ---- the step log (jr.h jr_step_log_append; DESIGN.md §15; state: jr.runahead.StepLog)
+    STEP_REC = STEP_REC
 
     def step_log_enable(self, capacity: int) -> None:
         """From here on train_step (each micro-batch of an accumulation group) and
@@ -2112,36 +2048,21 @@ class Engine(Replica):
         and skip flag.  step_log_read() fetches them.  A device failure
         (jr_device_check) of a logged step shows at the next synchronise, up to
         `capacity` steps late."""
-        capacity = int(capacity)
-        if capacity < 1:
-            raise ValueError("step_log_enable: capacity >= 1")
-        self._log = {"cap": capacity, "ring": self._t(4 * capacity, torch.int32), "cursor": self._t(1, torch.int32),
-                     "appended": 0, "read": 0}
+        self._log = StepLog(self, capacity)
 
     def _log_append(self, updated: bool) -> None:
-        lg = self._log
-        if lg is None:
-            return
-        if lg["appended"] - lg["read"] >= lg["cap"]:
-            raise RuntimeError(f"step log full: {lg['cap']} records unread (call step_log_read() at least every "
-                               f"{lg['cap']} steps, or enable a larger ring)")
-        step = self.opt_step_dev.data_ptr() if (self.opt_ex and updated) else None
-        _ffi.check("jr_step_log_append", self.lib.jr_step_log_append(
-            lg["ring"].data_ptr(), lg["cap"], lg["cursor"].data_ptr(), self.loss.data_ptr(), step, self._s))
-        lg["appended"] += 1
+        if self._log is not None:
+            step = self.opt_step_dev.data_ptr() if (self.opt_ex and updated) else None
+            self._log.append(self.loss.data_ptr(), step, self._s)
 
     def step_log_read(self) -> np.ndarray:
         """The records appended since the last read, oldest first, as a STEP_REC
         array (flags bit 0: an update ran and grad_norm / scale are its own; bit 1:
         the non-finite guard skipped it).  One synchronise."""
-        lg = self._log
-        if lg is None:
+        if self._log is None:
             raise ValueError("the step log is off: call step_log_enable(capacity) first")
         self.synchronize()
-        ring = lg["ring"].cpu().numpy().view(self.STEP_REC)
-        idx = np.arange(lg["read"], lg["appended"]) % lg["cap"]
-        lg["read"] = lg["appended"]
-        return ring[idx].copy()
+        return self._log.take()
 
     def capture(self, B: Optional[int] = None) -> None:
         """Capture fwd+bwd+update for batch B into a HIP graph (single GPU;
@@ -2152,7 +2073,8 @@ class Engine(Replica):
         (waits on events recorded mid-stream) crashed hipGraphInstantiate
         (DESIGN.md §3); more lanes run eagerly.  accum_steps = K > 1: one graph
         each for the micro-step that opens a group, one inside it (K > 2) and
-        the one that closes it, grad_scale 1 / K."""
+        the one that closes it, grad_scale 1 / K.  The host's books (_settle)
+        stay as they are: nothing ran."""
         B = B or self.batch
         self._no_update_on_average("capture")
         if self.optimizer == "adam":
@@ -2168,17 +2090,11 @@ class Engine(Replica):
                 opt = self._bound(opt, 1.0 / K)
             torch.cuda.synchronize(self.device)
             _ffi.check("jr_graph_begin", self.lib.jr_graph_begin(self._s))
-            ln = self.lanes
-            ln.capturing = not self.graph_precise
+            self.lanes.capturing = not self.graph_precise
             try:
-                ln.fork()
-                ln.run(fwd)
-                ln.join()
-                ln.run(bwd)
-                ln.join()
-                ln.run(opt)
+                self._enqueue_step((fwd, bwd, opt))
             finally:
-                ln.capturing = False
+                self.lanes.capturing = False
                 ex = ctypes.c_void_p()
                 _ffi.check("jr_graph_end", self.lib.jr_graph_end(self._s, ctypes.byref(ex)))
             self._graphs[B if ph is None else (B, ph)] = ex.value
@@ -2186,16 +2102,12 @@ class Engine(Replica):
     def replay(self, B: Optional[int] = None) -> None:
         B = B or self.batch
         self._no_update_on_average("replay")
-        K = self.accum_steps
-        ph = self._accum_phase() if K > 1 else None     # (choosing the graph is the only host work)
+        ph = self._accum_phase()        # (choosing the graph is the only host work)
         if self.opt_ex:     # a captured step is single-GPU: grad_scale 1 / K, whatever an eager update left
-            self._push_hyper(self.lr, 1.0 / K)
+            self._push_hyper(self.lr, 1.0 / self.accum_steps)
         _ffi.check("jr_graph_launch",
                    self.lib.jr_graph_launch(ctypes.c_void_p(self._graphs[B if ph is None else (B, ph)]), self._s))
-        if self.bn_momentum is not None:
-            self.updates += 1
-        if K > 1:
-            self._pending = 0 if ph == "close" else self._pending + 1
+        self._settle(closed=ph in (None, "close"))
 
     def synchronize(self) -> None:
         """Wait for every lane, then jr_device_check: a device-side failure

@@ -102,17 +102,22 @@ class Session:
 
     def train_batch(self, images, labels, augment=None, warp=None) -> tuple:
         """train.py:231-232: one step; returns (global_step, xent, probs).
-        augment, warp: jr.augment tables for this (uint8) batch, or None."""
-        if self.device_metrics:
-            return self._train_enqueue(images, labels, augment, warp)
-        B = self.engine.set_batch(images, labels, augment=augment, warp=warp)
+        augment, warp: jr.augment tables for this (uint8) batch, or None.
+        device_metrics: the batch goes through the staged feed, the step and the
+        Brier sums of its probabilities are enqueued and nothing is waited for --
+        the loss is in the engine's step log (Engine.step_log_enable), the
+        probabilities stay on the device: (global_step, None, None)."""
+        eng, ahead = self.engine, self.device_metrics
+        B = eng.set_batch(images, labels, augment=augment, warp=warp, **({"staged": True} if ahead else {}))
         step = self.global_step
-        self.engine.train_step(B, allreduce=getattr(self, "allreduce", None))
+        eng.train_step(B, allreduce=getattr(self, "allreduce", None))
+        if ahead:
+            eng.metrics_update(B, counts=False, brier=True)
         # global_step counts optimizer updates: with Engine(accum_steps=K > 1) a batch that
         # leaves its group open is no step (the loss and predictions are this batch's own)
-        if not getattr(self.engine, "accum_pending", int)():
+        if not getattr(eng, "accum_pending", int)():
             self.global_step += 1
-        return step, self.engine.loss_value(), self.engine.predictions(B)
+        return (step, None, None) if ahead else (step, eng.loss_value(), eng.predictions(B))
 
     def accum_flush(self) -> bool:
         """Close a partial group of accumulated micro-batches (Engine.accum_flush;
@@ -123,19 +128,6 @@ class Session:
         return done
 
     # ---------------------------------------------- device metrics (opt-in)
-    def _train_enqueue(self, images, labels, augment, warp) -> tuple:
-        """train_batch with device_metrics: the staged feed, the step, the Brier
-        sums of its probabilities -- all enqueued, nothing waited for.  The loss
-        is in the engine's step log (Engine.step_log_enable), the probabilities
-        stay on the device: (global_step, None, None)."""
-        B = self.engine.set_batch(images, labels, augment=augment, warp=warp, staged=True)
-        step = self.global_step
-        self.engine.train_step(B, allreduce=getattr(self, "allreduce", None))
-        self.engine.metrics_update(B, counts=False, brier=True)
-        if not self.engine.accum_pending():
-            self.global_step += 1
-        return step, None, None
-
     def predict_enqueue(self, images, labels) -> None:
         """predict() without the wait: the forward, then the counts and the Brier
         sums of its probabilities against `labels` on the device."""

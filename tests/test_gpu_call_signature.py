@@ -23,7 +23,10 @@ FIXTURE = os.path.join(HERE, "golden", "call_signatures.json")
 RES = 107
 PHASES = ("fwd", "bwd", "opt")
 
-# name -> (kind, constructor keywords, environment, [(batch, lanes or None), ...], phases)
+# name -> (kind, constructor keywords, environment, builds, phases); a build is (batch, lanes or None) or
+# (batch, lanes or None, {"training": ..., "accum": ...}) -- further keywords of _build_calls -- or "flush":
+# accum_flush's update list
+ACCUM = [(4, None, dict(training=True, accum=ph)) for ph in ("open", "inside", "close", None)] + ["flush"]
 CASES = {
     "x6h_l2_train": ("engine", dict(conv_math="x6h", lanes=2), {}, [(4, None), (3, None), (4, 1)], PHASES),
     "x8_l4_train": ("engine", dict(conv_math="x8", lanes=4), {}, [(4, None)], PHASES),
@@ -40,6 +43,16 @@ CASES = {
     "x8_adam": ("engine", dict(conv_math="x8", optimizer="adam"), {}, [(4, None)], ("opt",)),
     "ens3_x6h_l2": ("ensemble", dict(members=3, conv_math="x6h", lanes=2), {}, [(4, None), (3, None)], ("fwd",)),
     "ens2_bf16": ("ensemble", dict(members=2, dtype="bf16"), {}, [(4, None)], ("fwd",)),
+    "x8_decay_clip": ("engine", dict(conv_math="x8", weight_decay=1e-4, clip_norm=1.0), {}, [(4, None)], PHASES),
+    "x8_rmsprop_ema": ("engine", dict(conv_math="x8", optimizer="rmsprop", weight_ema=0.999), {}, [(4, None)], PHASES),
+    "x8_dropout": ("engine", dict(conv_math="x8", dropout=0.2), {},
+                   [(4, None, dict(training=True)), (4, None, dict(training=False))], PHASES),
+    "x8_loss_recipe": ("engine", dict(conv_math="x8", label_smoothing=0.1, class_weight=[2.0], focal_gamma=2.0), {},
+                       [(4, None)], PHASES),
+    "x8_bn_moving": ("engine", dict(conv_math="x8", bn_moving=0.99), {}, [(4, None)], PHASES),
+    "x8_accum3": ("engine", dict(conv_math="x8", accum_steps=3), {}, ACCUM, PHASES),
+    "bf16_accum3_every_call": ("engine", dict(accum_steps=3, dtype="bf16", dropout=0.2, clip_norm=1.0, weight_ema=0.999,
+                                              bn_moving=0.99), {}, ACCUM, PHASES),
 }
 
 
@@ -80,7 +93,8 @@ def _describe(calls):
 
 
 def build_case(name, setenv):
-    """{"B<batch>[_nl<lanes>]/<phase>": (text, {"sha256", "counts"})} of one case."""
+    """{"B<batch>[_nl<lanes>][_accum_<where>][_training_<flag>]/<phase>" or "flush/opt": (text, {"sha256",
+    "counts"})} of one case."""
     from jr.engine import Engine
     from jr.ensemble import EnsembleEngine
     from jr.init import init_params
@@ -91,7 +105,7 @@ def build_case(name, setenv):
     dtype = kw.get("dtype", "f32")
     conv_math = kw.get("conv_math") or ("x8" if dtype == "f32" else "bf16")
     batch = kw.pop("batch", 4)
-    _clear_overrides(dtype, conv_math, sorted({batch} | {B for B, _ in builds}))
+    _clear_overrides(dtype, conv_math, sorted({batch} | {b[0] for b in builds if b != "flush"}))
     out = {}
     if kind == "ensemble":
         from jr.inception import build_inception_v3
@@ -105,9 +119,13 @@ def build_case(name, setenv):
     if name == "f32_defer_flush":
         n = e.nparam
         e.set_flush_points([n // 2, n // 5, n // 20])
-    for B, nl in builds:
-        lists = e._build_calls(B) if nl is None else e._build_calls(B, nl)
-        key = f"B{B}" if nl is None else f"B{B}_nl{nl}"
+    for build in builds:
+        if build == "flush":
+            out["flush/opt"] = _describe(e._flush_calls())
+            continue
+        B, nl, more = (tuple(build) + ({},))[:3]
+        lists = e._build_calls(B, **more) if nl is None else e._build_calls(B, nl, **more)
+        key = (f"B{B}" if nl is None else f"B{B}_nl{nl}") + "".join(f"_{k}_{v}" for k, v in sorted(more.items()))
         for phase, calls in zip(PHASES, lists[:3]):
             if phase in phases:
                 out[f"{key}/{phase}"] = _describe(calls)

@@ -161,6 +161,45 @@ def test_accumulation_logs_every_micro_batch_and_the_flush():
     eng.close()
 
 
+@pytest.mark.parametrize("tables", ["none", "augment", "warp", "both"])
+def test_staged_and_unstaged_uploads_write_the_same_bytes(tables):
+    """Three consecutive uint8 batches of 3 in an engine planned for 4 (both slots, and one refilled), with
+    no table, a colour table, a warp table and both: set_batch(..., staged=True) leaves the input buffer and
+    the labels bit for bit as set_batch(...) does.  Both start from the same poisoned buffers, and the
+    staged three are enqueued back to back and read after one synchronise."""
+    from jr import augment, synth
+    from jr.engine import Engine
+    n = 3
+    eng = Engine(4, RES, RES, seed=3, tiles="heuristic", train=False)
+    rng = np.random.Generator(np.random.PCG64(5))
+    batches = []
+    for i in range(3):
+        aug = augment.draw(augment.AugmentSpec(), rng, n) if tables in ("augment", "both") else None
+        warp = (augment.draw_warp(augment.WarpSpec(rotate=20.0, zoom=(0.9, 1.1), shift=0.05), rng, n, RES, RES)
+                if tables in ("warp", "both") else None)
+        batches.append((synth.fundus_batch(300 + 10 * i, n, RES), synth.labels(300 + 10 * i, n, p=0.5), aug, warp))
+    xbuf = eng.acts[eng.g.input_buf]
+
+    def uploads(staged):
+        out = []
+        for x, y, aug, warp in batches:
+            with torch.cuda.stream(eng.stream):
+                xbuf.fill_(-3.0)
+                eng.labels.fill_(-3.0)
+            assert eng.set_batch(x, y, augment=aug, warp=warp, staged=staged) == n
+            with torch.cuda.stream(eng.stream):
+                out.append((xbuf.clone(), eng.labels.clone()))
+        eng.synchronize()
+        return [(a.view(torch.uint8).cpu().numpy(), b.view(torch.uint8).cpu().numpy()) for a, b in out]
+
+    plain, staged = uploads(False), uploads(True)
+    for (xa, ya), (xb, yb) in zip(plain, staged):
+        assert xa.tobytes() == xb.tobytes()
+        assert ya.tobytes() == yb.tobytes()
+    assert plain[0][0].tobytes() != plain[1][0].tobytes()       # the batches differ: a stale slot would show
+    eng.close()
+
+
 def test_staged_feed_takes_only_uint8_host_batches():
     """float32 batches and staged=False go the old way and leave the feed unbuilt."""
     from jr.engine import Engine
@@ -177,5 +216,5 @@ def test_staged_feed_takes_only_uint8_host_batches():
         eng.set_batch(x, y, staged=True)
         eng.forward(2)
         assert eng.predictions(2).tobytes() == want.tobytes()
-    assert eng._feed is not None and all(p.is_pinned() for p in eng._feed["pin"])
+    assert eng._feed is not None and all(p.is_pinned() for p in eng._feed.pin)
     eng.close()
