@@ -34,7 +34,6 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import lib.dataset  # noqa: E402
-import lib.evaluation  # noqa: E402
 import lib.metrics  # noqa: E402
 
 # evaluate.py:24-29
@@ -221,31 +220,64 @@ def load_bn_stats(paths, graph):
     return stats, checkpoint.read_meta(paths[0])["bn_moving"]
 
 
+class Members:
+    """The ensemble as predict_all and freeze_engines see it, whichever way it is held: a list of
+    jr.Engine (one per member) or one jr.ensemble.EnsembleEngine (every member's layer in one launch).
+    every: what set_batch / forward / freeze_bn are called on; count: the members; g: their graph;
+    device: where they live; predictions(n): [M][n, 1] of the batch just run."""
+
+    def __init__(self, engines):
+        self.engines, self.grouped = engines, hasattr(engines, "members")
+        self.every = [engines] if self.grouped else list(engines)
+        self.count = engines.members if self.grouped else len(self.every)
+        self.g, self.device = self.every[0].g, self.every[0].device
+
+    def predictions(self, n):
+        return list(self.engines.predictions(n)) if self.grouped else [e.predictions(n) for e in self.every]
+
+    def upload(self, x):
+        """One device copy of a uint8 batch for every member and view (it crosses PCIe once), waited for."""
+        import torch
+        xd = torch.as_tensor(x).to(self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        return xd
+
+    def run(self, x, y, bn, **tables):
+        """[M][n, 1]: one batch (a host array or upload()'s copy) through every member.  Every
+        member's forward is enqueued before the first result is read back: one host sync per
+        batch, not per member.  tables: set_batch's augment / warp of a test-time view."""
+        n = 0
+        for e in self.every:
+            n = e.set_batch(x, y, **tables)
+            e.forward(n, bn=bn)
+        return self.predictions(n)
+
+
+def _members(engines):
+    return engines if isinstance(engines, Members) else Members(engines)
+
+
 def freeze_engines(engines, stats=None, calibrate_dir=None, batches=16, batch_size=DEFAULT_BATCH_SIZE):
     """Frozen BN for every member: from saved statistics (one dict per
     member), or calibrated on the first `batches` batches of calibrate_dir
     (jr.Engine.calibrate_bn).  Returns the number of calibration batches."""
-    grouped = hasattr(engines, "members")
-    every = [engines] if grouped else engines
+    mem = _members(engines)
     k = 0
     if calibrate_dir is not None:
-        g = every[0].g
-        for e in every:
+        for e in mem.every:
             dataset = lib.dataset.initialize_dataset(
                 calibrate_dir, batch_size, num_workers=NUM_WORKERS, prefetch_buffer_size=2 * batch_size,
-                image_data_format="channels_last", num_channels=NUM_CHANNELS, image_dim=[g.height, g.width],
+                image_data_format="channels_last", num_channels=NUM_CHANNELS, image_dim=[mem.g.height, mem.g.width],
                 decode_dtype="uint8", shard=(0, 1))
             it = iter(dataset)
             try:
                 k = e.calibrate_bn(x for j, (x, _) in zip(range(batches), it))
             finally:
                 lib.dataset.close_iterator(it)
-    elif grouped:
-        engines.load_bn_moving(stats)
-    else:
-        for e, st in zip(engines, stats):
+    else:       # the grouped engine takes the list, a member's engine its own
+        for e, st in zip(mem.every, [stats] if mem.grouped else stats):
             e.load_bn_moving(st)
-    for e in every:
+    for e in mem.every:
         e.freeze_bn("moving")
     return k
 
@@ -255,20 +287,13 @@ def predict_views(engines, x, y, views, bn="batch"):
     `views` ((flags, matrix) pairs of jr.augment) in their order.  The batch
     crosses PCIe once; each view re-runs the input kernel from the device
     copy (jr_image_u8_warp_augment_nhwc), then every member's forward."""
-    import torch
     from jr import augment
-    grouped = hasattr(engines, "members")
-    every = [engines] if grouped else engines
-    xd = torch.as_tensor(x).to(every[0].device)
-    torch.cuda.current_stream(every[0].device).synchronize()
+    mem = _members(engines)
+    xd = mem.upload(x)
     seen = []       # [view][member][n, 1]
     for view in views:
         tab, warp = augment.view_tables(view, len(x))
-        n = 0
-        for e in every:
-            n = e.set_batch(xd, y, augment=tab, warp=warp)
-            e.forward(n, bn=bn)
-        seen.append(list(engines.predictions(n)) if grouped else [e.predictions(n) for e in every])
+        seen.append(mem.run(xd, y, bn, augment=tab, warp=warp))
     return [np.mean(np.array([v[m] for v in seen]), axis=0) for m in range(len(seen[0]))]
 
 
@@ -302,21 +327,20 @@ def write_index(path, labels, predictions, batch_size):
 def predict_all(engines, data_dir, batch_size, rank=0, world=1, bn="batch", tta="none", attribution=None):
     """Per-member predictions over this rank's batches: ([M][n_r, 1], [n_r, 1],
     batch indices).  Each batch is decoded once (this rank's batches only)
-    and run through every member.  bn: "batch", or "frozen" (freeze_engines).
+    and run through every member, while the decoder threads already work on
+    the next batches.  bn: "batch", or "frozen" (freeze_engines).
     tta: "none", or a mode of tta_views -- a member's prediction is then its
     mean over those views of the batch (predict_views).  attribution: None, or
     {"method", "steps", "dir"} -- after a batch's predictions are read, its
     saliency maps are written (write_maps; per-member engines, frozen BN)."""
-    import torch
-    grouped = hasattr(engines, "members")      # jr.ensemble.EnsembleEngine
-    g = engines.g if grouped else engines[0].g
+    mem = _members(engines)
     dataset = lib.dataset.initialize_dataset(
         data_dir, batch_size, num_workers=NUM_WORKERS, prefetch_buffer_size=2 * batch_size,
         image_data_format="channels_last", num_channels=NUM_CHANNELS,
-        image_dim=[g.height, g.width], decode_dtype="uint8",
+        image_dim=[mem.g.height, mem.g.width], decode_dtype="uint8",
         shard=(rank, world))
-    preds = [[] for _ in range(engines.members if grouped else len(engines))]
-    views = None if tta == "none" else tta_views(tta, g.height, g.width)
+    preds = [[] for _ in range(mem.count)]
+    views = None if tta == "none" else tta_views(tta, mem.g.height, mem.g.width)
     got_y, ids = [], []
     it = iter(dataset)
     try:
@@ -324,29 +348,13 @@ def predict_all(engines, data_dir, batch_size, rank=0, world=1, bn="batch", tta=
             ids.append(k * world + rank)
             got_y.append(y)
             if views is not None:
-                for m, p in enumerate(predict_views(engines, x, y, views, bn)):
-                    preds[m].append(p)
-                continue
-            # every member's forward is enqueued before the first result is
-            # read back (one host sync per batch, not per member), while the
-            # decoder threads already work on the next batches
-            if grouped:       # every member's layer in one launch
-                n = engines.set_batch(x, y)
-                engines.forward(n, bn=bn)
-                for m, p in enumerate(engines.predictions(n)):
-                    preds[m].append(p)
-                continue
-            # (the uint8 batch crosses PCIe once for all members)
-            xd = torch.as_tensor(x).to(engines[0].device)
-            torch.cuda.current_stream(engines[0].device).synchronize()
-            n = 0
-            for e in engines:
-                n = e.set_batch(xd, y)
-                e.forward(n, bn=bn)
-            for m, e in enumerate(engines):
-                preds[m].append(e.predictions(n))
-            if attribution is not None:
-                write_maps(engines, n, ids[-1], attribution)
+                batch = predict_views(mem, x, y, views, bn)
+            else:       # the grouped engine stages the host array itself; members share one device copy
+                batch = mem.run(x if mem.grouped else mem.upload(x), y, bn)
+            for m, p in enumerate(batch):
+                preds[m].append(p)
+            if attribution is not None and views is None and not mem.grouped:
+                write_maps(mem.every, len(batch[0]), ids[-1], attribution)
     finally:
         lib.dataset.close_iterator(it)
     empty = np.zeros((0, 1), np.float32)
@@ -355,121 +363,133 @@ def predict_all(engines, data_dir, batch_size, rank=0, world=1, bn="batch", tta=
     return preds, labels, ids
 
 
-def _one_batch(x, y):
-    """feed_dict_fn for lib.evaluation.perform_test: one batch, then the end
-    of the pass (evaluate.py:114-118 feed_images)."""
-    state = {"done": False}
+def merge_ranks(gathered, batch_size, members):
+    """(preds [M][n, 1], labels [n, 1]) in dataset order from every rank's (batch indices, preds,
+    labels) of predict_all: each rank holds whole batches of batch_size, but for the last batch of
+    the dataset, which may be partial, on the rank that got it; a rank may hold no batch at all."""
+    pieces = []
+    for o, p, y in gathered:
+        sizes = np.cumsum([0] + [batch_size] * len(o))
+        if len(o) and y.shape[0] < sizes[-1]:
+            sizes[-1] = y.shape[0]
+        for k, bi in enumerate(o):
+            pieces.append((bi, [m[sizes[k]:sizes[k + 1]] for m in p], y[sizes[k]:sizes[k + 1]]))
+    pieces.sort(key=lambda t: t[0])
+    preds = [np.vstack([pc[1][m] for pc in pieces]) for m in range(members)]
+    return preds, np.vstack([pc[2] for pc in pieces])
 
-    def feed():
-        if state["done"]:
-            raise StopIteration
-        state["done"] = True
-        return {"x": x, "y": y}
-    return feed
+
+# ---- main()'s three parts
+def choose_data_dir(parser, args):
+    """The data directory of -e / -m / -o --data_dir; None (the refusal and the help are printed) where
+    the flags name no single data set."""
+    # evaluate.py:53-56 (chained comparison kept as is, App. C Q5)
+    if bool(args.eyepacs) == bool(args.messidor) == bool(args.other):
+        print("Can only evaluate one data set at once!")
+    elif args.data_dir is not None:
+        return str(args.data_dir)
+    elif args.eyepacs:
+        return DEFAULT_EYEPACS_DIR
+    elif args.messidor:
+        return DEFAULT_MESSIDOR_DIR
+    else:
+        print("Please specify --data_dir.")
+    parser.print_help()
+    return None
+
+
+def build_members(args, paths, batch_size, r):
+    """(engines, attribution): every member resident on device r.local with the weights (--weights)
+    and the BN statistics (--bn) the flags name, frozen where they say so; rank 0 prints what was chosen."""
+    from jr import checkpoint
+    from jr.inception import build_inception_v3
+    say = print if r.rank == 0 else (lambda *a, **k: None)
+    meta = checkpoint.read_meta(paths[0])
+    graph = lambda: build_inception_v3(meta["height"], meta["width"], meta.get("units", 1))  # noqa: E731
+    # (before any engine is built: d4 refuses images that are not square)
+    n_views = len(tta_views(args.tta, meta["height"], meta["width"])) if args.tta != "none" else 1
+    conv_math, bn_stats, bn_info = args.conv_math, None, None
+    flats = None
+    if args.weights == "averaged":              # before any engine is built
+        flats = load_averaged(paths, graph())
+        say("Weights: averaged (the moving averages saved by train.py --weight_ema)")
+    if args.bn == "moving":
+        if args.bn_calibrate_dir is None:       # before any engine is built
+            bn_stats, bn_info = load_bn_stats(paths, graph())
+        if args.dtype == "f32" and conv_math == "x6h" and not args.x6h_frozen:
+            conv_math = "x8"
+            say("--bn moving: conv_math x8 is used instead of x6h (x6h scales activations by a bound that "
+                "holds only for values standardised by their own batch's statistics)")
+    attribution = None
+    if args.attribution is not None:
+        attribution = {"method": args.attribution, "steps": args.attribution_steps, "dir": str(args.attribution_dir)}
+        # (stderr: stdout stays byte-equal to the run without --attribution)
+        say(f"--attribution {args.attribution}: one engine per member (as --per_member), each with input-gradient "
+            f"buffers; maps to {attribution['dir']}", file=sys.stderr)
+    engines = make_engines(paths, meta, batch_size, device=r.local, conv_math=conv_math,
+                           dtype=args.dtype, grouped=not (args.per_member or attribution),
+                           input_grad=attribution is not None, x6h_frozen=args.x6h_frozen, flats=flats)
+    if args.bn == "moving":
+        k = freeze_engines(engines, bn_stats, args.bn_calibrate_dir, args.bn_calibrate_batches, batch_size)
+        if bn_info is not None:
+            say(f"BN statistics: moving (momentum {bn_info['momentum']}, {bn_info['updates']} updates)")
+        else:
+            say(f"BN statistics: moving (calibrated on {k} batches of {args.bn_calibrate_dir})")
+    if args.tta != "none":
+        say(f"Test-time augmentation: {args.tta} ({n_views} views)")
+    return engines, attribution
+
+
+def score(preds, labels, thresholds, save_path, attribution=None, batch_size=DEFAULT_BATCH_SIZE):
+    """evaluate.py:214-250: the linear ensemble average, its Brier score, AUC, confusion matrix at the
+    operating threshold (the last of `thresholds`), the printed lines and the operating-point CSV."""
+    from jr import cli
+    from jr.session import Session
+    avg_pred = np.mean(np.array(preds), axis=0)          # evaluate.py:214-217
+    if attribution is not None:
+        write_index(os.path.join(attribution["dir"], "index.csv"), labels, avg_pred, batch_size)
+    sess = Session(None, thresholds, NUM_THRESHOLDS, KEPSILON)
+    sess.reset()
+    sess.update(labels, avg_pred)
+    spec, sens = sess.specificities(), sess.sensitivities()
+    print(f"Brier score: {sess.value('brier'):6.4}, AUC: {sess.value('auc'):10.8}")
+    print(f"Confusion matrix at operating threshold {thresholds[-1]:0.3f}")
+    print(sess.confusion_matrix()[0])
+    print("Specificity: {0:0.4f}, Sensitivity: {1:0.4f} at Operating Threshold {2:0.4f}.".format(
+        spec[-1], sens[-1], thresholds[-1]))
+    cli.write_operating_points(save_path, thresholds, spec, sens, NUM_THRESHOLDS)
 
 
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    # evaluate.py:53-56 (chained comparison kept as is, App. C Q5)
-    if bool(args.eyepacs) == bool(args.messidor) == bool(args.other):
-        print("Can only evaluate one data set at once!")
-        parser.print_help()
+    data_dir = choose_data_dir(parser, args)
+    if data_dir is None:
         return 2
-    if args.data_dir is not None:
-        data_dir = str(args.data_dir)
-    elif args.eyepacs:
-        data_dir = DEFAULT_EYEPACS_DIR
-    elif args.messidor:
-        data_dir = DEFAULT_MESSIDOR_DIR
-    else:
-        print("Please specify --data_dir.")
-        parser.print_help()
-        return 2
-
     if args.weights == "averaged" and args.bn == "moving" and args.bn_calibrate_dir is None:
         raise SystemExit("--weights averaged --bn moving needs --bn_calibrate_dir DIR: the BN statistics saved with a "
                          "checkpoint belong to its trained weights, not to the averaged ones")
-
-    import torch
-    from jr import _ffi, checkpoint
+    from jr import _ffi, cli
 
     load_model_paths = expand_model_paths(str(args.load_model_path))
     batch_size = int(args.batch_size)
     operating_threshold = float(args.operating_threshold)
     save_path = str(args.save_operating_thresholds_path)
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    # rehearsal knobs for the N > 1 path on a one-GPU box (as bench.py's):
-    # JR_ONE_DEVICE=1 puts every rank on cuda:0, JR_DIST_BACKEND=gloo replaces
-    # RCCL (which refuses two ranks on one device); the only collective here
-    # is the final all_gather_object of the predictions
-    if os.environ.get("JR_ONE_DEVICE") == "1" or os.environ.get("JR_BENCH_ONE_DEVICE") == "1":
-        local = 0
-    backend = os.environ.get("JR_DIST_BACKEND", "nccl")
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        torch.cuda.set_device(local)
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-        else:
-            dist.init_process_group(backend)
-
+    # (the only collective here is the final all_gather_object of the predictions)
+    r = cli.ranks()
     random.seed(432)
-    if rank == 0:       # one copy of the reference's header lines, whatever the rank count
-        print(f"Numpy version: {np.__version__}")
-        print(f"Torch version: {torch.__version__} (libjr / MI355X backend)")
+    if r.rank == 0:       # one copy of the reference's header lines, whatever the rank count
+        cli.print_versions()
         print("""
 Evaluating: {},
 Saving operating thresholds metrics at: {},
 Using operating treshold: {},
 """.format(data_dir, save_path, operating_threshold))
         print("Trying to load model(s):\n{}".format("\n".join(load_model_paths)))
-
     thresholds = lib.metrics.generate_thresholds(NUM_THRESHOLDS, KEPSILON) + [operating_threshold]
-    meta = checkpoint.read_meta(load_model_paths[0])
-    # (before any engine is built: d4 refuses images that are not square)
-    n_views = len(tta_views(args.tta, meta["height"], meta["width"])) if args.tta != "none" else 1
-    conv_math, bn_stats, bn_info = args.conv_math, None, None
-    flats = None
-    if args.weights == "averaged":              # before any engine is built
-        from jr.inception import build_inception_v3
-        flats = load_averaged(load_model_paths, build_inception_v3(meta["height"], meta["width"], meta.get("units", 1)))
-        if rank == 0:
-            print("Weights: averaged (the moving averages saved by train.py --weight_ema)")
-    if args.bn == "moving":
-        if args.bn_calibrate_dir is None:       # before any engine is built
-            from jr.inception import build_inception_v3
-            bn_stats, bn_info = load_bn_stats(load_model_paths, build_inception_v3(
-                meta["height"], meta["width"], meta.get("units", 1)))
-        if args.dtype == "f32" and conv_math == "x6h" and not args.x6h_frozen:
-            conv_math = "x8"
-            if rank == 0:
-                print("--bn moving: conv_math x8 is used instead of x6h (x6h scales activations by a bound that "
-                      "holds only for values standardised by their own batch's statistics)")
-    attribution = None
-    if args.attribution is not None:
-        attribution = {"method": args.attribution, "steps": args.attribution_steps, "dir": str(args.attribution_dir)}
-        if rank == 0:       # (stderr: stdout stays byte-equal to the run without --attribution)
-            print(f"--attribution {args.attribution}: one engine per member (as --per_member), each with input-gradient "
-                  f"buffers; maps to {attribution['dir']}", file=sys.stderr)
-    engines = make_engines(load_model_paths, meta, batch_size, device=local, conv_math=conv_math,
-                           dtype=args.dtype, grouped=not (args.per_member or attribution),
-                           input_grad=attribution is not None, x6h_frozen=args.x6h_frozen, flats=flats)
-    if args.bn == "moving":
-        k = freeze_engines(engines, bn_stats, args.bn_calibrate_dir, args.bn_calibrate_batches, batch_size)
-        if rank == 0 and bn_info is not None:
-            print(f"BN statistics: moving (momentum {bn_info['momentum']}, {bn_info['updates']} updates)")
-        elif rank == 0:
-            print(f"BN statistics: moving (calibrated on {k} batches of {args.bn_calibrate_dir})")
-    if args.tta != "none" and rank == 0:
-        print(f"Test-time augmentation: {args.tta} ({n_views} views)")
+    engines, attribution = build_members(args, load_model_paths, batch_size, r)
     try:
-        preds, labels, order = predict_all(engines, data_dir, batch_size, rank, world,
+        preds, labels, order = predict_all(engines, data_dir, batch_size, r.rank, r.world,
                                            bn="frozen" if args.bn == "moving" else "batch", tta=args.tta,
                                            attribution=attribution)
     except _ffi.JRError as e:
@@ -477,59 +497,15 @@ Using operating treshold: {},
             print("--x6h_frozen: an activation exceeded the x6h bound under the frozen BN statistics; the "
                   "predictions are invalid -- repeat the run without --x6h_frozen (x8)", file=sys.stderr)
         raise
-
-    if dist:   # gather every rank's batches to rank 0, restore dataset order
-        gathered = [None] * world
-        dist.all_gather_object(gathered, (order, preds, labels))
-        if rank != 0:
-            dist.destroy_process_group()
-            return 0
-        pieces = []
-        for o, p, y in gathered:
-            sizes = np.cumsum([0] + [batch_size] * len(o))
-            # the last batch may be partial
-            if len(o) and y.shape[0] < sizes[-1]:
-                sizes[-1] = y.shape[0]
-            for k, bi in enumerate(o):
-                pieces.append((bi, [m[sizes[k]:sizes[k + 1]] for m in p], y[sizes[k]:sizes[k + 1]]))
-        pieces.sort(key=lambda t: t[0])
-        preds = [np.vstack([pc[1][m] for pc in pieces]) for m in range(len(load_model_paths))]
-        labels = np.vstack([pc[2] for pc in pieces])
-
-    all_predictions = np.array(preds)
-    avg_pred = np.mean(all_predictions, axis=0)          # evaluate.py:214-217
-    all_y = labels
-    if attribution is not None:
-        write_index(os.path.join(attribution["dir"], "index.csv"), all_y, avg_pred, batch_size)
-
-    names = {"tp": lib.metrics.true_positives_at_thresholds, "fp": lib.metrics.false_positives_at_thresholds,
-             "fn": lib.metrics.false_negatives_at_thresholds, "tn": lib.metrics.true_negatives_at_thresholds}
-    state = {k: lib.metrics.create_reset_metric(f, scope=k, thresholds=thresholds) for k, f in names.items()}
-    state["brier"] = lib.metrics.create_reset_metric(lib.metrics.mean_squared_error, scope="brier")
-    state["auc"] = lib.metrics.create_reset_metric(lib.metrics.auc, scope="auc")
-    for value, update, reset in state.values():
-        reset()
-        update(all_y, avg_pred)
-    tp, fp, fn, tn = (state[k][0]() for k in ("tp", "fp", "fn", "tn"))
-    test_conf_matrix = lib.metrics.confusion_matrix(tp[-1], fp[-1], fn[-1], tn[-1])
-    test_brier, test_auc = state["brier"][0](), state["auc"][0]()
-    test_specificities = tn / (tn + fp + np.float32(KEPSILON))
-    test_sensitivities = tp / (tp + fn + np.float32(KEPSILON))
-
-    print(f"Brier score: {test_brier:6.4}, AUC: {test_auc:10.8}")
-    print(f"Confusion matrix at operating threshold {operating_threshold:0.3f}")
-    print(test_conf_matrix[0])
-    print("Specificity: {0:0.4f}, Sensitivity: {1:0.4f} at Operating Threshold {2:0.4f}.".format(
-        test_specificities[-1], test_sensitivities[-1], thresholds[-1]))
-    os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
-    with open(save_path, "w") as f:
-        w = csv.writer(f, delimiter=" ")
-        w.writerow(["threshold", "specificity", "sensitivity"])
-        for idx in range(NUM_THRESHOLDS):
-            w.writerow(["{:0.4f}".format(v) for v in (thresholds[idx], test_specificities[idx],
-                                                       test_sensitivities[idx])])
-    if dist:
-        dist.destroy_process_group()
+    if r.dist:   # gather every rank's batches to rank 0, restore dataset order
+        gathered = [None] * r.world
+        r.dist.all_gather_object(gathered, (order, preds, labels))
+        if r.rank == 0:
+            preds, labels = merge_ranks(gathered, batch_size, len(load_model_paths))
+    if not r.dist or r.rank == 0:
+        score(preds, labels, thresholds, save_path, attribution, batch_size)
+    if r.dist:
+        r.dist.destroy_process_group()
     return 0
 
 

@@ -16,6 +16,10 @@ from lib import metrics as M
 
 
 class Session:
+    """engine: a jr.Engine -- or None for a pure scorer (evaluate.py: update, value,
+    confusion_matrix, specificities, sensitivities over predictions computed elsewhere;
+    device_metrics stays False and nothing under `model` below may be called)."""
+
     def __init__(self, engine, thresholds=None, num_thresholds: int = 200, kepsilon: float = 1e-7,
                  device_metrics: bool = False):
         self.engine = engine
@@ -38,6 +42,8 @@ class Session:
         # engine's staged feed, and train_batch / predict_enqueue return without waiting;
         # pull_metrics() brings the sums into the host states above once per pass
         self.device_metrics = bool(device_metrics)
+        if self.device_metrics and engine is None:
+            raise ValueError("device_metrics needs an engine: a Session without one only scores")
         if self.device_metrics:
             engine.metrics_init(self.thresholds + list(self.metrics["auc"][0].__self__.thresholds))
         # data-parallel ranks: reduce(vec float64) -> elementwise sum over ranks;
@@ -91,6 +97,33 @@ class Session:
     def sensitivities(self):
         tp, fn = self.value("tp"), self.value("fn")
         return tp / (tp + fn + np.float32(self.kepsilon))
+
+    # ------------------------------------------------------ a metrics pass
+    # begin_pass / score_batch per batch / end_pass: the one place that knows whether the
+    # streaming states of a pass live on the host or on the device
+    def begin_pass(self, *names) -> None:
+        """Zero the states of `names` ahead of a pass (and the device sums, where they are kept there)."""
+        self.reset(*names)
+        if self.device_metrics:
+            self.metrics_reset()
+
+    def score_batch(self, images, labels, *names) -> Optional[np.ndarray]:
+        """One batch of a pass: its forward and the update of `names`.  Returns the
+        probabilities -- or None with device_metrics, where nothing is waited for
+        (the device keeps every state; end_pass reads the ones it is asked for)."""
+        if self.device_metrics:
+            self.predict_enqueue(images, labels)
+            return None
+        probs = self.predict(images, labels)
+        self.update(labels, probs, *names)
+        return probs
+
+    def end_pass(self, *names) -> None:
+        """Close a pass: the device sums come into the host states (one synchronise),
+        then the states are summed over the ranks (collective, as sync_metrics)."""
+        if self.device_metrics:
+            self.pull_metrics(*names)
+        self.sync_metrics(*names)
 
     # ------------------------------------------------------------- model
     def predict(self, images, labels=None) -> np.ndarray:

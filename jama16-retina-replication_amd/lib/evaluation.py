@@ -15,12 +15,14 @@ keeps its arguments and outputs:
     StopIteration ends the pass (the OutOfRangeError of the reference).
 `sess` is a jr.session.Session (engine + metric states).  With
 Session(device_metrics=True) the default path keeps the streaming states on
-the GPU for the pass (predict_enqueue per batch, one pull_metrics at the end);
+the GPU for the pass (Session.begin_pass / score_batch / end_pass decide);
 custom_tensors always take the host path.
 """
 from __future__ import annotations
 
 import numpy as np
+
+METRICS = ("tp", "fp", "fn", "tn", "brier", "auc")
 
 
 def _batches(init_op, feed_dict_fn, feed_dict_args):
@@ -35,48 +37,35 @@ def _batches(init_op, feed_dict_fn, feed_dict_args):
         yield fd["x"], fd["y"]
 
 
+def _tensor(sess, name, labels, probs):
+    if name in ("predictions", "predictions:0", "predictions/Sigmoid:0"):
+        return probs
+    if name in ("labels", "y", "y:0"):
+        return np.asarray(labels, np.float32).reshape(len(probs), -1)
+    if name == "logits":
+        return sess.engine.logits[:len(probs)].cpu().numpy().reshape(len(probs), -1)
+    raise KeyError(f"unknown tensor {name!r}")
+
+
 def perform_test(sess, init_op, summary_writer=None, epoch=None,
                  feed_dict_fn=None, feed_dict_args={}, custom_tensors=[]):
-    if len(custom_tensors) == 0:
-        sess.reset("tp", "fp", "fn", "tn", "brier", "auc")
-
-    # a session that keeps its metrics on the device (Session(device_metrics=True)): every
-    # batch is enqueued, the sums come back once, and the report below reads them as ever
-    on_device = len(custom_tensors) == 0 and getattr(sess, "device_metrics", False)
-    if on_device:
-        sess.metrics_reset()
-        for images, labels in _batches(init_op, feed_dict_fn, feed_dict_args):
-            sess.predict_enqueue(images, labels)
-        sess.pull_metrics("tp", "fp", "fn", "tn", "brier", "auc")
-
-    batch_results = []
-    for images, labels in ([] if on_device else _batches(init_op, feed_dict_fn, feed_dict_args)):
-        probs = sess.predict(images, labels)
-        if len(custom_tensors) == 0:
-            sess.update(labels, probs, "tp", "fp", "fn", "tn", "brier", "auc")
-        else:
-            out = []
-            for name in custom_tensors:
-                if name in ("predictions", "predictions:0", "predictions/Sigmoid:0"):
-                    out.append(probs)
-                elif name in ("labels", "y", "y:0"):
-                    out.append(np.asarray(labels, np.float32).reshape(len(probs), -1))
-                elif name == "logits":
-                    out.append(sess.engine.logits[:len(probs)].cpu().numpy().reshape(len(probs), -1))
-                else:
-                    raise KeyError(f"unknown tensor {name!r}")
-            batch_results.append(out)
-
-    if len(custom_tensors) > 0:
+    batches = _batches(init_op, feed_dict_fn, feed_dict_args)
+    if len(custom_tensors) > 0:         # always on the host: the caller wants every batch's values
+        batch_results = []
+        for images, labels in batches:
+            probs = sess.predict(images, labels)
+            batch_results.append([_tensor(sess, name, labels, probs) for name in custom_tensors])
         if not batch_results:
             return [np.zeros((0, 1), np.float32) for _ in custom_tensors]
         return [np.vstack(x) for x in zip(*batch_results)]
 
-    # data-parallel ranks each ran their own batches: sum the metric states
-    # (no-op for one process) so every rank reads the same Brier / AUC
-    sync = getattr(sess, "sync_metrics", None)
-    if sync is not None:
-        sync("tp", "fp", "fn", "tn", "brier", "auc")
+    # the session knows where its streaming states live during the pass; data-parallel ranks each
+    # run their own batches, and end_pass sums the states (no-op for one process) so every rank
+    # reads the same Brier / AUC
+    sess.begin_pass(*METRICS)
+    for images, labels in batches:
+        sess.score_batch(images, labels, *METRICS)
+    sess.end_pass(*METRICS)
     test_conf_matrix = sess.confusion_matrix()
     test_brier = sess.value("brier")
     test_auc = sess.value("auc")

@@ -12,7 +12,6 @@ images are channels_last (Q3: the reference's channels_first path is a
 reshape that scrambles pixels, so it is not reproduced).
 """
 import argparse
-import csv
 import os
 import random
 import sys
@@ -68,6 +67,78 @@ class _Parser(argparse.ArgumentParser):
         if ns.dropout_seed is not None and ns.dropout is None:
             self.error("--dropout_seed needs --dropout")
         return ns
+
+
+# ---- argparse types: a whole number from a bound, a finite float under a test, and the comma lists
+def _int_arg(lo, what):
+    """The type of a whole number >= lo, refused as 'expected <what>, got ...'."""
+    def parse(text):
+        try:
+            v = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
+        if v < lo:
+            raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
+        return v
+    return parse
+
+
+def _float_arg(text, ok, what):
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
+    if not (np.isfinite(v) and ok(v)):
+        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
+    return v
+
+
+def _positive_float(text):
+    return _float_arg(text, lambda v: v > 0, "a finite value > 0")
+
+
+def _nonnegative_float(text):
+    return _float_arg(text, lambda v: v >= 0, "a finite value >= 0")
+
+
+def _unit_arg(what):
+    """The type of a float in [0, 1)."""
+    return lambda text: _float_arg(text, lambda v: 0.0 <= v < 1.0, what)
+
+
+# augmentation
+def _range_arg(text):
+    """'LO,HI' -> (lo, hi)."""
+    try:
+        lo, hi = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected LO,HI, got {text!r}")
+    return lo, hi
+
+
+# the optimizer recipe
+def _decay_arg(text):
+    """'RATE,EPOCHS' -> (rate, epochs): a rate > 0 and a whole number of epochs >= 1."""
+    try:
+        rate, epochs = text.split(",")
+        rate, epochs = _positive_float(rate), int(epochs)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected RATE,EPOCHS, got {text!r}")
+    if epochs < 1:
+        raise argparse.ArgumentTypeError(f"expected RATE,EPOCHS with EPOCHS >= 1, got {text!r}")
+    return rate, epochs
+
+
+def _rmsprop_arg(text):
+    """'RHO,MOMENTUM,EPS' -> (rho, momentum, eps): rho and momentum in [0, 1), eps > 0."""
+    what = "RHO,MOMENTUM,EPS with RHO and MOMENTUM in [0, 1) and EPS > 0"
+    try:
+        rho, momentum, eps = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
+    if not (0.0 <= rho < 1.0 and 0.0 <= momentum < 1.0 and eps > 0.0 and np.isfinite(eps)):
+        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
+    return rho, momentum, eps
 
 
 def build_parser():
@@ -144,7 +215,7 @@ def build_parser():
                    help="base learning rate (default {})".format(LEARNING_RATE))
     p.add_argument("--lr_decay", type=_decay_arg, default=None, metavar="RATE,EPOCHS",
                    help="exponential staircase: multiply the learning rate by RATE every EPOCHS epochs")
-    p.add_argument("--lr_warmup", type=_count_arg, default=None, metavar="STEPS",
+    p.add_argument("--lr_warmup", type=_int_arg(0, "a count >= 0"), default=None, metavar="STEPS",
                    help="linear warmup of the learning rate from LR/STEPS over the first STEPS steps")
     p.add_argument("--weight_decay", type=_nonnegative_float, default=None, metavar="WD",
                    help="L2 weight decay on the conv filters and the dense kernel (never BN betas or the bias)")
@@ -157,7 +228,8 @@ def build_parser():
                    help="the optimizer (default: nesterov, or sgd with -sgd; not together with -sgd)")
     p.add_argument("--rmsprop", type=_rmsprop_arg, default=None, metavar="RHO,MOMENTUM,EPS",
                    help="RMSProp's decay, momentum and epsilon (default 0.9,0.9,1.0; with --optimizer rmsprop)")
-    p.add_argument("--weight_ema", type=_ema_decay_arg, nargs="?", const=0.9999, default=None, metavar="DECAY",
+    p.add_argument("--weight_ema", type=_unit_arg("a decay in [0, 1)"), nargs="?", const=0.9999, default=None,
+                   metavar="DECAY",
                    help="keep a moving average of the weights (decay 0.9999 when given bare) on the GPU: validation, "
                         "early stopping and the final sweep then run on the averaged weights, and every checkpoint "
                         "carries both the trained weights and the average (<path>.ema, evaluate.py --weights averaged)")
@@ -166,7 +238,7 @@ def build_parser():
     # the loss recipe and dropout (not in the reference: off by default; jr.h jr_loss_spec, jr_dropout_*).  With any
     # of the first three the `Xent:` of the status line and the validation loss are the training objective
     # (smoothed, weighted, focal), no longer the plain cross-entropy
-    p.add_argument("--label_smoothing", type=_smoothing_arg, default=None, metavar="E",
+    p.add_argument("--label_smoothing", type=_unit_arg("a smoothing in [0, 1)"), default=None, metavar="E",
                    help="smooth the labels towards 1/2 by E in [0, 1) (0.1 in the published Inception-v3 recipe); "
                         "the `Xent:` status value is then the training objective")
     p.add_argument("--pos_weight", type=_positive_float, default=None, metavar="W",
@@ -175,18 +247,19 @@ def build_parser():
     p.add_argument("--focal_gamma", type=_nonnegative_float, default=None, metavar="G",
                    help="focal exponent G >= 0 on both terms of the loss; the `Xent:` status value is then the "
                         "training objective")
-    p.add_argument("--dropout", type=_dropout_arg, default=None, metavar="RATE",
+    p.add_argument("--dropout", type=_unit_arg("a rate in [0, 1)"), default=None, metavar="RATE",
                    help="drop the pooled features before the dense layer at RATE in [0, 1) in training steps only "
                         "(0.2 in the published Inception-v3 recipe); a new mask every step, drawn on the GPU")
     p.add_argument("--dropout_seed", type=int, default=None, metavar="N",
                    help="seed of the dropout masks (default 0; rank r draws stream r of it; with --dropout)")
     # gradient accumulation (not in the reference: off by default; jr.h jr_grad_accumulate)
-    p.add_argument("--accum_steps", type=_accum_arg, default=None, metavar="K",
+    p.add_argument("--accum_steps", type=_int_arg(1, "a count >= 1"), default=None, metavar="K",
                    help="accumulate K batches of {0} per optimizer update ({0} * K images per GPU and update, every "
                         "batch under its own BN statistics; default 1): --lr_decay epochs, --lr_warmup and the "
                         "`Step:` of the status line then count updates, and a partial group at the end of an epoch "
                         "is closed there".format(TRAIN_BATCH_SIZE))
-    p.add_argument("--status_every", type=_status_arg, default=1, metavar="N",
+    p.add_argument("--status_every", type=_int_arg(1, "a whole number of batches >= 1"), default=1,
+                   metavar="N",
                    help="print the status line every N batches (default 1: after every batch, which waits for "
                         "it).  N > 1 keeps the loss, the gradient norm and the Brier and threshold counts of "
                         "training, validation and the final sweep on the GPU, feeds batches through pinned "
@@ -196,44 +269,82 @@ def build_parser():
     return p
 
 
-def _status_arg(text):
-    n = int(text)
-    if n < 1:
-        raise argparse.ArgumentTypeError("--status_every: a whole number of batches >= 1")
-    return n
-
-
-def _accum_arg(text):
-    try:
-        v = int(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"expected a count >= 1, got {text!r}")
-    if v < 1:
-        raise argparse.ArgumentTypeError(f"expected a count >= 1, got {text!r}")
-    return v
-
-
-def accum_meta(args):
-    """What --accum_steps adds to the checkpoint .meta and to the Engine's keywords (nothing without it)."""
-    return {} if args.accum_steps is None else {"accum_steps": args.accum_steps}
-
-
-def accum_line(args, world, batches):
-    """The start-up line of --accum_steps (None without it); batches: per rank and epoch."""
-    if args.accum_steps is None:
+# ---- what each feature's flags mean: Engine keywords, checkpoint .meta entries, start-up lines
+def augment_spec(args):
+    """The jr.augment.AugmentSpec of the --augment* flags (None: --augment is off)."""
+    if not args.augment:
         return None
-    from jr.schedule import accum_groups
-    return ("Gradient accumulation: {0} batches of {1} per update, {2} images per update, {3} updates per epoch"
-            .format(args.accum_steps, TRAIN_BATCH_SIZE, TRAIN_BATCH_SIZE * args.accum_steps * world,
-                    accum_groups(batches, args.accum_steps)[1]))
+    from jr.augment import AugmentSpec
+    over = {"flip": not args.no_augment_flip}
+    for key in ("hue", "saturation", "contrast", "brightness"):
+        v = getattr(args, "augment_" + key)
+        if v is not None:
+            over[key] = v
+    return AugmentSpec(**over)
 
 
-def _smoothing_arg(text):
-    return _float_arg(text, lambda v: 0.0 <= v < 1.0, "a smoothing in [0, 1)")
+def warp_spec(args):
+    """The jr.augment.WarpSpec of the --augment_rotate / _zoom / _shift flags
+    (None: none of them is given); an omitted one takes its identity value."""
+    if not args.augment or all(getattr(args, f) is None for f in GEOMETRY_FLAGS):
+        return None
+    from jr.augment import WarpSpec
+    return WarpSpec(rotate=args.augment_rotate or 0.0, zoom=args.augment_zoom or (1.0, 1.0),
+                    shift=args.augment_shift or 0.0)
 
 
-def _dropout_arg(text):
-    return _float_arg(text, lambda v: 0.0 <= v < 1.0, "a rate in [0, 1)")
+RECIPE_FLAGS = ("learning_rate", "lr_decay", "lr_warmup", "weight_decay", "clip_norm")
+
+
+def opt_recipe(args):
+    """The optimizer recipe of the flags as saved in the checkpoint .meta
+    (None: none of them is given, the reference's settings)."""
+    if all(getattr(args, f) is None for f in RECIPE_FLAGS):
+        return None
+    return {"learning_rate": LEARNING_RATE if args.learning_rate is None else args.learning_rate,
+            "lr_decay": None if args.lr_decay is None else list(args.lr_decay),
+            "lr_warmup": args.lr_warmup or 0, "weight_decay": args.weight_decay or 0.0, "clip_norm": args.clip_norm}
+
+
+def opt_engine_kwargs(args):
+    """Engine keywords of the recipe: the device optimizer path for every flag
+    but a bare --learning_rate (none at all without a flag)."""
+    if all(getattr(args, f) is None for f in RECIPE_FLAGS[1:]):
+        return {}
+    return {"weight_decay": args.weight_decay or 0.0, "clip_norm": args.clip_norm, "device_lr": True}
+
+
+RMSPROP_DEFAULT = (0.9, 0.9, 1.0)
+
+
+def optimizer_name(args):
+    """The Engine's optimizer of the flags: --optimizer, else today's choice."""
+    if args.optimizer is not None:
+        return args.optimizer
+    return "sgd" if args.vanilla_sgd else ("nesterov" if USE_NESTEROV else "momentum")
+
+
+def optimizer_meta(args):
+    """What --optimizer / --rmsprop / --weight_ema add to the recipe saved in the
+    checkpoint .meta (nothing without them)."""
+    out = {}
+    if args.optimizer is not None:
+        out["name"] = args.optimizer
+        if args.optimizer == "rmsprop":
+            out["rmsprop"] = dict(zip(("rho", "momentum", "epsilon"), args.rmsprop or RMSPROP_DEFAULT))
+    if args.weight_ema is not None:
+        out["weight_ema"] = {"decay": args.weight_ema, "warm": not args.weight_ema_no_warm}
+    return out
+
+
+def ema_engine_kwargs(args):
+    """Engine keywords of --optimizer rmsprop and --weight_ema (none without them)."""
+    kw = {}
+    if args.optimizer == "rmsprop":
+        kw.update(zip(("rmsprop_rho", "rmsprop_momentum", "rmsprop_eps"), args.rmsprop or RMSPROP_DEFAULT))
+    if args.weight_ema is not None:
+        kw.update(weight_ema=args.weight_ema, weight_ema_warm=not args.weight_ema_no_warm)
+    return kw
 
 
 LOSS_FLAGS = ("label_smoothing", "pos_weight", "focal_gamma", "dropout")
@@ -280,146 +391,50 @@ def objective_line(args):
     return "Objective: " + ", ".join(parts)
 
 
-RMSPROP_DEFAULT = (0.9, 0.9, 1.0)
+def accum_meta(args):
+    """What --accum_steps adds to the checkpoint .meta and to the Engine's keywords (nothing without it)."""
+    return {} if args.accum_steps is None else {"accum_steps": args.accum_steps}
 
 
-def _rmsprop_arg(text):
-    """'RHO,MOMENTUM,EPS' -> (rho, momentum, eps): rho and momentum in [0, 1), eps > 0."""
-    what = "RHO,MOMENTUM,EPS with RHO and MOMENTUM in [0, 1) and EPS > 0"
-    try:
-        rho, momentum, eps = (float(v) for v in text.split(","))
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
-    if not (0.0 <= rho < 1.0 and 0.0 <= momentum < 1.0 and eps > 0.0 and np.isfinite(eps)):
-        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
-    return rho, momentum, eps
+def accum_line(args, world, batches):
+    """The start-up line of --accum_steps (None without it); batches: per rank and epoch."""
+    if args.accum_steps is None:
+        return None
+    from jr.schedule import accum_groups
+    return ("Gradient accumulation: {0} batches of {1} per update, {2} images per update, {3} updates per epoch"
+            .format(args.accum_steps, TRAIN_BATCH_SIZE, TRAIN_BATCH_SIZE * args.accum_steps * world,
+                    accum_groups(batches, args.accum_steps)[1]))
 
 
-def _ema_decay_arg(text):
-    return _float_arg(text, lambda v: 0.0 <= v < 1.0, "a decay in [0, 1)")
-
-
-def optimizer_name(args):
-    """The Engine's optimizer of the flags: --optimizer, else today's choice."""
-    if args.optimizer is not None:
-        return args.optimizer
-    return "sgd" if args.vanilla_sgd else ("nesterov" if USE_NESTEROV else "momentum")
-
-
-def optimizer_meta(args):
-    """What --optimizer / --rmsprop / --weight_ema add to the recipe saved in the
-    checkpoint .meta (nothing without them)."""
-    out = {}
-    if args.optimizer is not None:
-        out["name"] = args.optimizer
-        if args.optimizer == "rmsprop":
-            out["rmsprop"] = dict(zip(("rho", "momentum", "epsilon"), args.rmsprop or RMSPROP_DEFAULT))
-    if args.weight_ema is not None:
-        out["weight_ema"] = {"decay": args.weight_ema, "warm": not args.weight_ema_no_warm}
-    return out
-
-
-def ema_engine_kwargs(args):
-    """Engine keywords of --optimizer rmsprop and --weight_ema (none without them)."""
-    kw = {}
-    if args.optimizer == "rmsprop":
-        kw.update(zip(("rmsprop_rho", "rmsprop_momentum", "rmsprop_eps"), args.rmsprop or RMSPROP_DEFAULT))
-    if args.weight_ema is not None:
-        kw.update(weight_ema=args.weight_ema, weight_ema_warm=not args.weight_ema_no_warm)
+def engine_kwargs(args, rank, local):
+    """Every keyword the training Engine is built with: the reference's settings, then what each feature adds."""
+    kw = {"device": local, "optimizer": optimizer_name(args),
+          "lr": LEARNING_RATE if args.learning_rate is None else args.learning_rate, "momentum": MOMENTUM,
+          "seed": args.seed, "dtype": args.dtype, "conv_math": args.conv_math if args.dtype == "f32" else "bf16",
+          "tiles": "pinned" if args.tiles == "pinned" else "heuristic"}
+    if args.bn_moving is not None:
+        kw["bn_moving"] = args.bn_moving
+    for more in (opt_engine_kwargs(args), ema_engine_kwargs(args), loss_engine_kwargs(args, rank), accum_meta(args)):
+        kw.update(more)
     return kw
 
 
-def _float_arg(text, ok, what):
-    try:
-        v = float(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
-    if not (np.isfinite(v) and ok(v)):
-        raise argparse.ArgumentTypeError(f"expected {what}, got {text!r}")
-    return v
-
-
-def _positive_float(text):
-    return _float_arg(text, lambda v: v > 0, "a finite value > 0")
-
-
-def _nonnegative_float(text):
-    return _float_arg(text, lambda v: v >= 0, "a finite value >= 0")
-
-
-def _count_arg(text):
-    try:
-        v = int(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"expected a count >= 0, got {text!r}")
-    if v < 0:
-        raise argparse.ArgumentTypeError(f"expected a count >= 0, got {text!r}")
-    return v
-
-
-def _decay_arg(text):
-    """'RATE,EPOCHS' -> (rate, epochs): a rate > 0 and a whole number of epochs >= 1."""
-    try:
-        rate, epochs = text.split(",")
-        rate, epochs = _positive_float(rate), int(epochs)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"expected RATE,EPOCHS, got {text!r}")
-    if epochs < 1:
-        raise argparse.ArgumentTypeError(f"expected RATE,EPOCHS with EPOCHS >= 1, got {text!r}")
-    return rate, epochs
-
-
-RECIPE_FLAGS = ("learning_rate", "lr_decay", "lr_warmup", "weight_decay", "clip_norm")
-
-
-def opt_recipe(args):
-    """The optimizer recipe of the flags as saved in the checkpoint .meta
-    (None: none of them is given, the reference's settings)."""
-    if all(getattr(args, f) is None for f in RECIPE_FLAGS):
-        return None
-    return {"learning_rate": LEARNING_RATE if args.learning_rate is None else args.learning_rate,
-            "lr_decay": None if args.lr_decay is None else list(args.lr_decay),
-            "lr_warmup": args.lr_warmup or 0, "weight_decay": args.weight_decay or 0.0, "clip_norm": args.clip_norm}
-
-
-def opt_engine_kwargs(args):
-    """Engine keywords of the recipe: the device optimizer path for every flag
-    but a bare --learning_rate (none at all without a flag)."""
-    if all(getattr(args, f) is None for f in RECIPE_FLAGS[1:]):
-        return {}
-    return {"weight_decay": args.weight_decay or 0.0, "clip_norm": args.clip_norm, "device_lr": True}
-
-
-def _range_arg(text):
-    """'LO,HI' -> (lo, hi)."""
-    try:
-        lo, hi = (float(v) for v in text.split(","))
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"expected LO,HI, got {text!r}")
-    return lo, hi
-
-
-def augment_spec(args):
-    """The jr.augment.AugmentSpec of the --augment* flags (None: --augment is off)."""
-    if not args.augment:
-        return None
-    from jr.augment import AugmentSpec
-    over = {"flip": not args.no_augment_flip}
-    for key in ("hue", "saturation", "contrast", "brightness"):
-        v = getattr(args, "augment_" + key)
-        if v is not None:
-            over[key] = v
-    return AugmentSpec(**over)
-
-
-def warp_spec(args):
-    """The jr.augment.WarpSpec of the --augment_rotate / _zoom / _shift flags
-    (None: none of them is given); an omitted one takes its identity value."""
-    if not args.augment or all(getattr(args, f) is None for f in GEOMETRY_FLAGS):
-        return None
-    from jr.augment import WarpSpec
-    return WarpSpec(rotate=args.augment_rotate or 0.0, zoom=args.augment_zoom or (1.0, 1.0),
-                    shift=args.augment_shift or 0.0)
+def run_meta(args, aug_spec, geo_spec):
+    """What the run adds to every checkpoint's .meta beyond epoch, AUC and tile table:
+    the augmentation, the optimizer and loss recipes, the accumulation and --status_every in use."""
+    meta = {}
+    if aug_spec:
+        meta["augment"] = {"spec": aug_spec.to_meta(), "seed": args.augment_seed}
+    if geo_spec:
+        meta["augment_warp"] = {"spec": geo_spec.to_meta(), "seed": args.augment_seed}
+    if opt_recipe(args) or optimizer_meta(args):
+        meta["optimizer"] = {**(opt_recipe(args) or {}), **optimizer_meta(args)}
+    if loss_meta(args):
+        meta["loss"] = loss_meta(args)
+    meta.update(accum_meta(args))
+    if args.status_every > 1:
+        meta["status_every"] = args.status_every
+    return meta
 
 
 def status_line(epoch, num_epochs, batch_num, xent, i_step=None):
@@ -445,341 +460,366 @@ def load_tile_table(path: str) -> dict:
     return meta["tile_table"]
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
-    import torch
-    from jr import checkpoint
+# ---- the pieces of a run, in the order main() calls them
+def open_datasets(args, r):
+    """The training and validation sets.  Data parallel: every rank walks the same shuffled stream
+    of record handles (rank 0's seed) and decodes only its own batches (b % world == rank);
+    validation and the final sweep likewise, the metric counts summed over ranks (Session.end_pass)."""
+    seed = args.shuffle_seed if args.shuffle_seed is not None else int.from_bytes(os.urandom(4), "little")
+    if r.dist:
+        import torch
+        t = torch.tensor([seed], dtype=torch.int64, device=r.coll_dev)
+        r.dist.broadcast(t, 0)
+        seed = int(t.item())
+
+    def dataset(path, batch, seed):
+        return lib.dataset.initialize_dataset(
+            path, batch, num_workers=NUM_WORKERS, prefetch_buffer_size=2 * TRAIN_BATCH_SIZE,
+            shuffle_buffer_size=SHUFFLE_BUFFER_SIZE, image_data_format="channels_last", num_channels=NUM_CHANNELS,
+            image_dim=[args.image_size, args.image_size], seed=seed, decode_dtype="uint8",
+            shard=(r.rank, r.world) if r.dist else None)
+    return dataset(args.train_dir, TRAIN_BATCH_SIZE, seed), dataset(args.val_dir, VAL_BATCH_SIZE, seed + 1)
+
+
+def build_engine(args, r):
+    """The Engine of the flags with its conv tile table: --tile_table's, or the one
+    rank 0 timed under --tiles autotune (broadcast), else the engine's own."""
     from jr.engine import Engine
-    from jr.session import Session
-    from jr.summary import FileWriter
-
-    random.seed(432)                       # train.py:17
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    if rank == 0:       # one copy of the reference's header lines, whatever the rank count
-        print(f"Numpy version: {np.__version__}")
-        print(f"Torch version: {torch.__version__} (libjr / MI355X backend)")
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    # rehearsal knobs for the N > 1 path on a one-GPU box (as evaluate.py's
-    # and bench.py's): JR_ONE_DEVICE=1 puts every rank on cuda:0,
-    # JR_DIST_BACKEND=gloo replaces RCCL (which refuses two ranks on one device)
-    if os.environ.get("JR_ONE_DEVICE") == "1" or os.environ.get("JR_BENCH_ONE_DEVICE") == "1":
-        local = 0
-    backend = os.environ.get("JR_DIST_BACKEND", "nccl")
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        torch.cuda.set_device(local)
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-        else:
-            dist.init_process_group(backend)
-    # small host-side collectives (seed, metric sums, replica digests) run on
-    # device tensors under RCCL, host tensors under gloo
-    coll_dev = "cuda" if backend == "nccl" else "cpu"
-
-    if rank == 0:
-        print(f"""
-Training images folder: {args.train_dir},
-Validation images folder: {args.val_dir},
-Saving model and graph checkpoints at: {args.save_model_path},
-Saving summaries at: {args.save_summaries_dir},
-Saving operating points at: {args.save_operating_thresholds_path},
-Use SGD: {bool(args.vanilla_sgd)}
-""")
-
-    thresholds = lib.metrics.generate_thresholds(NUM_THRESHOLDS, KEPSILON) + [0.5]
-    size = [args.image_size, args.image_size]
-    shuffle_seed = args.shuffle_seed if args.shuffle_seed is not None else int.from_bytes(os.urandom(4), "little")
-    if dist:   # every rank walks the same shuffled stream of record handles
-        t = torch.tensor([shuffle_seed], dtype=torch.int64, device=coll_dev)
-        dist.broadcast(t, 0)
-        shuffle_seed = int(t.item())
-    # data parallel: each rank decodes only its own batches (b % world ==
-    # rank) of the common stream; validation and the final sweep likewise,
-    # with the metric counts summed over ranks (Session.sync_metrics)
-    shard = (rank, world) if dist else None
-    train_dataset = lib.dataset.initialize_dataset(
-        args.train_dir, TRAIN_BATCH_SIZE, num_workers=NUM_WORKERS,
-        prefetch_buffer_size=2 * TRAIN_BATCH_SIZE, shuffle_buffer_size=SHUFFLE_BUFFER_SIZE,
-        image_data_format="channels_last", num_channels=NUM_CHANNELS, image_dim=size,
-        seed=shuffle_seed, decode_dtype="uint8", shard=shard)
-    val_dataset = lib.dataset.initialize_dataset(
-        args.val_dir, VAL_BATCH_SIZE, num_workers=NUM_WORKERS,
-        prefetch_buffer_size=2 * TRAIN_BATCH_SIZE, shuffle_buffer_size=SHUFFLE_BUFFER_SIZE,
-        image_data_format="channels_last", num_channels=NUM_CHANNELS, image_dim=size,
-        seed=shuffle_seed + 1, decode_dtype="uint8", shard=shard)
-
     engine = Engine(max(TRAIN_BATCH_SIZE, VAL_BATCH_SIZE), args.image_size, args.image_size,
-                    device=local, optimizer=optimizer_name(args),
-                    lr=LEARNING_RATE if args.learning_rate is None else args.learning_rate, momentum=MOMENTUM,
-                    seed=args.seed, dtype=args.dtype,
-                    conv_math=args.conv_math if args.dtype == "f32" else "bf16",
-                    tiles="pinned" if args.tiles == "pinned" else "heuristic",
-                    **({} if args.bn_moving is None else {"bn_moving": args.bn_moving}), **opt_engine_kwargs(args),
-                    **ema_engine_kwargs(args), **loss_engine_kwargs(args, rank),
-                    **accum_meta(args))
+                    **engine_kwargs(args, r.rank, r.local))
     table = None
     if args.tile_table:
         table = load_tile_table(args.tile_table)
-    elif args.tiles == "autotune" and rank == 0:
+    elif args.tiles == "autotune" and r.rank == 0:
         engine.autotune()
         table = engine.tile_table()
-    if dist and args.tiles == "autotune" and not args.tile_table:
+    if r.dist and args.tiles == "autotune" and not args.tile_table:
         box = [table]
-        dist.broadcast_object_list(box, 0)
+        r.dist.broadcast_object_list(box, 0)
         table = box[0]
     if table is not None:
         engine.set_tile_table(table)
-    # --status_every N > 1: the loop that runs ahead of the host (jr.session device_metrics, the
-    # engine's step log with room for N batches and the flush of a partial accumulation group)
+    return engine
+
+
+def build_session(args, engine, thresholds, r):
+    """The Session over the engine.  --status_every N > 1 is the loop that runs ahead of the host:
+    the metrics stay on the device and the engine logs its steps, with room for N batches and the
+    flush of a partial accumulation group.  Data parallel: the gradient exchange and the metric sum."""
+    from jr.session import Session
     run_ahead = args.status_every > 1
     sess = Session(engine, thresholds, NUM_THRESHOLDS, KEPSILON, **({"device_metrics": True} if run_ahead else {}))
-    sess.rank = rank
+    sess.rank = r.rank
     if run_ahead:
         engine.step_log_enable(args.status_every + 1)
-    # one parameter table per training batch, each rank from its own stream
-    aug_spec = augment_spec(args)
-    aug_rng = np.random.Generator(np.random.PCG64([args.augment_seed, rank])) if aug_spec else None
-    # what the run adds to the checkpoint .meta: the augmentation and the optimizer recipe in use
-    run_meta = {"augment": {"spec": aug_spec.to_meta(), "seed": args.augment_seed}} if aug_spec else {}
-    # the geometry draws from a generator of its own: the colour draws of a seed
-    # are the same with and without it
-    geo_spec = warp_spec(args)
-    geo_rng = np.random.Generator(np.random.PCG64([args.augment_seed, rank, 1])) if geo_spec else None
-    if geo_spec:
-        run_meta["augment_warp"] = {"spec": geo_spec.to_meta(), "seed": args.augment_seed}
-    recipe = opt_recipe(args)
-    if recipe or optimizer_meta(args):
-        run_meta["optimizer"] = {**(recipe or {}), **optimizer_meta(args)}
-    if loss_meta(args):
-        run_meta["loss"] = loss_meta(args)
-        if rank == 0:
-            print(objective_line(args))
-    run_meta.update(accum_meta(args))
-    if run_ahead:
-        run_meta["status_every"] = args.status_every
-    # --weight_ema: validation, early stopping and the final sweep read the averaged weights
-    import contextlib
-    averaged = engine.averaged_weights if args.weight_ema is not None else contextlib.nullcontext
-    device_opt = bool(opt_engine_kwargs(args))
-    if dist:
+    if r.dist:
+        import torch
         from jr.dist import BucketAllReduce
-        sess.allreduce = BucketAllReduce(engine, world)
+        sess.allreduce = BucketAllReduce(engine, r.world)
 
         def _sum_over_ranks(vec):
-            t = torch.from_numpy(vec).to(coll_dev)
-            dist.all_reduce(t)
+            t = torch.from_numpy(vec).to(r.coll_dev)
+            r.dist.all_reduce(t)
             return t.cpu().numpy()
         sess.reduce = _sum_over_ranks
+    return sess
 
-    def check_replicas(epoch):
-        """Data parallel: every rank applies the same update to the same
-        reduced gradient, so the replicas must stay bitwise identical; compare
-        a digest of every rank's parameters once per epoch (and dump them for
-        --replica_dump_dir); with --weight_ema the digest covers the average too."""
-        if not dist and not args.replica_dump_dir:
-            return
-        flat = engine.params_numpy()
-        if args.replica_dump_dir:
-            os.makedirs(args.replica_dump_dir, exist_ok=True)
-            np.save(os.path.join(args.replica_dump_dir, f"params_e{epoch}_r{rank}.npy"), flat)
-        if dist:
-            import hashlib
-            digest = hashlib.sha256(flat.tobytes())
-            if args.weight_ema is not None:
-                digest.update(engine.ema_numpy().tobytes())
-            digest = digest.hexdigest()
-            got = [None] * world
-            dist.all_gather_object(got, digest)
-            if len(set(got)) != 1:
-                raise RuntimeError(f"data-parallel replicas diverged after epoch {epoch}: {got}")
 
-    def bn_state():
-        """checkpoint.save's bn_moving argument (--bn_moving), else nothing."""
-        if args.bn_moving is None:
-            return {}
-        return {"bn_moving": {"stats": engine.bn_moving_numpy(), "momentum": args.bn_moving,
-                              "updates": engine.updates}}
+class Augmenter:
+    """One parameter table per training batch, each rank from its own stream.  The geometry
+    draws from a generator of its own: the colour draws of a seed are the same with and without it."""
 
-    def ema_state():
-        """checkpoint.save's weight_ema argument (--weight_ema), else nothing."""
-        if args.weight_ema is None:
-            return {}
-        return {"weight_ema": {"flat": engine.ema_numpy(), "decay": args.weight_ema,
-                               "warm": not args.weight_ema_no_warm, "updates": engine.ema_updates()}}
-    train_writer = FileWriter(os.path.join(args.save_summaries_dir, "train")) if rank == 0 else None
+    def __init__(self, args, rank):
+        self.spec, self.geo = augment_spec(args), warp_spec(args)
+        self.size = (args.image_size, args.image_size)
+        self.rng = np.random.Generator(np.random.PCG64([args.augment_seed, rank])) if self.spec else None
+        self.geo_rng = np.random.Generator(np.random.PCG64([args.augment_seed, rank, 1])) if self.geo else None
 
-    latest_peak_auc = 0.0
-    waited_epochs = 0
-    saved = False
-    steps_per_epoch = None
-    if dist:   # every rank runs the same number of steps (matching collectives)
-        steps_per_epoch = -(-train_dataset.num_records() // TRAIN_BATCH_SIZE) // world
-    # the schedule counts optimizer steps; an epoch of --lr_decay is this many of them
-    # (every rank computes the same value from the same integers: jr.schedule).  --accum_steps K:
-    # an update takes K batches (--max_steps_per_epoch still counts batches), ceil(batches / K) per epoch
-    sched_epoch = None
-    if device_opt or args.accum_steps is not None:
+    def draw(self, n):
+        """Session.train_batch's (augment, warp) of a batch of n images; (None, None) without --augment."""
+        if self.spec is None:
+            return None, None
+        from jr import augment
+        warp = augment.draw_warp(self.geo, self.geo_rng, n, *self.size) if self.geo else None
+        return augment.draw(self.spec, self.rng, n), warp
+
+
+class Schedule:
+    """The learning rate of every update on the device optimizer path (jr.schedule): the recipe's, its
+    --lr_decay epochs counted in `epoch_updates` optimizer updates (every rank computes the same
+    value from the same integers)."""
+
+    def __init__(self, recipe, epoch_updates):
+        self.base, self.warmup, self.decay = recipe["learning_rate"], recipe["lr_warmup"], None
+        if recipe["lr_decay"]:
+            self.decay = (recipe["lr_decay"][0], recipe["lr_decay"][1] * max(epoch_updates, 1))
+
+    def rate(self, step) -> float:
+        from jr.schedule import learning_rate
+        return float(learning_rate(step, self.base, self.decay, self.warmup))
+
+
+def plan_epoch(args, r, dataset):
+    """(limit, sched).  limit: the batches of an epoch under data parallelism, where every rank runs the
+    same number (matching collectives); else None.  sched: the Schedule of the device optimizer path,
+    else None.  --accum_steps K: an update takes K batches (--max_steps_per_epoch still counts batches),
+    ceil(batches / K) updates per epoch; its start-up line is printed here."""
+    device_opt = bool(opt_engine_kwargs(args))
+    if not (r.dist or device_opt or args.accum_steps is not None):
+        return None, None       # (the records are counted only where the count is used)
+    batches = -(-dataset.num_records() // TRAIN_BATCH_SIZE) // r.world
+    limit = batches if r.dist else None
+    if args.max_steps_per_epoch is not None:
+        batches = min(batches, args.max_steps_per_epoch)
+    sched = None
+    if device_opt:
         from jr.schedule import accum_groups
-        epoch_batches = -(-train_dataset.num_records() // TRAIN_BATCH_SIZE) // world
-        if args.max_steps_per_epoch is not None:
-            epoch_batches = min(epoch_batches, args.max_steps_per_epoch)
-        if device_opt:
-            sched_epoch = accum_groups(epoch_batches, args.accum_steps or 1)[1]
-        if rank == 0 and args.accum_steps is not None:
-            print(accum_line(args, world, epoch_batches))
+        sched = Schedule(opt_recipe(args), accum_groups(batches, args.accum_steps or 1)[1])
+    if r.rank == 0 and args.accum_steps is not None:
+        print(accum_line(args, r.world, batches))
+    return limit, sched
 
-    def note_update(rec=None):
-        """After an update: the device's norm, clip and skip of it (16 bytes, after a synchronise;
-        --status_every N > 1: the step log's record of it)."""
-        nonlocal clipped, skipped
-        if rec is None:
-            norm, _, skip, _ = engine.opt_step()
-        else:
-            norm, skip = float(rec["grad_norm"]), int(rec["flags"]) >> 1 & 1
-        norms.append(norm)
-        skipped += skip
+
+class UpdateTally:
+    """The optimizer updates of one epoch on the device path: every update's gradient norm, how many
+    the clip scaled and how many the non-finite guard skipped, and the last learning rate set."""
+
+    def __init__(self, clip_norm=None):
+        self.clip_norm, self.norms, self.clipped, self.skipped, self.step_lr = clip_norm, [], 0, 0, None
+
+    def note(self, norm, skip) -> None:
+        self.norms.append(norm)
+        self.skipped += skip
         # (the kernel's own decision: fp32 norm against fp32 clip_norm)
-        clipped += int(not skip and args.clip_norm is not None and np.float32(norm) > np.float32(args.clip_norm))
+        self.clipped += int(not skip and self.clip_norm is not None and np.float32(norm) > np.float32(self.clip_norm))
 
-    def drain_log():
-        """--status_every N > 1: the records since the last read (one synchronise); the updates among
-        them are noted as the default loop notes them.  Returns the newest record's loss."""
-        recs = engine.step_log_read()
-        if device_opt:
-            for rec in recs[(recs["flags"] & 1) != 0]:
-                note_update(rec)
-        return float(recs["loss"][-1]) if len(recs) else None
-    for epoch in range(args.num_epochs):
-        sess.reset("brier")
-        if run_ahead:
-            sess.metrics_reset()
-        batch_num = 0
-        step_lr, norms, clipped, skipped = None, [], 0, 0
-        it = iter(train_dataset)
-        try:
-            for images, labels in it:
-                if steps_per_epoch is not None and batch_num >= steps_per_epoch:
-                    break
-                if args.max_steps_per_epoch is not None and batch_num >= args.max_steps_per_epoch:
-                    break
-                if device_opt:
-                    from jr.schedule import learning_rate
-                    decay = recipe["lr_decay"] and (recipe["lr_decay"][0], recipe["lr_decay"][1] * max(sched_epoch, 1))
-                    step_lr = float(learning_rate(sess.global_step, recipe["learning_rate"], decay or None,
-                                                  recipe["lr_warmup"]))
-                    engine.set_lr(step_lr)
-                if aug_spec is not None:
-                    from jr import augment
-                    warp = augment.draw_warp(geo_spec, geo_rng, len(images), *size) if geo_spec else None
-                    i_global, xent, probs = sess.train_batch(images, labels,
-                                                             augment.draw(aug_spec, aug_rng, len(images)), warp)
-                else:
-                    i_global, xent, probs = sess.train_batch(images, labels)
-                if run_ahead:
-                    # nothing of this batch is on the host yet: every N-th batch reads the log
-                    if batch_num % args.status_every == args.status_every - 1:
-                        xent = drain_log()
-                        if rank == 0:
-                            print(status_line(epoch, args.num_epochs, batch_num, xent, i_global), end="\r")
-                    batch_num += 1
-                    continue
-                if device_opt and engine.accum_pending() == 0:      # (read after updates only)
-                    note_update()
-                sess.update(labels, probs, "brier")
-                if rank == 0:
-                    print(status_line(epoch, args.num_epochs, batch_num, xent, i_global), end="\r")
-                batch_num += 1
-        finally:
-            lib.dataset.close_iterator(it)
-        # --accum_steps: a partial group is closed here, so validation, early stopping, checkpoints
-        # and the replica check never see an open one (every rank ran the same number of batches)
-        if run_ahead:
-            sess.accum_flush()
-            drain_log()
-            sess.pull_metrics("brier")
-        elif sess.accum_flush() and device_opt:
-            note_update()
-        sess.sync_metrics("brier")
-        check_replicas(epoch)
-        train_brier = sess.value("brier")
-        if rank == 0:
-            print("\nEnd of epoch {0}! (Brier: {1:8.6})".format(epoch, train_brier))
-            if device_opt and norms:
-                finite = [v for v in norms if np.isfinite(v)]      # (a skipped step's norm is inf or NaN)
-                median = float(np.median(np.asarray(finite, np.float64))) if finite else float("nan")
-                print("Learning rate: {0:.6g}, median gradient norm: {1:.6g}, clipped steps: {2}, skipped steps: {3}"
-                      .format(step_lr, median, clipped, skipped))
-                train_writer.add_summary({"grad_norm": median, "learning_rate": step_lr}, epoch)
+    def median(self) -> float:
+        finite = [v for v in self.norms if np.isfinite(v)]      # (a skipped step's norm is inf or NaN)
+        return float(np.median(np.asarray(finite, np.float64))) if finite else float("nan")
 
-        # every rank gets the same val_auc (summed counts), so the early-stop
-        # decisions below agree and the collectives stay matched
-        with averaged():
-            val_auc = lib.evaluation.perform_test(sess=sess, init_op=val_dataset,
-                                                  summary_writer=train_writer, epoch=epoch)
-        if val_auc < latest_peak_auc + MIN_DELTA_AUC:
-            if WAIT_EPOCHS == waited_epochs:
-                if rank == 0:
-                    print("Stopped early at epoch {0} with saved peak auc {1:10.8}".format(epoch + 1, latest_peak_auc))
-                break
-            waited_epochs += 1
-        else:
-            latest_peak_auc = val_auc
-            if rank == 0:
-                print(f"New peak auc reached: {val_auc:10.8}")
-                checkpoint.save(args.save_model_path, engine.g, engine.params_numpy(),
-                                {"epoch": epoch, "val_auc": float(val_auc), "tile_table": engine.tile_table(),
-                                 **run_meta}, **bn_state(), **ema_state())
-            saved = True
-            waited_epochs = 0
+    def line(self) -> str:
+        return ("Learning rate: {0:.6g}, median gradient norm: {1:.6g}, clipped steps: {2}, skipped steps: {3}"
+                .format(self.step_lr, self.median(), self.clipped, self.skipped))
 
-    # train.py:272-300: restore the best weights, sweep the training set,
-    # write specificity/sensitivity per threshold.
-    if dist:
-        dist.barrier()
-    if saved:
-        flat, _ = checkpoint.load(args.save_model_path, engine.g)
-        engine.load_params(flat)
-        if args.bn_moving is not None:      # the statistics saved with those weights
-            stats = checkpoint.load_bn_moving(args.save_model_path, engine.g)
-            if stats is not None:
-                engine.load_bn_moving(stats, checkpoint.read_meta(args.save_model_path)["bn_moving"]["updates"])
-        if args.weight_ema is not None:     # and the average saved with them
-            ema = checkpoint.load_ema(args.save_model_path, engine.g)
-            if ema is not None:
-                engine.load_ema(ema[0], ema[1]["updates"])
-    sess.reset("tp", "fp", "fn", "tn")
+    def summary(self) -> dict:
+        return {"grad_norm": self.median(), "learning_rate": self.step_lr}
+
+
+def _look(engine, tally, run_ahead, device_opt, xent=None):
+    """What the host learns when it looks at the device: the updates since its last look go to the
+    tally, the newest batch's loss comes back.  Running ahead, both are in the step log (one
+    synchronise for every batch since the last read); else they are the batch just run's own --
+    `xent`, and engine.opt_step() (16 bytes, after a synchronise) when the batch closed an update."""
     if run_ahead:
-        sess.metrics_reset()
-    it = iter(train_dataset)
+        recs = engine.step_log_read()
+        for rec in (recs[(recs["flags"] & 1) != 0] if device_opt else ()):
+            tally.note(float(rec["grad_norm"]), int(rec["flags"]) >> 1 & 1)
+        return float(recs["loss"][-1]) if len(recs) else None
+    if device_opt and engine.accum_pending() == 0:
+        norm, _, skip, _ = engine.opt_step()
+        tally.note(norm, skip)
+    return xent
+
+
+def train_epoch(sess, engine, dataset, args, epoch, sched, aug, tally, rank, out=sys.stdout, limit=None):
+    """The batches of one epoch.  Every --status_every-th batch the host looks (_look) and rank 0
+    prints the status line; with N = 1 that is every batch, whose Brier sums are then added on the host.
+    sched: the Schedule of the device optimizer path, else None; limit: plan_epoch's."""
+    run_ahead, device_opt = args.status_every > 1, sched is not None
+    sess.begin_pass("brier")
+    batch_num = 0
+    it = iter(dataset)
+    try:
+        for images, labels in it:
+            if limit is not None and batch_num >= limit:
+                break
+            if args.max_steps_per_epoch is not None and batch_num >= args.max_steps_per_epoch:
+                break
+            if device_opt:
+                tally.step_lr = sched.rate(sess.global_step)
+                engine.set_lr(tally.step_lr)
+            i_global, xent, probs = sess.train_batch(images, labels, *aug.draw(len(images)))
+            if batch_num % args.status_every == args.status_every - 1:
+                xent = _look(engine, tally, run_ahead, device_opt, xent)
+                if rank == 0:
+                    print(status_line(epoch, args.num_epochs, batch_num, xent, i_global), end="\r", file=out)
+            if not run_ahead:       # (running ahead, train_batch left them on the device)
+                sess.update(labels, probs, "brier")
+            batch_num += 1
+    finally:
+        lib.dataset.close_iterator(it)
+    # --accum_steps: a partial group is closed here, so validation, early stopping, checkpoints
+    # and the replica check never see an open one (every rank ran the same number of batches)
+    if sess.accum_flush() or run_ahead:
+        _look(engine, tally, run_ahead, device_opt)
+    sess.end_pass("brier")
+
+
+def check_replicas(engine, args, epoch, r):
+    """Data parallel: every rank applies the same update to the same
+    reduced gradient, so the replicas must stay bitwise identical; compare
+    a digest of every rank's parameters once per epoch (and dump them for
+    --replica_dump_dir); with --weight_ema the digest covers the average too."""
+    if not r.dist and not args.replica_dump_dir:
+        return
+    flat = engine.params_numpy()
+    if args.replica_dump_dir:
+        os.makedirs(args.replica_dump_dir, exist_ok=True)
+        np.save(os.path.join(args.replica_dump_dir, f"params_e{epoch}_r{r.rank}.npy"), flat)
+    if r.dist:
+        import hashlib
+        digest = hashlib.sha256(flat.tobytes())
+        if args.weight_ema is not None:
+            digest.update(engine.ema_numpy().tobytes())
+        got = [None] * r.world
+        r.dist.all_gather_object(got, digest.hexdigest())
+        if len(set(got)) != 1:
+            raise RuntimeError(f"data-parallel replicas diverged after epoch {epoch}: {got}")
+
+
+def report_epoch(sess, tally, epoch, writer, out=sys.stdout):
+    """Rank 0's lines at the end of an epoch's batches, and the summary of its updates."""
+    print("\nEnd of epoch {0}! (Brier: {1:8.6})".format(epoch, sess.value("brier")), file=out)
+    if tally.norms:
+        print(tally.line(), file=out)
+        writer.add_summary(tally.summary(), epoch)
+
+
+class EarlyStop:
+    """train.py:246-270: an epoch whose validation AUC does not beat the peak by MIN_DELTA_AUC
+    waits; the run stops at such an epoch once WAIT_EPOCHS of them were waited (the test comes
+    before the increment, as in the reference: WAIT_EPOCHS + 1 epochs without a new peak)."""
+    min_delta, wait = MIN_DELTA_AUC, WAIT_EPOCHS
+
+    def __init__(self):
+        self.peak, self.waited = 0.0, 0
+
+    def step(self, auc) -> str:
+        """"peak" (a new one: save), "wait" or "stop"."""
+        if auc < self.peak + self.min_delta:
+            if self.wait == self.waited:
+                return "stop"
+            self.waited += 1
+            return "wait"
+        self.peak, self.waited = auc, 0
+        return "peak"
+
+
+def save_best(args, engine, epoch, val_auc, meta):
+    """The checkpoint of a new peak: the weights, the run's .meta, and beside them the moving BN
+    statistics (--bn_moving) and the weight average (--weight_ema)."""
+    from jr import checkpoint
+    extra = {}
+    if args.bn_moving is not None:
+        extra["bn_moving"] = {"stats": engine.bn_moving_numpy(), "momentum": args.bn_moving,
+                              "updates": engine.updates}
+    if args.weight_ema is not None:
+        extra["weight_ema"] = {"flat": engine.ema_numpy(), "decay": args.weight_ema,
+                               "warm": not args.weight_ema_no_warm, "updates": engine.ema_updates()}
+    checkpoint.save(args.save_model_path, engine.g, engine.params_numpy(),
+                    {"epoch": epoch, "val_auc": float(val_auc), "tile_table": engine.tile_table(), **meta}, **extra)
+
+
+def restore_best(args, engine):
+    """train.py:272-275: the best weights back into the engine, with the BN
+    statistics and the average saved with them."""
+    from jr import checkpoint
+    flat, _ = checkpoint.load(args.save_model_path, engine.g)
+    engine.load_params(flat)
+    if args.bn_moving is not None:
+        stats = checkpoint.load_bn_moving(args.save_model_path, engine.g)
+        if stats is not None:
+            engine.load_bn_moving(stats, checkpoint.read_meta(args.save_model_path)["bn_moving"]["updates"])
+    if args.weight_ema is not None:
+        ema = checkpoint.load_ema(args.save_model_path, engine.g)
+        if ema is not None:
+            engine.load_ema(ema[0], ema[1]["updates"])
+
+
+def final_sweep(sess, dataset, averaged):
+    """train.py:276-290: the threshold counts of the training set under the restored weights."""
+    counts = ("tp", "fp", "fn", "tn")
+    sess.begin_pass(*counts)
+    it = iter(dataset)
     try:
         with averaged():
             for images, labels in it:
-                if run_ahead:
-                    sess.predict_enqueue(images, labels)
-                    continue
-                probs = sess.predict(images, labels)
-                sess.update(labels, probs, "tp", "fp", "fn", "tn")
-            if run_ahead:
-                sess.pull_metrics("tp", "fp", "fn", "tn")
+                sess.score_batch(images, labels, *counts)
     finally:
         lib.dataset.close_iterator(it)
-    sess.sync_metrics("tp", "fp", "fn", "tn")
+    sess.end_pass(*counts)
+
+
+BANNER = """
+Training images folder: {0.train_dir},
+Validation images folder: {0.val_dir},
+Saving model and graph checkpoints at: {0.save_model_path},
+Saving summaries at: {0.save_summaries_dir},
+Saving operating points at: {0.save_operating_thresholds_path},
+Use SGD: {1}
+"""
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    import contextlib
+    from jr import cli
+    from jr.summary import FileWriter
+
+    random.seed(432)                       # train.py:17
+    r = cli.ranks(versions_first=True)     # (rank 0: one copy of the reference's header lines)
+    rank = r.rank
     if rank == 0:
-        os.makedirs(os.path.dirname(os.path.abspath(args.save_operating_thresholds_path)), exist_ok=True)
-        spec, sens = sess.specificities(), sess.sensitivities()
-        with open(args.save_operating_thresholds_path, "w") as f:
-            w = csv.writer(f, delimiter=" ")
-            w.writerow(["threshold", "specificity", "sensitivity"])
-            for idx in range(NUM_THRESHOLDS):
-                w.writerow(["{:0.4f}".format(v) for v in (thresholds[idx], spec[idx], sens[idx])])
-    if train_writer:
-        train_writer.close()
-    if dist:
-        dist.destroy_process_group()
+        print(BANNER.format(args, bool(args.vanilla_sgd)))
+    thresholds = lib.metrics.generate_thresholds(NUM_THRESHOLDS, KEPSILON) + [0.5]
+    train_dataset, val_dataset = open_datasets(args, r)
+    engine = build_engine(args, r)
+    sess = build_session(args, engine, thresholds, r)
+    aug = Augmenter(args, rank)
+    meta = run_meta(args, aug.spec, aug.geo)
+    if rank == 0 and loss_meta(args):
+        print(objective_line(args))
+    # --weight_ema: validation, early stopping and the final sweep read the averaged weights
+    averaged = engine.averaged_weights if args.weight_ema is not None else contextlib.nullcontext
+    writer = FileWriter(os.path.join(args.save_summaries_dir, "train")) if rank == 0 else None
+    limit, sched = plan_epoch(args, r, train_dataset)
+
+    stop, saved = EarlyStop(), False
+    for epoch in range(args.num_epochs):
+        tally = UpdateTally(args.clip_norm)
+        train_epoch(sess, engine, train_dataset, args, epoch, sched, aug, tally, rank, limit=limit)
+        check_replicas(engine, args, epoch, r)
+        if rank == 0:
+            report_epoch(sess, tally, epoch, writer)
+        # every rank gets the same val_auc (summed counts), so the early-stop
+        # decisions below agree and the collectives stay matched
+        with averaged():
+            val_auc = lib.evaluation.perform_test(sess=sess, init_op=val_dataset, summary_writer=writer, epoch=epoch)
+        verdict = stop.step(val_auc)
+        if verdict == "stop":
+            if rank == 0:
+                print("Stopped early at epoch {0} with saved peak auc {1:10.8}".format(epoch + 1, stop.peak))
+            break
+        if verdict == "peak":
+            if rank == 0:
+                print(f"New peak auc reached: {val_auc:10.8}")
+                save_best(args, engine, epoch, val_auc, meta)
+            saved = True
+
+    # train.py:272-300: restore the best weights, sweep the training set,
+    # write specificity/sensitivity per threshold.
+    if r.dist:
+        r.dist.barrier()
+    if saved:
+        restore_best(args, engine)
+    final_sweep(sess, train_dataset, averaged)
+    if rank == 0:
+        cli.write_operating_points(args.save_operating_thresholds_path, thresholds,
+                                   sess.specificities(), sess.sensitivities(), NUM_THRESHOLDS)
+    if writer:
+        writer.close()
+    if r.dist:
+        r.dist.destroy_process_group()
     return 0
 
 
