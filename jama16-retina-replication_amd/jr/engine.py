@@ -76,7 +76,7 @@ import torch
 from . import _ffi
 from . import augment as _augment
 from .inception import BN_EPS, Graph, PoolNode, build_inception_v3
-from .init import init_params
+from .init import ALIGN, init_params
 from .lanes import Build, Call, Lanes, node_lanes, schedule
 from .plan import ConvUnit, bn_batch_groups, bn_moving_segments, build_plan, decay_ranges
 from .runahead import STEP_REC, Feed, Metrics, StepLog
@@ -121,6 +121,60 @@ def pinned_tile_table(conv_math: str, batch: int, height: int, width: int, train
                                                                               train):
             return t
     return None
+
+
+class MagRows:
+    """The layout of the JR_F32_X6H magnitude words, rows of ROW floats in one
+    tensor (Replica.absmax) -- the one place that knows it.  One row per (conv
+    launch, member) for its filter block, the members of a launch contiguous
+    (the grouped conv's convention); then, with dgrad, one row per launch for
+    its raw-output gradient.  The betas' maxima land in the LAST row: a row of
+    their own where there are no gradient rows (jr.EnsembleEngine); else
+    (jr.Engine) the last gradient row, zeroed again by the same prep and raised
+    by the first BN backward only after it: harmless, a larger bound; conv2d_1's
+    data gradient is never used (a row of their own there
+    too is `self.rows = ... + 1` below)."""
+    ROW = 64
+
+    def __init__(self, order: Dict[int, int], members: int, dgrad: bool):
+        launches = self._k = order          # launch -> its place in plan order
+        self.members, self.filt_rows = members, len(launches) * members
+        self.dgrad_rows = len(launches) if dgrad else 0
+        self.rows = self.filt_rows + (self.dgrad_rows or 1)
+        self.beta = self.rows - 1
+        self.size = self.ROW * self.rows
+
+    def filt(self, uid: int, m: int = 0) -> int:
+        """Row of member m's filter block of launch uid."""
+        return self._k[uid] * self.members + m
+
+    def dgrad(self, uid: int) -> int:
+        """Row of launch uid's raw-output gradient."""
+        if not self.dgrad_rows:
+            raise KeyError("no data-gradient magnitude rows")
+        return self.filt_rows + self._k[uid]
+
+    def span(self, row: int, rows: int = 1) -> Tuple[int, int]:
+        """(first float, float count) of `rows` rows from `row` on."""
+        return self.ROW * row, self.ROW * rows
+
+
+@dataclasses.dataclass(frozen=True)
+class Region:
+    """Elements start + r * stride + j (r < rows, j < width) of the flat tensor `name` (Replica.regions)."""
+    name: str
+    start: int
+    width: int
+    rows: int = 1
+    stride: int = 0
+
+    def contains(self, elem: int) -> bool:
+        e = elem - self.start
+        if e < 0:
+            return False
+        if self.rows == 1:
+            return e < self.width
+        return e // self.stride < self.rows and e % self.stride < self.width
 
 
 class Replica:
@@ -237,6 +291,37 @@ class Replica:
         """The conv2d_bn layer whose BN + ReLU a fused max-pool applies."""
         return next(m for m in self.g.nodes if m.y.buf == n.x)
 
+    def _alloc_forward(self, dgrad_rows: bool) -> None:
+        """What a forward of self.members members reads and writes, member-major
+        with member strides (act_ms, raw_ms, stats_ms; batch, units, nparam for
+        the head's and the parameters)."""
+        g, B, M, at = self.g, self.batch, self.members, self.act_dtype
+        if self.x6h:
+            # (first: every conv descriptor points into it; the ensemble's filters
+            # never change in inference: measured at load_params)
+            self._alloc_absmax(B, dgrad_rows)
+        self.act_ms = [B * b.h * b.w * (self.in_stride if b.id == g.input_buf else b.c) for b in g.bufs]
+        self.acts = [self._t(M * n, at) for n in self.act_ms]
+        # raw (pre-BN) output and BN statistics per conv launch; a fused
+        # group's members see channel slices of them
+        self.raw_ms = {u.first.idx: B * u.ho * u.wo * u.cout for u in self.cunits}
+        self.raw_unit = {k: self._t(M * n, at) for k, n in self.raw_ms.items()}
+        self.stats_ms = self.plan.stats_size
+        self.stats = self._t(M * self.stats_ms)
+        self._alloc_bn_moving()
+        self.feat = self._t(M * B * g.bufs[g.output_buf].c)
+        self.logits = self._t(M * B * self.units)
+        self.probs = self._t(M * B * self.units)
+        self.labels = self._t(B * self.units)
+        self.loss = self._t(4 * M)
+        self.params = self._t(M * self.nparam)
+
+    def _alloc_ws(self, nbytes: int) -> None:
+        """Every lane's own conv workspace of nbytes."""
+        self.ws_bytes = int(nbytes)
+        self.ws_lane = [self._t((self.ws_bytes + 15) // 4 + 4) for _ in range(self.nlanes)]
+        self.ws = self.ws_lane[0]
+
     def _alloc_bf16_filters(self, planes: int = 1, hwio: bool = True) -> None:
         """bf16 operand copies of every conv launch's kernel (block) of every
         member, written from the fp32 master parameters by ONE
@@ -264,25 +349,24 @@ class Replica:
         self.w_hwio = self._t(ho, torch.bfloat16) if hwio else None
         self.w_t = self._t(M * self.wt_ms, torch.bfloat16)
 
-    def _alloc_absmax(self, B: int, rows: int, beta_row: int) -> None:
-        """JR_F32_X6H magnitude words, 64 floats per row: one row per (conv
-        launch, member) for its filter block, the members of a launch
-        contiguous (the grouped conv's convention), then whatever rows the
-        caller keeps; and the jr_absmax_prep table (filters, then every BN
-        beta with the activation guard, their maxima landing in beta_row)."""
+    def _alloc_absmax(self, B: int, dgrad_rows: bool) -> None:
+        """The JR_F32_X6H magnitude words (MagRows) and the jr_absmax_prep
+        table: the filters, then every BN beta with the activation guard."""
         M = self.members
-        self.absmax = self._t(64 * rows)
-        self._arow = {u.first.idx: k for k, u in enumerate(self.cunits)}
+        self._arow = {u.first.idx: k for k, u in enumerate(self.cunits)}    # launch -> its place in plan order
+        self.mag = MagRows(self._arow, M, dgrad_rows)
+        self.absmax = self._t(self.mag.size)
         nmax = max(B * u.ho * u.wo for u in self.cunits)
         # activations are BN + ReLU outputs (or pools of them): |y| <= sqrt(N-1)
         # + max |beta|; bound = a power of two >= sqrt(N_max) + 1024, beta
         # guarded at that bound, so |y| <= 2 bound < the 4 bound the scale
         # keeps representable
         self.act_bound = float(2 ** int(np.ceil(np.log2(np.sqrt(nmax) + 1024))))
-        segs = [_ffi.AbsmaxSeg(m * self.nparam + u.koff, u.kh * u.kw * u.cin * u.cout, k * M + m, 0.0)
-                for k, u in enumerate(self.cunits) for m in range(M)]
+        segs = [_ffi.AbsmaxSeg(m * self.nparam + u.koff, u.kh * u.kw * u.cin * u.cout, self.mag.filt(u.first.idx, m),
+                               0.0) for u in self.cunits for m in range(M)]
         segs += [_ffi.AbsmaxSeg(m * self.nparam + self.plan.poff[f"batch_normalization_{n.idx + 1}/beta"], n.cout,
-                                beta_row, self.act_bound) for m in range(M) for u in self.cunits for n in u.members]
+                                self.mag.beta, self.act_bound)
+                 for m in range(M) for u in self.cunits for n in u.members]
         self.absmax_table = self._table(_ffi.AbsmaxSeg, segs)
         self.absmax_nseg = len(segs)
 
@@ -308,7 +392,23 @@ class Replica:
         return [("frozen",)] if b.stats_shift else []
 
     def _wmax(self, u: ConvUnit) -> int:
-        return self.absmax.data_ptr() + 4 * 64 * self._arow[u.first.idx] * self.members
+        """The magnitude rows of a launch's filters, member 0's first (w_absmax)."""
+        return self.absmax.data_ptr() + 4 * self.mag.span(self.mag.filt(u.first.idx))[0]
+
+    def _dmax(self, u: ConvUnit) -> int:
+        """The magnitude row of a launch's raw-output gradient (dy_absmax)."""
+        return self.absmax.data_ptr() + 4 * self.mag.span(self.mag.dgrad(u.first.idx))[0]
+
+    # ---- the statistics: addresses in the plan's layout (Plan.stats_size, ConvUnit.soff)
+    def _mean(self, u: ConvUnit, co: int = 0, m: int = 0) -> int:
+        """Member m's batch mean of a launch's channels from column co on (frozen: the caller adds stats_shift)."""
+        return self.stats.data_ptr() + 4 * (m * self.stats_ms + u.soff + co)
+
+    def _invstd(self, u: ConvUnit, co: int = 0, m: int = 0) -> int:
+        return self._mean(u, u.cout + co, m)
+
+    def _A(self, bid: int, m: int = 0) -> int:
+        return self.acts[bid].data_ptr() + self.esz * m * self.act_ms[bid]
 
     def _conv_desc(self, u: ConvUnit, B: int) -> _ffi.ConvDesc:
         if self.x8p:          # x describes the operand planes: channel radix padded to 8
@@ -391,10 +491,9 @@ class Replica:
 
     # ------------------------------------------- moving BN statistics, frozen BN
     def _alloc_bn_moving(self) -> None:
-        """Beside self.stats ([mean(c) | invstd(c)] per conv launch, member
-        stride self.stats_ms): `moving` ([moving_mean(c) | moving_var(c)] at the
-        same offsets, mean 0 and variance 1 as Keras initialises them) and
-        `frozen` (the statistics layout a frozen forward reads)."""
+        """Beside self.stats (the plan's statistics layout, member stride
+        self.stats_ms): `moving` (mean 0 and variance 1 as Keras initialises
+        them) and `frozen` (what a frozen forward reads)."""
         self.moving = self._t(self.members * self.stats_ms)
         self.frozen = self._t(self.members * self.stats_ms)
         self._bn_tables: Dict[int, tuple] = {}
@@ -405,10 +504,8 @@ class Replica:
     def _reset_bn_moving(self, var: float = 1.0) -> None:
         """moving_mean = 0, moving_var = var, on self.stream (in order with the launches that update them)."""
         host = np.zeros((self.members, self.stats_ms), np.float32)
-        off = 0
-        for u in self.cunits:
-            host[:, off + u.cout:off + 2 * u.cout] = var
-            off += 2 * u.cout
+        for n, _, ov in self.plan.bn_layers():
+            host[:, ov:ov + n.cout] = var
         with torch.cuda.stream(self.stream):
             self.moving.copy_(torch.from_numpy(host.reshape(-1)).to(self.device))
 
@@ -424,21 +521,13 @@ class Replica:
         return (table.data_ptr(), nseg, max_c, self.members, self.stats.data_ptr(), self.stats_ms,
                 self.moving.data_ptr(), self.stats_ms, float(momentum), BN_EPS, s)
 
-    def _bn_layers(self):
-        """(conv2d_bn layer, offset of its mean / moving_mean, offset of its invstd / moving_var)."""
-        off = 0
-        for u in self.cunits:
-            for n, co in zip(u.members, u.col_off):
-                yield n, off + co, off + u.cout + co
-            off += 2 * u.cout
-
     def _bn_moving_get(self) -> List[dict]:
         self.synchronize()
         host = self.moving.cpu().numpy().reshape(self.members, self.stats_ms)
         out = []
         for m in range(self.members):
             d = {}
-            for n, om, ov in sorted(self._bn_layers(), key=lambda t: t[0].idx):
+            for n, om, ov in sorted(self.plan.bn_layers(), key=lambda t: t[0].idx):
                 d[f"batch_normalization_{n.idx + 1}/moving_mean"] = host[m, om:om + n.cout].copy()
                 d[f"batch_normalization_{n.idx + 1}/moving_variance"] = host[m, ov:ov + n.cout].copy()
             out.append(d)
@@ -449,7 +538,7 @@ class Replica:
             raise ValueError(f"expected {self.members} members' BN statistics, got {len(dicts)}")
         host = np.zeros((self.members, self.stats_ms), np.float32)
         for m, d in enumerate(dicts):
-            for n, om, ov in self._bn_layers():
+            for n, om, ov in self.plan.bn_layers():
                 for key, o, kind in ((f"batch_normalization_{n.idx + 1}/moving_mean", om, "mean"),
                                      (f"batch_normalization_{n.idx + 1}/moving_variance", ov, "var")):
                     if key not in d:
@@ -521,6 +610,116 @@ class Replica:
         if self.frozen_source is None:
             raise ValueError("bn='frozen' before freeze_bn()")
         return True
+
+    # ----- the resource map: what memory the keys of the call lists name
+    # keys that name whole tensors (those the engine has), and tensors of a list or dict by index
+    _WHOLE = {"p": ("params",), "acc": ("accum", "adam_v"), "w16": ("w_hwio", "w_t"), "feat": ("feat",),
+              "head": ("logits", "probs", "loss"), "lab": ("labels",), "dfeat": ("dfeat",), "draw2": ("draw_stem2",),
+              "wss": ("ws_stem",), "gnorm": ("opt_partials", "opt_step_dev", "opt_hyper"), "bn_moving": ("moving",),
+              "frozen": ("frozen",), "target": ("ig_target",), "dinput": ("dinput",), "gacc": ("gacc",),
+              "ema": ("ema", "ema_state"), "drop": ("drop_state",), "feat_drop": ("feat_drop",)}
+    _INDEXED = {"draw": "draw_lane", "drawp": "drawp_lane", "ws": "ws_lane", "ap": "aplanes", "am": "argmax"}
+
+    @staticmethod
+    def _keep_of(lists) -> list:
+        """The kept objects of a _build_calls tuple (jr.Engine's five, jr.EnsembleEngine's two)."""
+        return lists[3] if len(lists) > 2 else lists[1]
+
+    @classmethod
+    def _slab_arena(cls, lists) -> Optional[torch.Tensor]:
+        """The deferred filter-gradient arena of one call-list build."""
+        return next((t for t in cls._keep_of(lists) if isinstance(t, torch.Tensor) and t.dtype == torch.float32), None)
+
+    def _slice_regions(self, name: str, t: torch.Tensor, buf: int, c_off: int, C: int) -> List[Region]:
+        """A channel slice (up to the next slice of self.slices) of every member's part of buffer t, C channels wide."""
+        offs = self.slices[buf]
+        k = offs.index(c_off)
+        width = (offs[k + 1] if k + 1 < len(offs) else C) - c_off
+        ms = t.numel() // self.members
+        return [Region(name, m * ms + c_off, width, ms // C, C) for m in range(self.members)]
+
+    def regions(self, key, lists=None) -> List[Region]:
+        """The memory a resource key of the call lists names (member-major
+        tensors: every member's part).  `lists`: the _build_calls tuple the key
+        comes from (needed for ("slab", uid): the arena belongs to one build).
+        Total over what the builders emit; an unknown key raises KeyError."""
+        kind, g = key[0], self.g
+        if kind == "a":
+            C = self.in_stride if key[1] == g.input_buf else g.bufs[key[1]].c
+            return self._slice_regions(f"acts[{key[1]}]", self.acts[key[1]], key[1], key[2], C)
+        if kind == "d":
+            return self._slice_regions(f"dacts[{key[1]}]", self.dacts[key[1]], key[1], key[2], g.bufs[key[1]].c)
+        if kind == "r":
+            u = self.plan.unit_of[key[1]]
+            return [Region(f"raw[{key[1]}]", 0, self.raw_unit[key[1]].numel()),
+                    Region("stats", u.soff, 2 * u.cout, self.members, self.stats_ms)]
+        if kind == "g":
+            # a tensor's resource includes the alignment padding behind it (jr.init.ALIGN):
+            # the optimizer walks the whole flat buffer, so the ("g", ...) keys together
+            # are all of `grads`
+            pad = lambda n: (n + ALIGN - 1) // ALIGN * ALIGN     # noqa: E731
+            if key[1] == "dense":
+                sizes = {name: (off, pad(size)) for name, _, off, size in self.plan.layout}
+                return [Region("grads", *sizes["dense/kernel"]), Region("grads", *sizes["dense/bias"])]
+            u = self.plan.unit_of[key[1]]
+            betas = [self.plan.poff[f"batch_normalization_{m.idx + 1}/beta"] for m in u.members]
+            return [Region("grads", u.koff, pad(u.kh * u.kw * u.cin * u.cout))] + [
+                Region("grads", o, pad(m.cout)) for o, m in zip(betas, u.members)]
+        if kind == "wmax":
+            return [Region("absmax", *self.mag.span(0, self.mag.filt_rows))]
+        if kind == "dmax":
+            return [Region("absmax", *self.mag.span(self.mag.dgrad(key[1])))]
+        if kind == "drawb":
+            return [Region(f"drawb[{key[1]}][{key[2]}]", 0, self.drawb[key[1]][key[2]].numel())]
+        if kind == "slab":
+            # read from the bound jr_conv2d_bwd_filter_slabs call (arena pointer and byte count)
+            c = next(c for c in lists[1] if key in c.writes and c.fn.__name__ == "jr_conv2d_bwd_filter_slabs")
+            off = int(c.args[4]) - self._slab_arena(lists).data_ptr()
+            return [Region("slab_arena", off // 4, int(c.args[5]) // 4)]
+        if kind in self._INDEXED:
+            name = self._INDEXED[kind]
+            return [Region(f"{name}[{key[1]}]", 0, getattr(self, name)[key[1]].numel())]
+        out = [Region(n, 0, getattr(self, n).numel()) for n in self._WHOLE.get(kind, ())
+               if getattr(self, n, None) is not None]
+        if not out:
+            raise KeyError(f"regions: unknown resource key {key!r}")
+        return out
+
+    def universe(self, lists=None) -> Dict[str, torch.Tensor]:
+        """Every device tensor the engine owns, by the names regions() uses; with
+        `lists` (a _build_calls tuple) also that build's slab arena and device tables."""
+        out = {}
+
+        def put(name, t):
+            if isinstance(t, torch.Tensor):
+                out[name] = t
+
+        for name in ("stats", "moving", "frozen", "feat", "logits", "probs", "labels", "loss", "params", "grads",
+                     "accum", "adam_v", "dfeat", "draw_stem2", "w_hwio", "w_t", "wprep_table", "absmax", "absmax_table",
+                     "ws_stem", "dinput", "x0", "attr_acc", "ig_target", "opt_partials", "opt_hyper", "opt_step_dev",
+                     "_opt_ranges_dev", "_aug_ws", "_aug_tab", "_warp_tab", "gacc", "ema", "ema_state", "drop_state",
+                     "feat_drop"):
+            put(name, getattr(self, name, None))
+        for name in ("acts", "dacts", "draw_lane", "drawp_lane", "ws_lane"):
+            for k, t in enumerate(getattr(self, name, None) or ()):
+                put(f"{name}[{k}]", t)
+        for name, short in (("raw_unit", "raw"), ("argmax", "argmax"), ("aplanes", "aplanes")):
+            for k, t in (getattr(self, name, None) or {}).items():
+                put(f"{short}[{k}]", t)
+        for s, row in enumerate(getattr(self, "drawb", None) or ()):
+            for k, t in enumerate(row):
+                put(f"drawb[{s}][{k}]", t)
+        for B, tab in (getattr(self, "_bn_tables", None) or {}).items():
+            put(f"bn_table[{B}]", tab[0])
+        if lists is not None:
+            arena = self._slab_arena(lists)
+            put("slab_arena", arena)
+            k = 0
+            for t in self._keep_of(lists):
+                if isinstance(t, torch.Tensor) and t is not arena:
+                    put(f"keep_table[{k}]", t)
+                    k += 1
+        return out
 
 
 class Engine(Replica):
@@ -734,45 +933,20 @@ class Engine(Replica):
     # ------------------------------------------------------------------ memory
     def _alloc(self) -> None:
         g, B, at = self.g, self.batch, self.act_dtype
-        if self.x6h:
-            # (first: every conv descriptor points into it) filter rows 0..U-1,
-            # raw-output gradient rows U..2U-1.  The betas' maxima land in the
-            # last gradient row, zeroed again by the same prep and raised by the
-            # first BN backward only after it: harmless, a larger bound; conv2d_1's
-            # data gradient is never used (jr.EnsembleEngine: a row of their own)
-            U = len(self.cunits)
-            self._alloc_absmax(B, 2 * U, 2 * U - 1)
-        self.acts = [self._t(B * b.h * b.w * (self.in_stride if b.id == g.input_buf else b.c), at)
-                     for b in g.bufs]
-        # raw (pre-BN) output and BN statistics per conv launch; a fused
-        # group's members see channel slices of them
-        self.raw_unit = {u.first.idx: self._t(B * u.ho * u.wo * u.cout, at) for u in self.cunits}
-        self.stats_ms = 2 * sum(u.cout for u in self.cunits)
-        self.stats = self._t(self.stats_ms)
-        self._alloc_bn_moving()
+        self._alloc_forward(dgrad_rows=True)
+        # per-layer views of a launch's raw output and statistics (tests/test_gpu_layerwise.py)
         self.raw, self.mean, self.invstd = {}, {}, {}
-        self.mean_unit, self.invstd_unit = {}, {}
-        off = 0
         for u in self.cunits:
             r = self.raw_unit[u.first.idx].view(B * u.ho * u.wo, u.cout)
-            self.mean_unit[u.first.idx] = self.stats[off:off + u.cout]
-            self.invstd_unit[u.first.idx] = self.stats[off + u.cout:off + 2 * u.cout]
             for n, co in zip(u.members, u.col_off):
                 self.raw[n.idx] = r[:, co:co + n.cout]
-                self.mean[n.idx] = self.stats[off + co:off + co + n.cout]
-                self.invstd[n.idx] = self.stats[off + u.cout + co:off + u.cout + co + n.cout]
-            off += 2 * u.cout
+        for n, om, oi in self.plan.bn_layers():
+            self.mean[n.idx], self.invstd[n.idx] = self.stats[om:om + n.cout], self.stats[oi:oi + n.cout]
         self.argmax = {}
         for i, n in enumerate(g.nodes):
             if n.kind == "maxpool":
                 self.argmax[i] = self._t(B * n.ho * n.wo * n.c, torch.uint8)
         feat_c = g.bufs[g.output_buf].c
-        self.feat = self._t(B * feat_c)
-        self.logits = self._t(B * self.units)
-        self.probs = self._t(B * self.units)
-        self.labels = self._t(B * self.units)
-        self.loss = self._t(4)
-        self.params = self._t(self.nparam)
         self.draw_stem2, self.bn_batch, self.drawb = None, [], []
         if self.train_mode:
             self.grads = self._t(self.nparam)
@@ -842,16 +1016,11 @@ class Engine(Replica):
                              for u in grp))
         for i in self.pool_fused:                      # the fused max-pool + BN backward's partials
             ws = max(ws, self.lib.jr_bn_relu_bwd_maxpool_workspace_size(ctypes.byref(self._pool_desc(g.nodes[i], B))))
-        self.ws_bytes = int(ws)
-        self.ws_lane = [self._t((self.ws_bytes + 15) // 4 + 4) for _ in range(self.nlanes)]
+        self._alloc_ws(ws)
         # the stem filter gradients' own workspace on lane 1
         self.ws_stem = self._t((self.ws_bytes + 15) // 4 + 4) if self.draw_stem2 is not None else None
-        self.ws = self.ws_lane[0]
         # launch -> its group of batched BN backwards
         self._in_batch = {u.first.idx: grp for grp in self.bn_batch for u in grp}
-
-    def _dmax(self, u: ConvUnit) -> int:
-        return self.absmax.data_ptr() + 4 * 64 * (len(self.cunits) + self._arow[u.first.idx])
 
     def _alloc_planes(self) -> None:
         """JR_F32_X8P operand planes (jr.h): the exact bf16 h/m/l split of
@@ -1227,9 +1396,6 @@ class Engine(Replica):
     # what a conv reads -- x8p: the split planes of its input buffer, written
     # once (by the lane of its first consumer) when the buffer is complete;
     # its filters (w16: their bf16 copies); x6h: their magnitude words too
-    def _A(self, bid: int) -> int:
-        return self.acts[bid].data_ptr()
-
     def _D(self, bid: int) -> int:
         return self.dacts[bid].data_ptr()
 
@@ -1276,7 +1442,7 @@ class Engine(Replica):
         d = self._conv_desc(u, B)
         b.keep.append(d)
         M, uid = B * u.ho * u.wo, u.first.idx
-        raw, mean, invstd = (t[uid].data_ptr() for t in (self.raw_unit, self.mean_unit, self.invstd_unit))
+        raw, mean, invstd = self.raw_unit[uid].data_ptr(), self._mean(u), self._invstd(u)
         if self.x8p and u.x not in b.split_done:
             b.split_done.add(u.x)
             xb, cp = g.bufs[u.x], self.plane_c[u.x]
@@ -1303,7 +1469,7 @@ class Engine(Replica):
             for m, co in zip(u.members, u.col_off):
                 b.add(b.fwd, L.jr_bn_relu_apply_stats,
                       (dt, raw, co, u.cout, M, m.cout, part, lay.P, lay.R, u.cout, co, BN_EPS,
-                       self.mean[m.idx].data_ptr(), self.invstd[m.idx].data_ptr(), self._beta(m), self._A(m.y.buf),
+                       mean + 4 * co, invstd + 4 * co, self._beta(m), self._A(m.y.buf),
                        m.y.c_off, g.bufs[m.y.buf].c, s),
                       "bn_relu", ln, [("r", uid), ("ws", ln), ("p",)], [("a", m.y.buf, m.y.c_off), ("r", uid)],
                       nbytes=2 * M * m.cout * self.esz)
@@ -1330,8 +1496,8 @@ class Engine(Replica):
                 continue        # applied inside its max-pool
             fn, lim = (L.jr_bn_relu_apply, ()) if b.guard is None else (L.jr_bn_relu_apply_guard, (b.guard,))
             b.add(b.fwd, fn,
-                  (dt, raw, co, u.cout, M, m.cout, self.mean[m.idx].data_ptr() + b.stats_shift,
-                   self.invstd[m.idx].data_ptr() + b.stats_shift, self._beta(m), self._A(m.y.buf), m.y.c_off,
+                  (dt, raw, co, u.cout, M, m.cout, mean + 4 * co + b.stats_shift,
+                   invstd + 4 * co + b.stats_shift, self._beta(m), self._A(m.y.buf), m.y.c_off,
                    g.bufs[m.y.buf].c) + lim + (s,),
                   "bn_relu", ln, [("r", uid), ("p",)] + self._frozen_reads(b), [("a", m.y.buf, m.y.c_off)],
                   nbytes=2 * M * m.cout * self.esz)
@@ -1344,12 +1510,13 @@ class Engine(Replica):
         if i in self.pool_fused:
             pn = self._pool_producer(n)
             d.x_c_off, d.x_c_stride = 0, pn.cout                       # its raw output
-            puid = self.plan.unit_of[pn.idx].first.idx
+            pu = self.plan.unit_of[pn.idx]          # (a launch of its own: fusable_pools)
+            puid = pu.first.idx
             fn, lim = ((L.jr_bn_relu_maxpool3x3s2_fwd, ()) if b.guard is None
                        else (L.jr_bn_relu_maxpool3x3s2_fwd_guard, (b.guard,)))
             b.add(b.fwd, fn,
-                  (ctypes.byref(d), dt, self.raw_unit[puid].data_ptr(), self.mean[pn.idx].data_ptr() + b.stats_shift,
-                   self.invstd[pn.idx].data_ptr() + b.stats_shift, self._beta(pn), self._A(n.y.buf),
+                  (ctypes.byref(d), dt, self.raw_unit[puid].data_ptr(), self._mean(pu) + b.stats_shift,
+                   self._invstd(pu) + b.stats_shift, self._beta(pn), self._A(n.y.buf),
                    self.argmax[i].data_ptr()) + lim + (s,),
                   "bn_relu_maxpool_fwd", ln, [("r", puid), ("p",)] + self._frozen_reads(b), out + [("am", i)],
                   nbytes=B * n.c * (n.h * n.w * self.esz + n.ho * n.wo * (self.esz + 1)))
@@ -1503,8 +1670,7 @@ class Engine(Replica):
             layers[k].x = self.raw_unit[vid].data_ptr()
             layers[k].x_c_off, layers[k].x_c_stride = 0, v.cout
             layers[k].m, layers[k].c = B * v.ho * v.wo, v.cout
-            layers[k].mean = self.mean_unit[vid].data_ptr()
-            layers[k].invstd = self.invstd_unit[vid].data_ptr()
+            layers[k].mean, layers[k].invstd = self._mean(v), self._invstd(v)
             layers[k].dx = ptr
             reads += [("d", m.y.buf, m.y.c_off) for m in v.members]
             writes += [("drawb", b.bset, k), ("g", vid)]
@@ -1519,8 +1685,8 @@ class Engine(Replica):
         pd = self._pool_desc(pn, b.B)
         b.keep.append(pd)
         args = (self.dt, ctypes.byref(pd), self.argmax[pool_i].data_ptr(), self._D(pn.y.buf), self._D(pn.x),
-                self.raw_unit[uid].data_ptr(), u.cout, self.mean_unit[uid].data_ptr(),
-                self.invstd_unit[uid].data_ptr(), self._beta(m0), draw, self._dbeta(m0), b.WS[ln], b.wsb)
+                self.raw_unit[uid].data_ptr(), u.cout, self._mean(u), self._invstd(u), self._beta(m0), draw,
+                self._dbeta(m0), b.WS[ln], b.wsb)
         fn = self.lib.jr_bn_relu_bwd_maxpool
         if self.x6h:    # also the raw-output gradient's magnitude (dy_absmax of its GEMMs)
             fn, args = self.lib.jr_bn_relu_bwd_maxpool_absmax, args + (self._dmax(u),)
@@ -1538,8 +1704,7 @@ class Engine(Replica):
             segs = (_ffi.BnSeg * len(grp))(*self._bn_segs(m for m, _ in grp))
             b.keep.append(segs)
             args = (self.dt, len(grp), ctypes.byref(segs), self.raw_unit[uid].data_ptr(), co0, u.cout, M, cg,
-                    self.mean_unit[uid].data_ptr() + 4 * co0, self.invstd_unit[uid].data_ptr() + 4 * co0,
-                    draw, b.WS[ln], b.wsb)
+                    self._mean(u, co0), self._invstd(u, co0), draw, b.WS[ln], b.wsb)
             fn = self.lib.jr_bn_relu_bwd_multi
             if self.x6h:
                 fn, args = self.lib.jr_bn_relu_bwd_multi_absmax, args + (self._dmax(u),)
@@ -1616,14 +1781,14 @@ class Engine(Replica):
         ob, s0 = g.bufs[g.output_buf], b.S[0]
         if self.x6h:
             # x6h (x6h_frozen): every frozen BN backward raises its launch's
-            # data-gradient row (the dy_absmax of its dgrad), so the rows [U, 2U)
+            # data-gradient row (the dy_absmax of its dgrad), so those rows
             # start from zero on EVERY run -- two input_gradient calls after one
-            # forward give the same bits as one.  (Row 2U - 1 also held the
+            # forward give the same bits as one.  (The last of them also held the
             # betas' maxima of the forward's jr_absmax_prep: their guard was
             # evaluated inside that launch, nothing reads them afterwards.)
-            U = len(self.cunits)
-            b.add(b.bwd, self.lib.jr_absmax_reset, (self.absmax.data_ptr() + 4 * 64 * U, 64 * U, s0),
-                  "absmax_reset", 0, [], [("dmax", u.first.idx) for u in self.cunits], nbytes=4 * 64 * U)
+            first, n = self.mag.span(self.mag.filt_rows, self.mag.dgrad_rows)
+            b.add(b.bwd, self.lib.jr_absmax_reset, (self.absmax.data_ptr() + 4 * first, n, s0),
+                  "absmax_reset", 0, [], [("dmax", u.first.idx) for u in self.cunits], nbytes=4 * n)
         b.add(b.bwd, self.lib.jr_head_logit_bwd,
               (self._p("dense/kernel"), self.ig_target.data_ptr(), B, ob.c, self.units, self.dfeat.data_ptr(), s0),
               "head_logit_bwd", 0, [("p",), ("target",)], [("dfeat",)])
@@ -1659,8 +1824,7 @@ class Engine(Replica):
                         else (self.lib.jr_bn_relu_bwd_frozen, ()))
             b.add(b.bwd, fn,
                   (self.dt, len(grp), ctypes.byref(segs), self.raw_unit[uid].data_ptr(), co0, u.cout, M, cg,
-                   self.mean_unit[uid].data_ptr() + 4 * co0 + b.stats_shift,
-                   self.invstd_unit[uid].data_ptr() + 4 * co0 + b.stats_shift, draw) + amax + (b.S[ln],),
+                   self._mean(u, co0) + b.stats_shift, self._invstd(u, co0) + b.stats_shift, draw) + amax + (b.S[ln],),
                   "bn_relu_bwd_frozen", ln, [("d", m.y.buf, m.y.c_off) for m, _ in grp] + [("r", uid), ("p",)],
                   [dkey] + ([("dmax", uid)] if self.x6h else []), nbytes=3 * M * cg * self.esz)
         if u.x != self.g.input_buf:

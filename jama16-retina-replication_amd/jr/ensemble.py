@@ -73,32 +73,8 @@ class EnsembleEngine(Replica):
 
     # ------------------------------------------------------------------ memory
     def _alloc(self) -> None:
-        g, B, M, at = self.g, self.batch, self.members, self.act_dtype
-        if self.x6h:
-            # (first: every conv descriptor points into it) a row per (launch,
-            # member) and one for the betas' maxima; the filters never change
-            # in inference: measured at load_params
-            U = len(self.cunits)
-            self._alloc_absmax(B, U * M + 1, U * M)
-        # member stride of every activation buffer: one member's B images
-        self.act_ms = [B * b.h * b.w * (self.in_stride if b.id == g.input_buf else b.c) for b in g.bufs]
-        self.acts = [self._t(M * n, at) for n in self.act_ms]
-        self.raw_ms = {u.first.idx: B * u.ho * u.wo * u.cout for u in self.cunits}
-        self.raw_unit = {k: self._t(M * n, at) for k, n in self.raw_ms.items()}
-        self.stats_ms = 2 * sum(u.cout for u in self.cunits)
-        self.stats = self._t(M * self.stats_ms)
-        self._alloc_bn_moving()
-        self.stat_off, off = {}, 0
-        for u in self.cunits:
-            self.stat_off[u.first.idx] = off
-            off += 2 * u.cout
-        feat_c = g.bufs[g.output_buf].c
-        self.feat = self._t(M * B * feat_c)
-        self.logits = self._t(M * B * self.units)
-        self.probs = self._t(M * B * self.units)
-        self.labels = self._t(B * self.units)
-        self.loss = self._t(4 * M)
-        self.params = self._t(M * self.nparam)
+        B, M = self.batch, self.members
+        self._alloc_forward(dgrad_rows=False)
         if self.dt == _ffi.JR_BF16:
             # the bf16 W^T operand copies of every member (weights never change
             # in inference: prepared once, at load_params)
@@ -107,9 +83,7 @@ class EnsembleEngine(Replica):
         for u in self.cunits:
             d = self._conv_desc(u, B)
             ws = max(ws, self.lib.jr_conv2d_workspace_size_grouped(ctypes.byref(d), self.cdt, M))
-        self.ws_bytes = int(ws)
-        self.ws_lane = [self._t((self.ws_bytes + 15) // 4 + 4) for _ in range(self.nlanes)]
-        self.ws = self.ws_lane[0]
+        self._alloc_ws(ws)
 
     def load_params(self, params: List[np.ndarray]) -> None:
         """Keras-layout flat parameters of every member (jr.checkpoint.load)."""
@@ -169,9 +143,6 @@ class EnsembleEngine(Replica):
         self._calls[key] = (b.fwd, b.keep)
         return self._calls[key]
 
-    def _A(self, bid: int, m: int = 0) -> int:
-        return self.acts[bid].data_ptr() + self.esz * m * self.act_ms[bid]
-
     def _fwd_conv(self, b: Build, ln: int, u) -> None:
         """One grouped conv + statistics launch, one grouped BN + ReLU per member layer."""
         L, g, M, B, s = self.lib, self.g, self.members, b.B, b.S[ln]
@@ -183,8 +154,7 @@ class EnsembleEngine(Replica):
         else:
             w, w_ms = self.params.data_ptr() + 4 * u.koff, self.nparam
         raw = self.raw_unit[uid].data_ptr()
-        mean = self.stats.data_ptr() + 4 * self.stat_off[uid]
-        inv = mean + 4 * u.cout
+        mean, inv = self._mean(u), self._invstd(u)
         b.add(b.fwd, L.jr_conv2d_fwd_bn_stats_grouped,
               (ctypes.byref(d), self.cdt, M, self._A(u.x), self.act_ms[u.x], w, w_ms, raw, self.raw_ms[uid], BN_EPS,
                mean, inv, self.stats_ms, b.WS[ln], b.wsb, s),
@@ -213,13 +183,14 @@ class EnsembleEngine(Replica):
             xi, yo, out = self._A(n.x, m), self._A(n.y.buf, m), [("a", n.y.buf, n.y.c_off)]
             if i in self.pool_fused:    # BN + ReLU of the producing layer on the fly
                 pn = self._pool_producer(n)
-                puid = self.plan.unit_of[pn.idx].first.idx
-                mean = self.stats.data_ptr() + 4 * (self.stat_off[puid] + m * self.stats_ms) + b.stats_shift
+                pu = self.plan.unit_of[pn.idx]
+                puid = pu.first.idx
+                mean, inv = self._mean(pu, 0, m) + b.stats_shift, self._invstd(pu, 0, m) + b.stats_shift
                 fn, lim = ((L.jr_bn_relu_maxpool3x3s2_fwd_grouped, ()) if b.guard is None
                            else (L.jr_bn_relu_maxpool3x3s2_fwd_grouped_guard, (b.guard,)))
                 b.add(b.fwd, fn,
                       (ctypes.byref(d), self.dt, B, self.raw_unit[puid].data_ptr() + self.esz * m * self.raw_ms[puid],
-                       mean, mean + 4 * pn.cout, self.stats_ms, self._beta(pn, m), self.nparam, yo, None) + lim + (s,),
+                       mean, inv, self.stats_ms, self._beta(pn, m), self.nparam, yo, None) + lim + (s,),
                       "bn_relu_maxpool_fwd", ln, [("r", puid)] + self._frozen_reads(b), out)
             elif n.kind == "maxpool":
                 b.add(b.fwd, L.jr_maxpool3x3s2_fwd, (ctypes.byref(d), self.dt, xi, yo, None, s), "maxpool_fwd", ln,

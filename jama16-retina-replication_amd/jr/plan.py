@@ -41,6 +41,7 @@ class ConvUnit:
     members: List[ConvNode]
     col_off: List[int]
     koff: int = 0                     # internal offset of the kernel block
+    soff: int = 0                     # offset of its [mean(c) | invstd(c)] block in the statistics layout
 
     @property
     def first(self) -> ConvNode:
@@ -78,6 +79,16 @@ class Plan:
     poff: Dict[str, int]                          # contiguous tensors: betas, dense, unfused kernels
     kview: Dict[str, Tuple[int, int, int, int, int]] = field(default_factory=dict)
     # conv kernel name -> (block offset, row stride, column offset, rows, cols)
+    # the statistics layout, per member: one block [mean(c) | invstd(c)] per conv launch at its
+    # ConvUnit.soff, launches in plan order.  The batch statistics, `frozen` (the same layout) and
+    # `moving` ([moving_mean(c) | moving_var(c)]) all use these offsets; build_plan is their one home
+    stats_size: int = 0
+
+    def bn_layers(self):
+        """(conv2d_bn layer, offset of its mean / moving_mean, offset of its invstd / moving_var)."""
+        for u in self.units:
+            for n, co in zip(u.members, u.col_off):
+                yield n, u.soff + co, u.soff + u.cout + co
 
     def to_internal(self, g: Graph, flat: np.ndarray) -> np.ndarray:
         keras, total = param_layout(g.params)
@@ -172,7 +183,11 @@ def build_plan(g: Graph, fuse_siblings: bool = True) -> Plan:
         poff[name] = o
         if n is not None and name.endswith("/kernel"):
             unit_of[n.idx].koff = o
-    return Plan(units, unit_of, layout, off, poff, kview)
+    soff = 0
+    for u in units:
+        u.soff = soff
+        soff += 2 * u.cout
+    return Plan(units, unit_of, layout, off, poff, kview, soff)
 
 
 def decay_ranges(plan: Plan) -> List[Tuple[int, int]]:
@@ -195,17 +210,16 @@ def decay_ranges(plan: Plan) -> List[Tuple[int, int]]:
 def bn_moving_segments(units: List[ConvUnit], batch: int) -> List[Tuple[int, int, int, int]]:
     """(stats offset, moving offset, rows, c) per conv launch: the segment
     table of jr_bn_moving_update / jr_bn_moving_freeze at this batch.  The
-    statistics layout [mean(c) | invstd(c)] and the moving layout
-    [moving_mean(c) | moving_var(c)] share their offsets.  A launch with fewer
-    than two rows (n * ho * wo) has no unbiased variance: refused."""
-    segs, off = [], 0
+    statistics and the moving layout share their offsets (Plan.stats_size).
+    A launch with fewer than two rows (n * ho * wo) has no unbiased variance:
+    refused."""
+    segs = []
     for u in units:
         rows = int(batch) * u.ho * u.wo
         if rows < 2:
             raise ValueError(f"BN moving statistics need at least 2 rows per channel: {u.name} has "
                              f"{rows} at batch {batch} ({u.ho}x{u.wo} outputs)")
-        segs.append((off, off, rows, u.cout))
-        off += 2 * u.cout
+        segs.append((u.soff, u.soff, rows, u.cout))
     return segs
 
 

@@ -3,9 +3,9 @@ test_step_audit.py for the CPU checks of these helpers and
 test_gpu_step_audit.py for the audits of the engine).
 
 jr.lanes.schedule orders the calls of a step by the resources they DECLARE
-(Call.reads / Call.writes).  This module says what memory each resource key
-names (regions), lists every device tensor an engine owns (universe), and
-drives a call list one call at a time over a shadow copy of that memory, so a
+(Call.reads / Call.writes).  What memory each resource key names and which
+device tensors an engine owns is the engines' own knowledge (jr.engine:
+Replica.regions, Replica.universe, Region); this module drives a call list one call at a time over a shadow copy of that memory, so a
 test can ask which bytes a call really wrote (write-set audit) and whether it
 read anything it did not declare (read-set audit, by poisoning everything
 else with quiet NaNs).  trace / first_difference digest every declared write
@@ -33,6 +33,8 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from jr.engine import Region
+
 WRITE_IMPLIES_READ = True
 
 # quiet-NaN bit patterns by dtype, as (same-size integer dtype, pattern)
@@ -44,183 +46,11 @@ SCRATCH_KEYS = ("ws", "wss")
 MAX_FINDINGS = 20
 
 
-@dataclasses.dataclass(frozen=True)
-class Region:
-    """Elements start + r * stride + j (r < rows, j < width) of the flat tensor `name`."""
-    name: str
-    start: int
-    width: int
-    rows: int = 1
-    stride: int = 0
-
-    def contains(self, elem: int) -> bool:
-        e = elem - self.start
-        if e < 0:
-            return False
-        if self.rows == 1:
-            return e < self.width
-        return e // self.stride < self.rows and e % self.stride < self.width
-
-
-# ------------------------------------------------------- engine: resource map
+# ---------------------------------------------------------------- exclusions
 # per-lane raw-gradient scratch: sized for the largest launch, so a digest of
 # the whole buffer also sees what earlier launches of THAT lane left behind --
 # comparable between two runs of one list, not between a one- and a two-lane list
 LANE_SCRATCH = ("draw", "draw2", "drawb", "drawp")
-
-
-def _units(engine) -> dict:
-    return {u.first.idx: u for u in engine.cunits}
-
-
-def _slice_region(engine, name: str, tensor, buf: int, c_off: int) -> Region:
-    g = engine.g
-    C = engine.in_stride if (buf == g.input_buf and name.startswith("acts")) else g.bufs[buf].c
-    offs = engine.slices[buf]
-    k = offs.index(c_off)
-    width = (offs[k + 1] if k + 1 < len(offs) else C) - c_off
-    return Region(name, c_off, width, tensor.numel() // C, C)
-
-
-def _stat_offsets(engine) -> dict:
-    out, off = {}, 0
-    for u in engine.cunits:
-        out[u.first.idx] = off
-        off += 2 * u.cout
-    return out
-
-
-def slab_regions(lists) -> dict:
-    """("slab", uid) -> (offset, count) in fp32 words of the deferred
-    filter-gradient arena of one call-list build, read from the bound
-    jr_conv2d_bwd_filter_slabs calls (arena pointer and byte count)."""
-    arena = slab_arena(lists)
-    out = {}
-    if arena is None:
-        return out
-    for c in lists[1] or ():
-        if c.name == "conv_wgrad" and getattr(c.fn, "__name__", "") == "jr_conv2d_bwd_filter_slabs":
-            key = next(k for k in c.writes if k[0] == "slab")
-            out[key] = ((int(c.args[4]) - arena.data_ptr()) // 4, int(c.args[5]) // 4)
-    return out
-
-
-def slab_arena(lists):
-    if lists is None:
-        return None
-    return next((t for t in lists[3] if isinstance(t, torch.Tensor) and t.dtype == torch.float32), None)
-
-
-def regions(engine, key, lists=None) -> List[Region]:
-    """The memory a resource key of jr.Engine's call lists names.  `lists`:
-    the _build_calls tuple the key comes from (needed for ("slab", uid): the
-    arena belongs to one build).  An unknown key raises KeyError."""
-    e, kind = engine, key[0]
-    if kind == "a":
-        return [_slice_region(e, f"acts[{key[1]}]", e.acts[key[1]], key[1], key[2])]
-    if kind == "d":
-        return [_slice_region(e, f"dacts[{key[1]}]", e.dacts[key[1]], key[1], key[2])]
-    if kind == "r":
-        u, off = _units(e)[key[1]], _stat_offsets(e)[key[1]]
-        return [Region(f"raw[{key[1]}]", 0, e.raw_unit[key[1]].numel()), Region("stats", off, 2 * u.cout)]
-    if kind == "g":
-        # a tensor's resource includes the alignment padding behind it (jr.init.ALIGN):
-        # the optimizer walks the whole flat buffer, so the ("g", ...) keys together
-        # are all of `grads`
-        from jr.init import ALIGN
-        pad = lambda n: (n + ALIGN - 1) // ALIGN * ALIGN     # noqa: E731
-        if key[1] == "dense":
-            sizes = {name: (off, pad(size)) for name, _, off, size in e.plan.layout}
-            return [Region("grads", *sizes["dense/kernel"]), Region("grads", *sizes["dense/bias"])]
-        u = _units(e)[key[1]]
-        out = [Region("grads", u.koff, pad(u.kh * u.kw * u.cin * u.cout))]
-        out += [Region("grads", e.plan.poff[f"batch_normalization_{m.idx + 1}/beta"], pad(m.cout)) for m in u.members]
-        return out
-    if kind == "p":
-        return [Region("params", 0, e.params.numel())]
-    if kind == "acc":
-        out = [Region("accum", 0, e.accum.numel())]
-        return out + ([Region("adam_v", 0, e.adam_v.numel())] if e.adam_v is not None else [])
-    if kind == "w16":
-        return [Region(n, 0, getattr(e, n).numel()) for n in ("w_hwio", "w_t") if getattr(e, n, None) is not None]
-    if kind == "wmax":
-        return [Region("absmax", 0, 64 * len(e.cunits) * e.members)]
-    if kind == "dmax":
-        return [Region("absmax", 64 * (len(e.cunits) + e._arow[key[1]]), 64)]
-    if kind == "draw":
-        return [Region(f"draw_lane[{key[1]}]", 0, e.draw_lane[key[1]].numel())]
-    if kind == "draw2":
-        return [Region("draw_stem2", 0, e.draw_stem2.numel())]
-    if kind == "drawb":
-        return [Region(f"drawb[{key[1]}][{key[2]}]", 0, e.drawb[key[1]][key[2]].numel())]
-    if kind == "drawp":
-        return [Region(f"drawp_lane[{key[1]}]", 0, e.drawp_lane[key[1]].numel())]
-    if kind == "ap":
-        return [Region(f"aplanes[{key[1]}]", 0, e.aplanes[key[1]].numel())]
-    if kind == "slab":
-        off, n = slab_regions(lists)[key]
-        return [Region("slab_arena", off, n)]
-    if kind == "ws":
-        return [Region(f"ws_lane[{key[1]}]", 0, e.ws_lane[key[1]].numel())]
-    if kind == "wss":
-        return [Region("ws_stem", 0, e.ws_stem.numel())]
-    if kind == "am":
-        return [Region(f"argmax[{key[1]}]", 0, e.argmax[key[1]].numel())]
-    if kind == "feat":
-        return [Region("feat", 0, e.feat.numel())]
-    if kind == "head":
-        return [Region(n, 0, getattr(e, n).numel()) for n in ("logits", "probs", "loss")]
-    if kind == "lab":
-        return [Region("labels", 0, e.labels.numel())]
-    if kind == "dfeat":
-        return [Region("dfeat", 0, e.dfeat.numel())]
-    if kind == "gnorm":
-        return [Region(n, 0, getattr(e, n).numel()) for n in ("opt_partials", "opt_step_dev", "opt_hyper")]
-    if kind == "bn_moving":
-        return [Region("moving", 0, e.moving.numel())]
-    if kind == "frozen":
-        return [Region("frozen", 0, e.frozen.numel())]
-    if kind == "target":
-        return [Region("ig_target", 0, e.ig_target.numel())]
-    if kind == "dinput":
-        return [Region("dinput", 0, e.dinput.numel())]
-    raise KeyError(f"step_audit.regions: unknown resource key {key!r}")
-
-
-def universe(engine, lists=None) -> Dict[str, torch.Tensor]:
-    """Every device tensor the engine owns, by name; with `lists` (a
-    _build_calls tuple) also that build's slab arena and device tables."""
-    e, out = engine, {}
-
-    def put(name, t):
-        if isinstance(t, torch.Tensor):
-            out[name] = t
-
-    for name in ("stats", "moving", "frozen", "feat", "logits", "probs", "labels", "loss", "params", "grads", "accum",
-                 "adam_v", "dfeat", "draw_stem2", "w_hwio", "w_t", "wprep_table", "absmax", "absmax_table", "ws_stem",
-                 "dinput", "x0", "attr_acc", "ig_target", "opt_partials", "opt_hyper", "opt_step_dev",
-                 "_opt_ranges_dev", "_aug_ws", "_aug_tab", "_warp_tab"):
-        put(name, getattr(e, name, None))
-    for name in ("acts", "dacts", "draw_lane", "drawp_lane", "ws_lane"):
-        for k, t in enumerate(getattr(e, name, None) or ()):
-            put(f"{name}[{k}]", t)
-    for name, short in (("raw_unit", "raw"), ("argmax", "argmax"), ("aplanes", "aplanes")):
-        for k, t in (getattr(e, name, None) or {}).items():
-            put(f"{short}[{k}]", t)
-    for s, row in enumerate(getattr(e, "drawb", None) or ()):
-        for k, t in enumerate(row):
-            put(f"drawb[{s}][{k}]", t)
-    for B, tab in (getattr(e, "_bn_tables", None) or {}).items():
-        put(f"bn_table[{B}]", tab[0])
-    if lists is not None:
-        arena = slab_arena(lists)
-        put("slab_arena", arena)
-        k = 0
-        for t in lists[3]:
-            if isinstance(t, torch.Tensor) and t is not arena:
-                put(f"keep_table[{k}]", t)
-                k += 1
-    return out
 
 
 def never_poison(name: str, t: torch.Tensor) -> bool:
@@ -415,7 +245,7 @@ class SerialAudit:
 def engine_audit(engine, lists, poison: bool = True, phases=(0, 1, 2)) -> Tuple[List[str], List[str]]:
     """SerialAudit over a jr.Engine's call lists (a _build_calls tuple), in issue order."""
     calls = [c for p in phases for c in (lists[p] or ())]
-    audit = SerialAudit(universe(engine, lists), lambda k: regions(engine, k, lists), torch.cuda.synchronize)
+    audit = SerialAudit(engine.universe(lists), lambda k: engine.regions(k, lists), torch.cuda.synchronize)
     return audit.run(calls, poison)
 
 
@@ -448,7 +278,7 @@ class Tracer:
 
     def __init__(self, engine, lists, steps: int):
         self.engine, self.steps, self.step = engine, steps, 0
-        uni = universe(engine, lists)
+        uni = engine.universe(lists)
         self.rows, self.phases = [], []
         n = 1
         for p in range(3):
@@ -460,7 +290,7 @@ class Tracer:
                 for k in c.writes:
                     if k[0] in SCRATCH_KEYS:
                         continue
-                    vs = [region_view(uni[r.name], r) for r in regions(engine, k, lists)]
+                    vs = [region_view(uni[r.name], r) for r in engine.regions(k, lists)]
                     n = max(n, max(v.numel() for v in vs))
                     views.append((len(self.rows), vs))
                     self.rows.append((c.idx, c.name, c.lane, k))

@@ -275,25 +275,9 @@ def test_a_skipped_group_leaves_nothing_behind():
 
 
 # ---------------------------------------------------------------------- step audit
-# resource keys tests/step_audit.py does not know: the accumulator, and those of the keywords its own
-# audits leave off (the weight average, dropout)
-EXTRA = {"gacc": ("gacc",), "ema": ("ema", "ema_state"), "drop": ("drop_state",), "feat_drop": ("feat_drop",)}
-
-
 def _audit(e, lists, phases=(0, 1, 2)):
     import step_audit
-    uni = step_audit.universe(e, lists)
-    for names in EXTRA.values():
-        for n in names:
-            uni[n] = getattr(e, n)
-
-    def region_of(key):
-        if key[0] in EXTRA:
-            return [step_audit.Region(n, 0, getattr(e, n).numel()) for n in EXTRA[key[0]]]
-        return step_audit.regions(e, key, lists)
-
-    calls = [c for p in phases for c in (lists[p] or ())]
-    return step_audit.SerialAudit(uni, region_of, torch.cuda.synchronize).run(calls, True)
+    return step_audit.engine_audit(e, lists, True, phases)
 
 
 @pytest.mark.parametrize("phase", ["open", "inside", "close", "flush"])

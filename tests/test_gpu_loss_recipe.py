@@ -463,15 +463,7 @@ def test_audit_of_one_step_with_everything_on():
     eng.synchronize()
     torch.cuda.synchronize()
     lists = eng._build_calls(B, training=True)
-
-    def region_of(key):
-        if key == ("drop",):
-            return [step_audit.Region("drop_state", 0, eng.drop_state.numel())]
-        if key == ("feat_drop",):
-            return [step_audit.Region("feat_drop", 0, eng.feat_drop.numel())]
-        return step_audit.regions(eng, key, lists)
-    tensors = dict(step_audit.universe(eng, lists), drop_state=eng.drop_state, feat_drop=eng.feat_drop)
-    audit = step_audit.SerialAudit(tensors, region_of, torch.cuda.synchronize)
+    audit = step_audit.SerialAudit(eng.universe(lists), lambda k: eng.regions(k, lists), torch.cuda.synchronize)
     t0 = time.perf_counter()
     calls = [c for p in lists[:3] for c in p]
     wfind, rfind = audit.run(calls)

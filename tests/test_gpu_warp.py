@@ -247,7 +247,7 @@ def test_engines_set_batch_warp():
     def buffers(e):
         e.synchronize()
         full = A.bits(e.acts[e.g.input_buf])
-        stride = e.act_ms[e.g.input_buf] if e.members > 1 else count
+        stride = e.act_ms[e.g.input_buf]
         return [full[m * stride:m * stride + count] for m in range(e.members)]
 
     both, warp_only, colour_only = direct(tab, wtab), direct(augment.identity(B), wtab), direct(tab, None)

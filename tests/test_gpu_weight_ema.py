@@ -501,13 +501,7 @@ def test_audit_of_one_ema_step(batch):
     eng.synchronize()
     torch.cuda.synchronize()
     lists = eng._build_calls(2)
-
-    def region_of(key):
-        if key == ("ema",):
-            return [step_audit.Region("ema", 0, eng.ema.numel()), step_audit.Region("ema_state", 0, eng.ema_state.numel())]
-        return step_audit.regions(eng, key, lists)
-    tensors = dict(step_audit.universe(eng, lists), ema=eng.ema, ema_state=eng.ema_state)
-    audit = step_audit.SerialAudit(tensors, region_of, torch.cuda.synchronize)
+    audit = step_audit.SerialAudit(eng.universe(lists), lambda k: eng.regions(k, lists), torch.cuda.synchronize)
     wfind, rfind = audit.run(list(lists[2]))
     assert ("ema",) in audit.keys
     assert not wfind, "\n".join(wfind)

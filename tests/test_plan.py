@@ -77,3 +77,45 @@ def test_reverse_walk_finalizes_suffixes(g, fuse):
         suffix = {off for _, _, off, _ in plan.layout if off >= u.koff}
         assert suffix <= final, (u.name, sorted(suffix - final)[:3])
     assert final == {off for _, _, off, _ in plan.layout}
+
+
+@pytest.mark.parametrize("fuse", [True, False])
+@pytest.mark.parametrize("res", [75, 107, 299])
+def test_statistics_layout_is_the_plans(res, fuse):
+    """The statistics layout, [mean(c) | invstd(c)] per conv launch in plan order: the plan's offsets
+    against a walk of this test's own; they tile [0, stats_size) without gap or overlap; bn_layers
+    names every conv2d_bn layer's slices inside its launch's block; and bn_moving_segments returns
+    what that walk gives at batch 1 (refused where a launch has a single row: the 1x1 blocks of
+    75^2), 2 and 64."""
+    from jr.plan import bn_moving_segments
+    graph = build_inception_v3(res, res)
+    plan = build_plan(graph, fuse_siblings=fuse)
+    want, off = [], 0
+    for u in plan.units:
+        want.append(off)
+        off += 2 * sum(n.cout for n in u.members)
+    assert [u.soff for u in plan.units] == want and plan.stats_size == off
+    assert off == 2 * sum(n.cout for n in graph.convs)
+    covered = np.zeros(plan.stats_size, np.int32)
+    for u in plan.units:
+        covered[u.soff:u.soff + 2 * u.cout] += 1
+    assert np.all(covered == 1)
+    layers = list(plan.bn_layers())
+    assert sorted(n.idx for n, _, _ in layers) == [n.idx for n in graph.convs]
+    covered[:] = 0
+    for n, om, oi in layers:
+        u = plan.unit_of[n.idx]
+        co = u.col_off[u.members.index(n)]
+        assert (om, oi) == (u.soff + co, u.soff + u.cout + co)
+        covered[om:om + n.cout] += 1
+        covered[oi:oi + n.cout] += 1
+    assert np.all(covered == 1)
+    for batch in (1, 2, 64):
+        rows = [batch * u.ho * u.wo for u in plan.units]
+        if min(rows) < 2:
+            assert (res, batch) == (75, 1)
+            with pytest.raises(ValueError, match="at least 2 rows"):
+                bn_moving_segments(plan.units, batch)
+        else:
+            segs = [(o, o, r, u.cout) for o, r, u in zip(want, rows, plan.units)]
+            assert bn_moving_segments(plan.units, batch) == segs
